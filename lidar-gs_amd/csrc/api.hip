@@ -60,9 +60,12 @@ __global__ void __launch_bounds__(256) k_cnt_bytes(const uint8_t* __restrict__ p
     for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
     if ((threadIdx.x & 63) == 0 && c) atomicAdd(out, (unsigned long long)c);
 }
+}  // namespace
+
 // queued behind a forward's last launch (see above); `view` = the selection a backward on these buffers will make, or NULL
-void queue_counters(const uint32_t* totals, const uint8_t* flags, size_t R, size_t flags_stride, int flags_planes, const uint8_t* touched, size_t P,
-                    const lg::RenderBwdArgs* view, hipStream_t s) {
+void lg::note_forward(size_t P, size_t R, const FrameLayout& L, const uint32_t* totals, const uint8_t* flags, const uint8_t* touched,
+                      const RenderBwdArgs* view, hipStream_t s) {
+    g_counters[0] = (long long)P; g_counters[2] = (long long)R; g_counters[4] = L.TH; g_counters[5] = L.grid.num_tiles(); g_counters[7] = L.S;
     g_counters[1] = g_counters[3] = g_counters[8] = g_counters[9] = -1;
     g_counters[6] = flags ? -1 : 0;
     t_cnt.pending = false;
@@ -70,7 +73,7 @@ void queue_counters(const uint32_t* totals, const uint8_t* flags, size_t R, size
     unsigned long long* d = t_cnt.dev;
     if (hipMemsetAsync(d, 0, 8 * sizeof *d, s) != hipSuccess) return;
     hipLaunchKernelGGL(k_cnt_diag, dim3(1), dim3(64), 0, s, reinterpret_cast<const unsigned long long*>(totals + LG_TOTALS_DIAG_WORD), d);
-    if (flags && R) hipLaunchKernelGGL(k_cnt_bytes, dim3(512, flags_planes), dim3(256), 0, s, flags, R, flags_stride, d + 2);
+    if (flags && R) hipLaunchKernelGGL(k_cnt_bytes, dim3(512, L.grid.waves_per_tile), dim3(256), 0, s, flags, R, L.Rp, d + 2);
     if (touched && P) hipLaunchKernelGGL(k_cnt_bytes, dim3(512, 1), dim3(256), 0, s, touched, P, (size_t)0, d + 3);
     if (view) lg::launch_count_backward_entries(*view, d + 4, s);
     t_cnt.host[5] = (flags && R ? 1u : 0u) | (touched && P ? 2u : 0u) | (view ? 4u : 0u);     // which of the counts exist (host-side word of the same page)
@@ -79,6 +82,7 @@ void queue_counters(const uint32_t* totals, const uint8_t* flags, size_t R, size
     t_cnt.pending = true;
 }
 
+namespace {
 int fail(int code, const char* fmt, const char* detail = "") {
     snprintf(g_err, sizeof g_err, fmt, detail);
     return code;
@@ -114,13 +118,6 @@ int forced_tile_rows() {
     }();
     return th;
 }
-// LIDARGS_NO_PRUNE=1 switches the conservative footprint pruning of the preprocess off (every tile / row of the reference rect is binned):
-// a diagnostic and a test instrument -- pruned entries are exactly those no pixel can take, so the results must not change.
-bool prune_footprints() {
-    static const bool on = [] { const char* e = getenv("LIDARGS_NO_PRUNE"); return !(e && atoi(e) != 0); }();
-    return on;
-}
-int tile_rows() { return forced_tile_rows() ? forced_tile_rows() : 4; }      // what non-adaptive callers (surfel variant) use
 
 // Tile height from the instance totals the preprocess accumulated for heights 4 / 8 / 16 / 32.  The blend costs the same for every
 // height (per-lane row test + contribution flags), the binning costs ~18 ns per 1000 instances, and a taller tile makes pass 1
@@ -148,8 +145,6 @@ int choose_tile_rows(const unsigned long long (&inst)[4], int height) {
 // address and cloned / offloaded / checkpointed saved buffers work (the backward rebuilds its view from (P, R, W*H)).
 // Which Gaussians have a gradient at all is a byte map IN the geometry buffer (GeomView::touched): every backward clears exactly their lines first.
 inline int encode_rendered(size_t R, int TH) { return (int)(((R + 3) & ~(size_t)3) | (size_t)(TH == 8 ? 1 : (TH == 16 ? 2 : (TH == 32 ? 3 : 0)))); }
-inline size_t rendered_capacity(int nr) { return (size_t)(nr & ~3); }
-inline int rendered_tile_rows(int nr) { return 4 << (nr & 3); }
 
 // One pinned 4-KB landing buffer and one event per host thread and device: the host waits for the copy alone, not for what
 // was queued behind it.
@@ -228,14 +223,6 @@ SegPlan plan_segments(size_t R, int waves_per_tile, int surfel, size_t patches =
     if (env_nrounds >= 0) { p.n_rounds = env_nrounds; for (int k = 0; k < env_nrounds; k++) p.rounds[k] = env_rounds[k]; }
     return p;
 }
-bool pass1_gated(const SegPlan& p, int S) { return p.n_rounds > 0 && p.rounds[0] < S; }
-
-// The backward blend walks the work list k_render_combine filled (lidargs_common.h WorkList) on every plain or column-wedge frame that
-// runs the segmented launches; forward_impl and backward_impl both decide with this.  LIDARGS_WORK_LISTS=0: the slot grid again (A/B, tests).
-bool backward_list(int S, size_t patches, bool fused) {
-    static const bool on = [] { const char* e = getenv("LIDARGS_WORK_LISTS"); return !e || atoi(e) != 0; }();
-    return on && lg::work_lists_fit(patches, S) && !fused && S > 1;
-}
 
 // Pass 1 in rounds of growing depth: the first segments of every list, then -- only for the patches some pixel of which is
 // still unsaturated -- the next ones, and so on.  In a street scene most patches saturate within a few hundred entries,
@@ -278,49 +265,19 @@ int ceil_log2(uint32_t n) {
     while ((1u << b) < n && b < 31) b++;
     return b;
 }
-}  // namespace
 
-// helpers shared with the surfel entry points (surfel_api.inc)
-namespace lg {
-int api_fail(int code, const char* msg) { return fail(code, "%s", msg); }
-int api_check_launch(hipStream_t s, int debug, const char* what) { return check_launch(s, debug, what); }
-int api_tile_rows() { return tile_rows(); }
-bool api_prune_footprints() { return prune_footprints(); }
-int api_ceil_log2(uint32_t n) { return ceil_log2(n); }
-int api_range_sort_bits() { return range_sort_bits(); }
-SegPlan api_plan_segments(size_t R, int waves_per_tile, int surfel) { return plan_segments(R, waves_per_tile, surfel); }
-int api_read_words_zero_behind(const uint32_t* dev, int n, uint32_t* out, void* zero, size_t zero_bytes, hipStream_t s) {
-    if (n > HostRead::WORDS || !t_host_read.ready()) return (int)hipErrorOutOfMemory;
-    hipError_t e = hipMemcpyAsync(t_host_read.words, dev, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipEventRecord(t_host_read.copied, s);
-    if (e == hipSuccess && zero && zero_bytes) e = hipMemsetAsync(zero, 0, zero_bytes, s);
-    if (e == hipSuccess) e = hipEventSynchronize(t_host_read.copied);
-    if (e == hipSuccess) memcpy(out, t_host_read.words, (size_t)n * sizeof(uint32_t));
-    return (int)e;
-}
 // The same read in two halves: the copy is queued at `begin`, more work is queued behind it, and `end` waits for the copy only.
-int api_read_words_begin(const uint32_t* dev, int n, hipStream_t s) {
+int read_words_begin(const uint32_t* dev, int n, hipStream_t s) {
     if (n > HostRead::WORDS || !t_host_read.ready()) return (int)hipErrorOutOfMemory;
     hipError_t e = hipMemcpyAsync(t_host_read.words, dev, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipEventRecord(t_host_read.copied, s);
     return (int)e;
 }
-int api_read_words_end(int n, uint32_t* out) {
+int read_words_end(int n, uint32_t* out) {
     const hipError_t e = hipEventSynchronize(t_host_read.copied);
     if (e == hipSuccess) memcpy(out, t_host_read.words, (size_t)n * sizeof(uint32_t));
     return (int)e;
 }
-void api_note_forward(long long P, long long R, int TH, int tiles, int S, const void* totals, const uint8_t* flags, size_t flags_stride,
-                      int flags_planes, const uint8_t* touched, hipStream_t s) {   // diagnostics only (lidargs_last_counters)
-    g_counters[0] = P; g_counters[2] = R; g_counters[4] = TH; g_counters[5] = tiles; g_counters[7] = S;
-    queue_counters((const uint32_t*)totals, flags, (size_t)R, flags_stride, flags_planes, touched, (size_t)P, nullptr, s);
-}
-int api_encode_rendered(size_t R, int TH) { return encode_rendered(R, TH); }
-size_t api_rendered_capacity(int nr) { return rendered_capacity(nr); }
-int api_rendered_tile_rows(int nr) { return rendered_tile_rows(nr); }
-}  // namespace lg
-
-namespace {
 
 // ---- per-stage event timing -------------------------------------------------------------------
 // While enabled, every forward/backward call records one HIP event per stage boundary on the op's
@@ -334,36 +291,207 @@ struct Profiler {
     int ncalls = 0;          // calls recorded since enable
     Call* calls = nullptr;
     Call* cur = nullptr;
-    void begin(hipStream_t s, int kind) {
-        cur = nullptr;
-        if (!enabled) return;
-        if (seen[kind]++ % every != 0) return;
-        if (!calls) calls = new Call[MAX_CALLS];
-        cur = &calls[ncalls % MAX_CALLS];
-        ncalls++;
-        if (!cur->created) { for (auto& e : cur->ev) (void)hipEventCreate(&e); cur->created = true; }
-        cur->n = 0;
-        (void)hipEventRecord(cur->ev[0], s);
-    }
-    void mark(const char* name, hipStream_t s) {
-        if (!cur || cur->n >= LIDARGS_MAX_STAGES) return;
-        cur->names[cur->n] = name;
-        (void)hipEventRecord(cur->ev[cur->n + 1], s);
-        cur->n++;
-    }
 };
 Profiler g_prof;   // process-wide: autograd runs backward on its own thread
 }  // namespace
-namespace lg {
-void api_prof_begin(hipStream_t s, int kind) { g_prof.begin(s, kind); }
-void api_prof_mark(const char* name, hipStream_t s) { g_prof.mark(name, s); }
-}  // namespace lg
-namespace {
 
-struct Common {
-    int P, W, H;
-    lg::TileGrid grid;
-};
+// helpers shared with the other entry-point files
+namespace lg {
+int api_fail(int code, const char* msg) { return fail(code, "%s", msg); }
+int api_check_launch(hipStream_t s, int debug, const char* what) { return check_launch(s, debug, what); }
+int api_read_words_zero_behind(const uint32_t* dev, int n, uint32_t* out, void* zero, size_t zero_bytes, hipStream_t s) {
+    hipError_t e = (hipError_t)read_words_begin(dev, n, s);
+    if (e == hipSuccess && zero && zero_bytes) e = hipMemsetAsync(zero, 0, zero_bytes, s);
+    return e == hipSuccess ? read_words_end(n, out) : (int)e;
+}
+// LIDARGS_NO_PRUNE=1 switches the conservative footprint pruning of the preprocess off (every tile / row of the reference rect is binned):
+// a diagnostic and a test instrument -- pruned entries are exactly those no pixel can take, so the results must not change.
+bool prune_footprints() {
+    static const bool on = [] { const char* e = getenv("LIDARGS_NO_PRUNE"); return !(e && atoi(e) != 0); }();
+    return on;
+}
+int tile_rows() { return forced_tile_rows() ? forced_tile_rows() : 4; }      // what non-adaptive callers (surfel variant) use
+
+FrameLayout frame_layout(int num_rendered, int W, int H, int col_lo, int col_hi, FrameVariant variant) {
+    const bool surfel = variant == FRAME_SURFEL, shell = variant == FRAME_SHELL;
+    FrameLayout L;
+    L.TH = 4 << (num_rendered & 3);                       // (encode_rendered)
+    L.Rp = (size_t)(num_rendered & ~3);
+    L.grid = make_grid(W, H, L.TH);
+    if (col_lo >= 0) { L.grid.x_lo = col_lo / LG_TILE_W; L.grid.x_n = (col_hi + LG_TILE_W - 1) / LG_TILE_W - L.grid.x_lo; }   // the blends cover the wedge's own tile columns only
+    L.patches = (size_t)L.grid.num_tiles() * L.grid.waves_per_tile;
+    L.plan = surfel ? plan_segments(L.Rp, L.grid.waves_per_tile, 1) : plan_segments(L.Rp, L.grid.waves_per_tile, 0, (size_t)L.grid.window_patches());
+    L.S = choose_segments(L.Rp, L.plan.max_segments);
+    L.fused = L.plan.fused && !shell;                     // the plain frame (a range shell's two phases keep the launches; surfel plans are never fused)
+    L.gated = L.fused || (L.plan.n_rounds > 0 && L.plan.rounds[0] < L.S);
+    L.flags = L.fused || L.S > 1 || shell || surfel;      // a shell's backward always reads the flags; the surfel forward always runs pass 1
+    // The backward blend walks the work list k_render_combine filled (lidargs_common.h WorkList) on every plain or column-wedge frame that
+    // runs the segmented launches (a shell's backward keeps the slot grid).  LIDARGS_WORK_LISTS=0: the slot grid again (A/B, tests).
+    static const bool lists = [] { const char* e = getenv("LIDARGS_WORK_LISTS"); return !e || atoi(e) != 0; }();
+    L.work_list = lists && !surfel && !shell && work_lists_fit(L.patches, L.S) && !L.fused && L.S > 1;
+    L.buf = surfel ? SURFEL_BUFFERS : GAUSS_BUFFERS;
+    return L;
+}
+void prof_begin(hipStream_t s, int kind) {
+    Profiler& p = g_prof;
+    p.cur = nullptr;
+    if (!p.enabled) return;
+    if (p.seen[kind]++ % p.every != 0) return;
+    if (!p.calls) p.calls = new Profiler::Call[Profiler::MAX_CALLS];
+    p.cur = &p.calls[p.ncalls % Profiler::MAX_CALLS];
+    p.ncalls++;
+    if (!p.cur->created) { for (auto& e : p.cur->ev) (void)hipEventCreate(&e); p.cur->created = true; }
+    p.cur->n = 0;
+    (void)hipEventRecord(p.cur->ev[0], s);
+}
+void prof_mark(const char* name, hipStream_t s) {
+    Profiler::Call* c = g_prof.cur;
+    if (!c || c->n >= LIDARGS_MAX_STAGES) return;
+    c->names[c->n] = name;
+    (void)hipEventRecord(c->ev[c->n + 1], s);
+    c->n++;
+}
+
+// The binning sequence of both rasterizers' forwards (lidargs_common.h BinSpec): the preprocess has run and left the instance totals,
+// key span and spans in the geometry buffer.
+int bin_frame(const BinSpec& spec, const GeomView& geom, uint2* ranges, size_t P, int W, int H, int col_lo, int col_hi, bool compact,
+              char* (*binning_alloc)(void*, size_t), void* binning_user, int debug, hipStream_t stream, BinnedFrame* out) {
+    const bool enqueue_only = spec.capacity > 0, surfel = spec.variant == FRAME_SURFEL;
+    // 1. range sort of the Gaussians on the low 31 key bits (8 + 8 + 8 + 7 by default; LIDARGS_RANGE_SORT_BITS=11 gives 11 + 10 + 10, slower
+    //    at 2 M keys): ranges are positive floats (bit 31 clear), and a culled Gaussian's key 0xFFFFFFFF still sorts behind every
+    //    valid one (valid keys are < bits(lidar_far) < 0x7FFFFFFF)
+    //    Everything the host decides on -- the instance totals per tile height -- is known once the preprocess has run: their copy
+    //    (2 KB into pinned memory) is queued here, the sort behind it, and the host waits for the copy while the sort runs.
+    if (!enqueue_only) LG_HIP((hipError_t)read_words_begin(geom.totals, LG_TOTALS_READ_WORDS, stream));
+    RadixTail span_tail;                                               // the sort's last pass leaves the spans in range order as well
+    span_tail.src = geom.spans; span_tail.dst = geom.span_sorted; span_tail.mode = compact ? 1 : 2;
+    const uint32_t* ids_sorted = geom.id_a;
+    int first_side = 1;                                                // where the first pass left the pairs (0: a side, 1: b side)
+    // The sort runs on key - kmin (the preprocess left ~kmin and kmax in the totals' slots): a frame's ranges span far fewer than 31 key
+    // bits -- 2 m .. 80 m is 26 -- and every 8-9 bits less is a pass (three launches) less.  kmin is rounded down to a multiple of 256,
+    // so the first pass (the key's own low byte) needs no host knowledge and is queued right behind the totals' copy; the host then
+    // reads the span and queues as many more passes as it has bits.
+    // Round 5: frames of up to 4 M Gaussians sort in ONE bucket pass + one launch that finishes every bucket in LDS (binning.hip
+    // launch_range_sort_buckets), with the frame's range span folded on the device: queued whole behind the totals' copy.
+    const bool buckets = range_sort_buckets_ok(P);
+    if (buckets) {
+        launch_range_sort_buckets(geom.key_a, geom.key_b, geom.id_a, geom.id_b, P, geom.scratch, geom.totals + LG_TOTALS_KEYSPAN_WORD, span_tail, stream);
+        LG_STAGE_CHECK("range sort");
+    } else if (enqueue_only) {                                         // no host read: all 31 bits of the raw key
+        const int side = launch_radix_sort_pairs(geom.key_a, geom.key_b, geom.id_a, geom.id_b, P, 31, geom.scratch, stream,
+                                                 range_sort_bits(), nullptr, SORT_MAX_RADIX_BITS, true, span_tail);   // (scratch carved for 11-bit digits; ids = positions)
+        ids_sorted = side ? geom.id_b : geom.id_a;
+        LG_STAGE_CHECK("range sort");
+    } else {
+        // (its result side is kept: one pass of the general form ends on the b side, the single-launch form of small inputs on the a side)
+        first_side = launch_radix_sort_pairs(geom.key_a, geom.key_b, geom.id_a, geom.id_b, P, 8, geom.scratch, stream, 8, nullptr,
+                                             SORT_MAX_RADIX_BITS, true);
+        LG_STAGE_CHECK("range sort, first pass");
+    }
+
+    // 2. the one host wait (R3/cr/rasterizer_impl.cu:292), for a copy that was queued before the sort: the instance totals for tile
+    //    heights 4 / 8 / 16 / 32 -> tile height, R; then the instance offsets in range order for that height.  The device is still
+    //    sorting while the host decides and queues what follows (the packed gradient lines are zeroed by the preprocess itself, so
+    //    there is no fill to queue behind the copy any more, and no guess of the tile height).
+    uint32_t totals_h[LG_TOTALS_READ_WORDS];                           // the slots of 64-bit instance totals the preprocess filled
+    if (!enqueue_only) {
+        LG_HIP((hipError_t)read_words_end(LG_TOTALS_READ_WORDS, totals_h));
+        if (!buckets) {   // the rest of the range sort: bits [8, bits of (kmax - kmin + 1)) in passes of at most 9 bits; at least one pass, for the tail
+            uint32_t kinv = 0u, kmax = 0u;
+            for (int slot = 0; slot < LG_INST_SLOTS; slot++) {
+                kinv = std::max(kinv, totals_h[LG_TOTALS_KEYSPAN_WORD + 2 * slot]); kmax = std::max(kmax, totals_h[LG_TOTALS_KEYSPAN_WORD + 2 * slot + 1]);
+            }
+            KeyBias kb;
+            kb.kmin = (~kinv) & ~255u;                                      // a multiple of 256: (key - kmin) & 255 == key & 255
+            if (kmax < kb.kmin) { kb.kmin = 0u; kmax = 0u; }               // no visible Gaussian: every key is the culled one
+            kb.cull = ((kmax - kb.kmin) | 255u) + 1u;                       // above every valid key - kmin in the bits the later passes sort on
+            int bits = 32 - __builtin_clz(kb.cull | 1u);
+            if (bits < 9) bits = 9;
+            static const int env_full = [] { const char* e = getenv("LIDARGS_RANGE_SORT_FULL"); return e ? atoi(e) : 0; }();   // 1: always 31 bits (A/B)
+            if (env_full && !surfel) { bits = 32; kb.kmin = 0u; kb.cull = 0xFFFFFFFFu; }
+            uint32_t* const k_in = first_side ? geom.key_b : geom.key_a; uint32_t* const k_out = first_side ? geom.key_a : geom.key_b;
+            uint32_t* const v_in = first_side ? geom.id_b : geom.id_a; uint32_t* const v_out = first_side ? geom.id_a : geom.id_b;
+            const int side = launch_radix_sort_pairs(k_in, k_out, v_in, v_out, P, bits, geom.scratch, stream,
+                                                     bits > 26 ? 8 : 9, nullptr, SORT_MAX_RADIX_BITS, false, span_tail, 8, &kb);
+            ids_sorted = side ? v_out : v_in;
+            LG_STAGE_CHECK("range sort");
+        }
+    }
+    prof_mark("range_sort", stream);
+    int TH = spec.tile_rows;
+    size_t R;
+    uint32_t* status_dev = geom.totals + LG_TOTALS_STATUS_WORD;
+    if (!enqueue_only) {
+        unsigned long long inst[4] = {0, 0, 0, 0};
+        for (int slot = 0; slot < LG_INST_SLOTS; slot++) {
+            unsigned long long v[4];
+            memcpy(v, totals_h + LG_TOTALS_SLOT_WORD + 8 * slot, sizeof v);
+            inst[0] += v[0]; inst[1] += v[1]; inst[2] += v[2]; inst[3] += v[3];
+        }
+        if (!TH) TH = choose_tile_rows(inst, H);                       // 4, 8, 16 or 32
+        // (the surfel preprocess sums the instances of its one tile height in word 0 of each slot)
+        const unsigned long long R64 = (surfel || TH == 4) ? inst[0] : (TH == 8 ? inst[1] : (TH == 16 ? inst[2] : inst[3]));
+        if (R64 > (unsigned long long)std::numeric_limits<int>::max() - 4ull) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "%s: instance count overflows int", spec.what);
+        R = (size_t)R64;
+        launch_instance_offsets(geom.span_sorted, compact, TH, geom.block_off, geom.totals, P, stream, false);   // (the host has R from the preprocess's totals; the emit adds the block sums up itself)
+        LG_STAGE_CHECK("instance scan");
+    } else {
+        // the capacity, rounded up to the multiple of 4 `num_rendered` can carry, stands in for the count everywhere on the host: the
+        // emit's cap, k_finish_totals' cap, the tile sort, the tile ranges and the buffer carving all see this ONE number (round 2
+        // sorted and ranged only the unrounded capacity: need in (capacity, rounded] dropped instances with no overflow flag)
+        R = ((size_t)spec.capacity + 3) & ~(size_t)3;
+        launch_instance_offsets(geom.span_sorted, compact, TH, geom.block_off, geom.totals, P, stream);
+        LG_STAGE_CHECK("instance scan");
+        launch_finish_totals(geom.totals, reinterpret_cast<const unsigned long long*>(geom.totals + LG_TOTALS_SLOT_WORD), (uint32_t)R, status_dev, stream);
+        if (spec.status_host) LG_HIP(hipMemcpyAsync(spec.status_host, status_dev, LG_STATUS_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    }
+    const uint32_t* R_dev = enqueue_only ? status_dev + 1 : nullptr;   // instances binned = min(needed, capacity), on the device
+    prof_mark("scan+readback", stream);
+
+    // everything a later call on these buffers derives (plan, carving, flag stride) comes from the returned int alone
+    const int rendered = encode_rendered(R, TH);
+    const FrameLayout& L = out->L = frame_layout(rendered, W, H, col_lo, col_hi, spec.variant);
+    out->R = R;
+    char* bin_p = binning_alloc(binning_user, L.bin_carve(nullptr, nullptr));
+    if (!bin_p) return fail(LIDARGS_ERR_ALLOC, "%s: binning allocator returned NULL", spec.what);
+    BinView& bin = out->bin;
+    L.bin_carve(bin_p, &bin);
+
+    // 3. emit instances in range order, bin them by tile (stable); 16-bit tile keys whenever the tile ids fit (LIDARGS_TILE_KEY32=1: A/B)
+    static const bool key32 = [] { const char* e = getenv("LIDARGS_TILE_KEY32"); return e && atoi(e) != 0; }();
+    const int tiles = L.grid.num_tiles();
+    const bool key16 = tiles <= 65536 && (surfel || !key32);
+    if (R) {
+        // the sorted lists are wanted on the a side (the backward finds them there whatever the pass count was): a sort that will end on
+        // the other side -- an odd number of passes: images of at most 256 list tiles -- gets its input there, instead of two copies behind it
+        const int bits = ceil_log2((uint32_t)tiles);
+        const bool flip = radix_sort_result_side(R, bits) != 0;
+        uint32_t* const k_in = flip ? bin.tile_b : bin.tile_a; uint32_t* const k_out = flip ? bin.tile_a : bin.tile_b;
+        uint32_t* const v_in = flip ? bin.val_b : bin.val_a; uint32_t* const v_out = flip ? bin.val_a : bin.val_b;
+        launch_emit_instances(ids_sorted, geom.block_off, geom.span_sorted, compact, P, L.grid, k_in, v_in, stream,
+                              enqueue_only ? (uint32_t)L.Rp : 0xFFFFFFFFu, key16, ranges, !enqueue_only);
+        LG_STAGE_CHECK("emit");
+        prof_mark("emit", stream);
+        const int side = key16 ? launch_radix_sort_pairs16(reinterpret_cast<uint16_t*>(k_in), reinterpret_cast<uint16_t*>(k_out), v_in, v_out, R,
+                                                           bits, bin.scratch, stream, R_dev)
+                               : launch_radix_sort_pairs(k_in, k_out, v_in, v_out, R, bits, bin.scratch, stream, 0, R_dev);
+        const int bside = side ^ (flip ? 1 : 0);                       // 1: the result is NOT on the a side after all (never, by radix_sort_result_side)
+        if (bside) {   // keep the backward's view independent of the pass count: result always in (tile_a, val_a)
+            LG_HIP(hipMemcpyAsync(bin.tile_a, bin.tile_b, R * (key16 ? sizeof(uint16_t) : sizeof(uint32_t)), hipMemcpyDeviceToDevice, stream));
+            LG_HIP(hipMemcpyAsync(bin.val_a, bin.val_b, R * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+        }
+        LG_STAGE_CHECK("tile bin");
+        prof_mark("tile_bin", stream);
+    }
+    // (the launch also clears the counters of the backward's work list, where there is one: nothing before the blends touches them)
+    launch_tile_ranges(bin.tile_a, R, ranges, tiles, stream, R_dev, key16, bin.work, bin.work ? LG_WORK_REGIONS * LG_WORK_CNT_STRIDE : 0, R != 0);
+    LG_STAGE_CHECK("tile ranges");
+    prof_mark("ranges", stream);
+    return rendered;
+}
+}  // namespace lg
+
+namespace {
 
 int forward_impl(lidargs_alloc_fn geometry_alloc, void* geometry_user, lidargs_alloc_fn binning_alloc, void* binning_user,
                  lidargs_alloc_fn image_alloc, void* image_user, int P, const float* background, int width, int height,
@@ -399,13 +527,13 @@ int forward_impl(lidargs_alloc_fn geometry_alloc, void* geometry_user, lidargs_a
     if (P == 0) return 0;   // R3/rasterize_points.cu:87: outputs stay as the caller initialised them
 
     const lg::TileGrid grid4 = lg::make_grid(width, height, 4);        // the image buffer is laid out for the finest tiling
-    g_prof.begin(stream, 0);
+    lg::prof_begin(stream, 0);
 
-    char* geom_p = geometry_alloc(geometry_user, lg::geom_carve(nullptr, (size_t)P, nullptr));
+    char* geom_p = geometry_alloc(geometry_user, lg::geom_carve(nullptr, (size_t)P, lg::GAUSS_BUFFERS, nullptr));
     if (!geom_p) return fail(LIDARGS_ERR_ALLOC, "geometry allocator returned NULL%s");
     char* img_p = image_alloc(image_user, lg::img_carve(nullptr, width, height, grid4.num_tiles(), nullptr));
     if (!img_p) return fail(LIDARGS_ERR_ALLOC, "image allocator returned NULL%s");
-    lg::GeomView geom; lg::geom_carve(geom_p, (size_t)P, &geom);
+    lg::GeomView geom; lg::geom_carve(geom_p, (size_t)P, lg::GAUSS_BUFFERS, &geom);
     lg::ImgView img; lg::img_carve(img_p, width, height, grid4.num_tiles(), &img);
     LG_HIP(hipMemsetAsync(geom.totals, 0, LG_TOTALS_WORDS * sizeof(uint32_t), stream));
 
@@ -415,7 +543,7 @@ int forward_impl(lidargs_alloc_fn geometry_alloc, void* geometry_user, lidargs_a
     pp.near_f = near_f; pp.far_f = far_f; pp.shell_lo = shell_lo; pp.shell_hi = shell_hi;
     pp.tile_x_lo = 0; pp.tile_x_hi = grid4.tiles_x;
     pp.compact = lg::compact_spans(grid4.tiles_x, height) ? 1 : 0;
-    pp.prune = prune_footprints() ? 1 : 0;
+    pp.prune = lg::prune_footprints() ? 1 : 0;
     if (col_lo >= 0) {                                                   // column wedge: whole 16-pixel tile columns
         if (col_lo % LG_TILE_W || (col_hi % LG_TILE_W && col_hi != width) || col_hi <= col_lo || col_hi > width)
             return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward: a column wedge must be [multiple of 16, multiple of 16 or width)%s");
@@ -430,194 +558,61 @@ int forward_impl(lidargs_alloc_fn geometry_alloc, void* geometry_user, lidargs_a
     lg::launch_preprocess(pp, means3D, scales, rotations, opacities, colors_precomp, cov3D_precomp, beams, radii, radii_xy,
                           geom, &img, false, stream);                  // also fills the pixel-ray tables of the image buffer
     LG_STAGE_CHECK("preprocess");
-    g_prof.mark("preprocess", stream);
+    lg::prof_mark("preprocess", stream);
 
-    // 1. range sort of the Gaussians on the low 31 key bits (8 + 8 + 8 + 7 by default; LIDARGS_RANGE_SORT_BITS=11 gives 11 + 10 + 10, slower
-    //    at 2 M keys): ranges are positive floats (bit 31 clear), and a culled Gaussian's key 0xFFFFFFFF still sorts behind every
-    //    valid one (valid keys are < bits(lidar_far) < 0x7FFFFFFF)
-    //    Everything the host decides on -- the instance totals per tile height -- is known once the preprocess has run: their copy
-    //    (2 KB into pinned memory) is queued here, the sort behind it, and the host waits for the copy while the sort runs.
-    if (!enqueue_only) LG_HIP((hipError_t)lg::api_read_words_begin(geom.totals, LG_TOTALS_READ_WORDS, stream));
-    lg::RadixTail span_tail;                                           // the sort's last pass leaves the spans in range order as well
-    span_tail.src = geom.spans; span_tail.dst = geom.span_sorted; span_tail.mode = pp.compact ? 1 : 2;
-    const uint32_t* ids_sorted;
-    int first_side = 1;                                                // where the first pass left the pairs (0: a side, 1: b side)
-    // The sort runs on key - kmin (the preprocess left ~kmin and kmax in the totals' slots): a frame's ranges span far fewer than 31 key
-    // bits -- 2 m .. 80 m is 26 -- and every 8-9 bits less is a pass (three launches) less.  kmin is rounded down to a multiple of 256,
-    // so the first pass (the key's own low byte) needs no host knowledge and is queued right behind the totals' copy; the host then
-    // reads the span and queues as many more passes as it has bits.
-    // Round 5: frames of up to 4 M Gaussians sort in ONE bucket pass + one launch that finishes every bucket in LDS (binning.hip
-    // launch_range_sort_buckets), with the frame's range span folded on the device: queued whole behind the totals' copy.
-    const bool buckets = lg::range_sort_buckets_ok((size_t)P);
-    if (buckets) {
-        lg::launch_range_sort_buckets(geom.key_a, geom.key_b, geom.id_a, geom.id_b, (size_t)P, geom.scratch, geom.totals + LG_TOTALS_KEYSPAN_WORD, span_tail, stream);
-        ids_sorted = geom.id_a;
-        LG_STAGE_CHECK("range sort");
-        g_prof.mark("range_sort", stream);
-    } else if (enqueue_only) {                                         // no host read: all 31 bits of the raw key
-        const int side = lg::launch_radix_sort_pairs(geom.key_a, geom.key_b, geom.id_a, geom.id_b, (size_t)P, 31, geom.scratch, stream,
-                                                     range_sort_bits(), nullptr, lg::SORT_MAX_RADIX_BITS, true, span_tail);   // (scratch carved for 11-bit digits; ids = positions)
-        ids_sorted = side ? geom.id_b : geom.id_a;
-        LG_STAGE_CHECK("range sort");
-        g_prof.mark("range_sort", stream);
-    } else {
-        // (its result side is kept: one pass of the general form ends on the b side, the single-launch form of small inputs on the a side)
-        first_side = lg::launch_radix_sort_pairs(geom.key_a, geom.key_b, geom.id_a, geom.id_b, (size_t)P, 8, geom.scratch, stream, 8, nullptr,
-                                                 lg::SORT_MAX_RADIX_BITS, true);
-        LG_STAGE_CHECK("range sort, first pass");
-        ids_sorted = nullptr;
-    }
-
-    // 2. the one host wait (R3/cr/rasterizer_impl.cu:292), for a copy that was queued before the sort: the instance totals for tile
-    //    heights 4 / 8 / 16 / 32 -> tile height, R; then the instance offsets in range order for that height.  The device is still
-    //    sorting while the host decides and queues what follows (the packed gradient lines are zeroed by the preprocess itself, so
-    //    there is no fill to queue behind the copy any more, and no guess of the tile height).
-    int TH;
-    size_t R;
-    uint32_t* status_dev = geom.totals + LG_TOTALS_STATUS_WORD;
-    if (!enqueue_only) {
-        uint32_t totals_h[LG_TOTALS_READ_WORDS];                           // the slots of 64-bit instance totals the preprocess filled
-        LG_HIP((hipError_t)lg::api_read_words_end(LG_TOTALS_READ_WORDS, totals_h));
-        if (!buckets) {   // the rest of the range sort: bits [8, bits of (kmax - kmin + 1)) in passes of at most 9 bits; at least one pass, for the tail
-            uint32_t kinv = 0u, kmax = 0u;
-            for (int slot = 0; slot < LG_INST_SLOTS; slot++) {
-                kinv = std::max(kinv, totals_h[LG_TOTALS_KEYSPAN_WORD + 2 * slot]); kmax = std::max(kmax, totals_h[LG_TOTALS_KEYSPAN_WORD + 2 * slot + 1]);
-            }
-            lg::KeyBias kb;
-            kb.kmin = (~kinv) & ~255u;                                      // a multiple of 256: (key - kmin) & 255 == key & 255
-            if (kmax < kb.kmin) { kb.kmin = 0u; kmax = 0u; }               // no visible Gaussian: every key is the culled one
-            kb.cull = ((kmax - kb.kmin) | 255u) + 1u;                       // above every valid key - kmin in the bits the later passes sort on
-            const uint32_t top = kb.cull;
-            int bits = 32 - __builtin_clz(top | 1u);
-            if (bits < 9) bits = 9;
-            static const int env_full = [] { const char* e = getenv("LIDARGS_RANGE_SORT_FULL"); return e ? atoi(e) : 0; }();   // 1: always 31 bits (A/B)
-            if (env_full) { bits = 32; kb.kmin = 0u; kb.cull = 0xFFFFFFFFu; }
-            uint32_t* const k_in = first_side ? geom.key_b : geom.key_a; uint32_t* const k_out = first_side ? geom.key_a : geom.key_b;
-            uint32_t* const v_in = first_side ? geom.id_b : geom.id_a; uint32_t* const v_out = first_side ? geom.id_a : geom.id_b;
-            const int side = lg::launch_radix_sort_pairs(k_in, k_out, v_in, v_out, (size_t)P, bits, geom.scratch, stream,
-                                                         bits > 26 ? 8 : 9, nullptr, lg::SORT_MAX_RADIX_BITS, false, span_tail, 8, &kb);
-            ids_sorted = side ? v_out : v_in;
-            LG_STAGE_CHECK("range sort");
-            g_prof.mark("range_sort", stream);
-        }
-        unsigned long long inst[4] = {0, 0, 0, 0};
-        for (int slot = 0; slot < LG_INST_SLOTS; slot++) {
-            unsigned long long v[4];
-            memcpy(v, totals_h + LG_TOTALS_SLOT_WORD + 8 * slot, sizeof v);
-            inst[0] += v[0]; inst[1] += v[1]; inst[2] += v[2]; inst[3] += v[3];
-        }
-        const unsigned long long inst4[4] = {inst[0], inst[1], inst[2], inst[3]};
-        TH = choose_tile_rows(inst4, height);                              // 4, 8, 16 or 32
-        const unsigned long long R64 = TH == 4 ? inst[0] : (TH == 8 ? inst[1] : (TH == 16 ? inst[2] : inst[3]));
-        if (R64 > (unsigned long long)std::numeric_limits<int>::max() - 4ull) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward: instance count overflows int%s");
-        R = (size_t)R64;
-        lg::launch_instance_offsets(geom.span_sorted, pp.compact != 0, TH, geom.block_off, geom.totals, (size_t)P, stream, false);   // (the host has R from the preprocess's totals; the emit adds the block sums up itself)
-        LG_STAGE_CHECK("instance scan");
-    } else {
-        TH = fixed_tile_rows;
-        // the capacity, rounded up to the multiple of 4 `num_rendered` can carry, stands in for the count everywhere on the host: the
-        // emit's cap, k_finish_totals' cap, the tile sort, the tile ranges and the buffer carving all see this ONE number (round 2
-        // sorted and ranged only the unrounded capacity: need in (capacity, rounded] dropped instances with no overflow flag)
-        R = ((size_t)instance_capacity + 3) & ~(size_t)3;
-        lg::launch_instance_offsets(geom.span_sorted, pp.compact != 0, TH, geom.block_off, geom.totals, (size_t)P, stream);
-        LG_STAGE_CHECK("instance scan");
-        lg::launch_finish_totals(geom.totals, reinterpret_cast<const unsigned long long*>(geom.totals + LG_TOTALS_SLOT_WORD),
-                                 (uint32_t)R, status_dev, stream);
-        if (status_host) LG_HIP(hipMemcpyAsync(status_host, status_dev, LG_STATUS_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    }
-    lg::TileGrid grid = lg::make_grid(width, height, TH);
-    if (col_lo >= 0) { grid.x_lo = pp.tile_x_lo; grid.x_n = pp.tile_x_hi - pp.tile_x_lo; }   // the blends cover the wedge's own tile columns only
-    const uint32_t* R_dev = enqueue_only ? status_dev + 1 : nullptr;       // instances binned = min(needed, capacity), on the device
-    g_prof.mark("scan+readback", stream);
-
-    // everything a later call on these buffers derives (plan, carving, flag stride) comes from the returned int alone
-    const int rendered = encode_rendered(R, TH);
-    const size_t Rp = rendered_capacity(rendered);
-    const size_t patches = (size_t)grid.num_tiles() * grid.waves_per_tile;
-    const lg::SegPlan plan = plan_segments(Rp, grid.waves_per_tile, 0, (size_t)grid.window_patches());
-    const int S = lg::choose_segments(Rp, plan.max_segments);
-    char* bin_p = binning_alloc(binning_user, lg::bin_carve(nullptr, Rp, patches, grid.waves_per_tile, S, nullptr));
-    if (!bin_p) return fail(LIDARGS_ERR_ALLOC, "binning allocator returned NULL%s");
-    lg::BinView bin; lg::bin_carve(bin_p, Rp, patches, grid.waves_per_tile, S, &bin);
-
-    // 3. emit instances in range order, bin them by tile (stable); 16-bit tile keys whenever the tile ids fit (LIDARGS_TILE_KEY32=1: A/B)
-    static const bool key32 = [] { const char* e = getenv("LIDARGS_TILE_KEY32"); return e && atoi(e) != 0; }();
-    const bool key16 = grid.num_tiles() <= 65536 && !key32;
-    const uint32_t* point_list = bin.val_a;
-    if (R) {
-        // the sorted lists are wanted on the a side (the backward finds them there whatever the pass count was): a sort that will end on
-        // the other side -- an odd number of passes: images of at most 256 list tiles -- gets its input there, instead of two copies behind it
-        const int bits = ceil_log2((uint32_t)grid.num_tiles());
-        const bool flip = lg::radix_sort_result_side(R, bits) != 0;
-        uint32_t* const k_in = flip ? bin.tile_b : bin.tile_a; uint32_t* const k_out = flip ? bin.tile_a : bin.tile_b;
-        uint32_t* const v_in = flip ? bin.val_b : bin.val_a; uint32_t* const v_out = flip ? bin.val_a : bin.val_b;
-        lg::launch_emit_instances(ids_sorted, geom.block_off, geom.span_sorted, pp.compact != 0, (size_t)P, grid,
-                                  k_in, v_in, stream, enqueue_only ? (uint32_t)Rp : 0xFFFFFFFFu, key16, img.ranges, !enqueue_only);
-        LG_STAGE_CHECK("emit");
-        g_prof.mark("emit", stream);
-        const int side = key16 ? lg::launch_radix_sort_pairs16(reinterpret_cast<uint16_t*>(k_in), reinterpret_cast<uint16_t*>(k_out), v_in, v_out, R,
-                                                               bits, bin.scratch, stream, R_dev)
-                               : lg::launch_radix_sort_pairs(k_in, k_out, v_in, v_out, R, bits, bin.scratch, stream, 0, R_dev);
-        const int bside = side ^ (flip ? 1 : 0);                       // 1: the result is NOT on the a side after all (never, by radix_sort_result_side)
-        if (bside) {   // keep the backward's view independent of the pass count: result always in (tile_a, val_a)
-            LG_HIP(hipMemcpyAsync(bin.tile_a, bin.tile_b, R * (key16 ? sizeof(uint16_t) : sizeof(uint32_t)), hipMemcpyDeviceToDevice, stream));
-            LG_HIP(hipMemcpyAsync(bin.val_a, bin.val_b, R * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
-        }
-        LG_STAGE_CHECK("tile bin");
-        g_prof.mark("tile_bin", stream);
-    }
-    lg::launch_tile_ranges(bin.tile_a, R, img.ranges, grid.num_tiles(), stream, R_dev, key16, bin.work, LG_WORK_REGIONS * LG_WORK_CNT_STRIDE, R != 0);
-    LG_STAGE_CHECK("tile ranges");
-    g_prof.mark("ranges", stream);
+    const lg::BinSpec spec = {is_shell ? lg::FRAME_SHELL : lg::FRAME_GAUSS, fixed_tile_rows, instance_capacity, status_host, "forward"};
+    lg::BinnedFrame bf;
+    const int rendered = lg::bin_frame(spec, geom, img.ranges, (size_t)P, width, height, col_lo, col_hi, pp.compact != 0, binning_alloc, binning_user,
+                                       debug, stream, &bf);
+    if (rendered < 0) return rendered;
+    const lg::FrameLayout& L = bf.L;
+    const lg::BinView& bin = bf.bin;
+    const size_t R = bf.R;
 
     lg::RenderFwdArgs ra;
     ra.fill.cnt = nullptr;
-    ra.grid = grid; ra.ranges = img.ranges; ra.point_list = point_list; ra.rec = geom.rec; ra.rowspan = geom.rowspan;
+    ra.grid = L.grid; ra.ranges = img.ranges; ra.point_list = bin.val_a; ra.rec = geom.rec; ra.rowspan = geom.rowspan;
     ra.coltab = img.coltab; ra.rowtab = img.rowtab; ra.bg = background; ra.T_in = T_in;
     ra.final_T = img.final_T; ra.T_pass = T_out;
     ra.out_color = out_color; ra.out_depth = out_depth; ra.out_occ = out_occ;
-    ra.seg = bin.seg; ra.S = S; ra.seg_len = plan.seg_len;
-    ra.run_pass1 = (S > 1 || transmittance_pass || is_shell) ? 1 : 0;   // (a shell's backward always reads the flags)
-    ra.flags = ra.run_pass1 ? bin.flags : nullptr; ra.R = Rp;
+    ra.seg = bin.seg; ra.S = L.S; ra.seg_len = L.plan.seg_len;
+    ra.run_pass1 = (L.S > 1 || transmittance_pass || is_shell) ? 1 : 0;   // (a shell's backward always reads the flags)
+    ra.flags = ra.run_pass1 ? bin.flags : nullptr; ra.R = L.Rp;
     ra.touched = geom.touched;                                         // marked wherever a contribution flag is set (cleared by the preprocess)
     ra.transmittance_only = transmittance_pass;
-    ra.seg_lo = 0; ra.seg_hi = S; ra.front = 0; ra.alive = nullptr;
+    ra.seg_lo = 0; ra.seg_hi = L.S; ra.front = 0; ra.alive = nullptr;
     int head = 0;                                                      // segments at the head of every list that round 1 walked completely
-    const bool fused = plan.fused && !is_shell;                        // the plain frame (a range shell's two phases keep the launches)
     // no flags (a one-segment plan: LIDARGS_MAX_SEGMENTS=1): pass 2 and the backward walk every listed entry, so every Gaussian may be added to
-    if (!fused && !ra.run_pass1 && R) lg::launch_touch_all(geom.touched, radii, (size_t)P, stream);
-    if (fused) {
+    if (!L.fused && !ra.run_pass1 && R) lg::launch_touch_all(geom.touched, radii, (size_t)P, stream);
+    if (L.fused) {
         ra.flags = bin.flags; ra.alive = bin.alive;
         lg::launch_render_fused(ra, stream);
         LG_STAGE_CHECK("render fused");
-        g_prof.mark("render_fused", stream);
+        lg::prof_mark("render_fused", stream);
     } else {
     if (ra.run_pass1) {
-        run_pass1_rounds(ra, plan, bin.alive, stream, transmittance_pass ? nullptr : &head);
+        run_pass1_rounds(ra, L.plan, bin.alive, stream, transmittance_pass ? nullptr : &head);
         LG_STAGE_CHECK("render pass 1");
-        g_prof.mark("render_pass1", stream);
+        lg::prof_mark("render_pass1", stream);
     }
-    ra.seg_lo = head; ra.seg_hi = S;
+    ra.seg_lo = head; ra.seg_hi = L.S;
     if (!transmittance_pass) {
         lg::launch_render_pass2(ra, stream);
         LG_STAGE_CHECK("render pass 2");
-        g_prof.mark("render_pass2", stream);
+        lg::prof_mark("render_pass2", stream);
     }
-    // not in a range shell's phases: their backward (lidargs_backward_shell) keeps the slot grid
-    if (!is_shell && backward_list(S, patches, false)) ra.fill = lg::work_list(bin);
+    if (L.work_list) ra.fill = lg::work_list(bin);
     lg::launch_render_combine(ra, stream);
     LG_STAGE_CHECK("render combine");
-    g_prof.mark("render_combine", stream);
+    lg::prof_mark("render_combine", stream);
     }
 
-    g_counters[0] = P; g_counters[2] = (long long)R; g_counters[4] = TH; g_counters[5] = grid.num_tiles(); g_counters[7] = S;
-    if (g_counters_on) {   // the selection a backward on these buffers will make (backward_impl builds the same view): counted now, while the buffers are certainly alive
-        lg::RenderBwdArgs v = lg::RenderBwdArgs();
-        v.walk.cnt = nullptr; v.grid = grid; v.ranges = img.ranges; v.seg = bin.seg; v.S = S; v.seg_len = plan.seg_len; v.R = Rp;
-        v.alive = (fused || pass1_gated(plan, S)) ? bin.alive : nullptr;
-        v.flags = (fused || S > 1 || is_shell) ? bin.flags : nullptr;
-        queue_counters(geom.totals, ra.flags, R, Rp, grid.waves_per_tile, geom.touched, (size_t)P, (R != 0 && !transmittance_pass) ? &v : nullptr, stream);
-    } else queue_counters(nullptr, ra.flags, 0, 0, 0, nullptr, 0, nullptr, stream);
+    // the selection a backward on these buffers will make (backward_impl builds the same view): counted now, while the buffers are certainly alive
+    lg::RenderBwdArgs v = lg::RenderBwdArgs();
+    v.walk.cnt = nullptr; v.grid = L.grid; v.ranges = img.ranges; v.seg = bin.seg; v.S = L.S; v.seg_len = L.plan.seg_len; v.R = L.Rp;
+    v.alive = L.gated ? bin.alive : nullptr;
+    v.flags = L.flags ? bin.flags : nullptr;
+    lg::note_forward((size_t)P, R, L, geom.totals, ra.flags, geom.touched, (R != 0 && !transmittance_pass) ? &v : nullptr, stream);
     return rendered;
 }
 
@@ -638,20 +633,13 @@ int backward_impl(int P, int R, const float* background, int width, int height, 
         !dL_dopacity || !dL_dcolor || !dL_dmean3D || !dL_dscale || !dL_drot || (cov3D_precomp && !dL_dcov3D))
         return fail(LIDARGS_ERR_INVALID_ARGUMENT, "backward: NULL required pointer%s");
 
-    lg::GeomView geom; lg::geom_carve(geom_buffer, (size_t)P, &geom);
-    const int TH = rendered_tile_rows(R);                              // the forward's num_rendered carries its tile height
-    const size_t Rp = rendered_capacity(R);
-    lg::TileGrid grid = lg::make_grid(width, height, TH);
-    if (col_lo >= 0) {                                                 // a column wedge's buffers: only its own patches were rendered
-        if (col_lo % LG_TILE_W || col_hi <= col_lo || col_hi > width) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "backward: bad column wedge%s");
-        grid.x_lo = col_lo / LG_TILE_W; grid.x_n = (col_hi + LG_TILE_W - 1) / LG_TILE_W - grid.x_lo;
-    }
-    const size_t patches = (size_t)grid.num_tiles() * grid.waves_per_tile;
-    const lg::SegPlan plan = plan_segments(Rp, grid.waves_per_tile, 0, (size_t)grid.window_patches());
-    const int S = lg::choose_segments(Rp, plan.max_segments);
-    lg::BinView bin; lg::bin_carve(binning_buffer, Rp, patches, grid.waves_per_tile, S, &bin);
+    lg::GeomView geom; lg::geom_carve(geom_buffer, (size_t)P, lg::GAUSS_BUFFERS, &geom);
+    // a column wedge's buffers: only its own patches were rendered
+    if (col_lo >= 0 && (col_lo % LG_TILE_W || col_hi <= col_lo || col_hi > width)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "backward: bad column wedge%s");
+    const lg::FrameLayout L = lg::frame_layout(R, width, height, col_lo, col_hi, shell_mode ? lg::FRAME_SHELL : lg::FRAME_GAUSS);   // (from the forward's num_rendered)
+    lg::BinView bin; L.bin_carve(binning_buffer, &bin);
     lg::ImgView img; lg::img_carve(image_buffer, width, height, lg::make_grid(width, height, 4).num_tiles(), &img);
-    g_prof.begin(stream, 1);
+    lg::prof_begin(stream, 1);
 
     // Only the Gaussians the forward marked as touched are ever added to, and every backward on these buffers (the first, or a later one
     // under retain_graph) starts by clearing exactly their packed lines, listing them, and zeroing the caller's gradient rows.
@@ -659,22 +647,21 @@ int backward_impl(int P, int R, const float* background, int width, int height, 
     zr.add(dL_dmean2D, 4); zr.add(dL_dconic, 4); zr.add(dL_dopacity, 1); zr.add(dL_dcolor, 2); zr.add(dL_ddepths, 1); zr.add(dL_dmean3D, 3);
     zr.add(dL_dsphere_means3D, 3); zr.add(dL_dbasis_u1, 3); zr.add(dL_dbasis_u2, 3); zr.add(dL_dcov3D, 6); zr.add(dL_dscale, 3); zr.add(dL_drot, 4);
     lg::launch_zero_touched(geom.touched, reinterpret_cast<float4*>(geom.gacc), 4, (size_t)P, geom.tlist, geom.tcount, zr, stream);
-    g_prof.mark("bwd_zero", stream);
+    lg::prof_mark("bwd_zero", stream);
 
     lg::RenderBwdArgs rb;
     rb.walk.cnt = nullptr;
-    rb.grid = grid; rb.ranges = img.ranges; rb.point_list = bin.val_a; rb.rec = geom.rec; rb.rowspan = geom.rowspan;
+    rb.grid = L.grid; rb.ranges = img.ranges; rb.point_list = bin.val_a; rb.rec = geom.rec; rb.rowspan = geom.rowspan;
     rb.coltab = img.coltab; rb.rowtab = img.rowtab; rb.bg = background; rb.final_T = img.final_T;
-    rb.seg = bin.seg; rb.S = S; rb.seg_len = plan.seg_len;
-    const bool fused = plan.fused && !shell_mode;                      // as the forward decided (forward_impl): flags and limits always exist
-    rb.alive = (fused || pass1_gated(plan, S)) ? bin.alive : nullptr;
-    rb.flags = (fused || S > 1 || shell_mode) ? bin.flags : nullptr; rb.R = Rp;
+    rb.seg = bin.seg; rb.S = L.S; rb.seg_len = L.plan.seg_len;
+    rb.alive = L.gated ? bin.alive : nullptr;
+    rb.flags = L.flags ? bin.flags : nullptr; rb.R = L.Rp;
     rb.T_final_global = T_final_global; rb.behind = behind;
     rb.dL_dpix = dL_dpix; rb.dL_ddepth = dL_dout_depth; rb.dL_docc = dL_dout_occ; rb.gacc = geom.gacc;
-    if (!shell_mode && backward_list(S, patches, fused)) rb.walk = lg::work_list(bin);          // as forward_impl decided
+    if (L.work_list) rb.walk = lg::work_list(bin);
     lg::launch_render_backward(rb, stream);
     LG_STAGE_CHECK("render backward");
-    g_prof.mark("render_bwd", stream);
+    lg::prof_mark("render_bwd", stream);
 
     lg::GaussBwdArgs gb;
     gb.P = P; gb.scale_modifier = scale_modifier;
@@ -687,7 +674,7 @@ int backward_impl(int P, int R, const float* background, int width, int height, 
     gb.dL_drot = dL_drot;
     lg::launch_gaussian_backward(gb, stream);
     LG_STAGE_CHECK("gaussian backward");
-    g_prof.mark("gaussian_bwd", stream);
+    lg::prof_mark("gaussian_bwd", stream);
     return 0;
 }
 
@@ -759,7 +746,7 @@ int lidargs_visible_filter(lidargs_alloc_fn geometry_alloc, void* geometry_user,
     if (!means3D || !viewmatrix || !beam_inclinations || !radii)   // radii_xy: optional
         return fail(LIDARGS_ERR_INVALID_ARGUMENT, "visible_filter: NULL required pointer%s");
     if (!cov3D_precomp && (!scales || !rotations)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "visible_filter: need scales+rotations or cov3D_precomp%s");
-    const lg::TileGrid grid = lg::make_grid(width, height, tile_rows());
+    const lg::TileGrid grid = lg::make_grid(width, height, lg::tile_rows());
     lg::PreprocessParams pp;
     pp.P = P; pp.W = width; pp.H = height; pp.TH = grid.TH; pp.tiles_x = grid.tiles_x; pp.tiles_y = grid.tiles_y;
     pp.scale_modifier = scale_modifier;
@@ -930,31 +917,26 @@ int lidargs_render_shell(int P, int R, const float* background, int width, int h
                          float* out_occ, float* T_out, float* T_end_out, int debug, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     if (P <= 0 || R < 0 || !geom_buffer || !binning_buffer || !image_buffer) return fail(LIDARGS_ERR_STATE, "render_shell: missing forward buffers%s");
-    lg::GeomView geom; lg::geom_carve(geom_buffer, (size_t)P, &geom);
-    const int TH = rendered_tile_rows(R);
-    const size_t Rp = rendered_capacity(R);
-    const lg::TileGrid grid = lg::make_grid(width, height, TH);
-    const size_t patches = (size_t)grid.num_tiles() * grid.waves_per_tile;
-    const lg::SegPlan plan = plan_segments(Rp, grid.waves_per_tile, 0, (size_t)grid.window_patches());
-    const int S = lg::choose_segments(Rp, plan.max_segments);
-    lg::BinView bin; lg::bin_carve(binning_buffer, Rp, patches, grid.waves_per_tile, S, &bin);
+    lg::GeomView geom; lg::geom_carve(geom_buffer, (size_t)P, lg::GAUSS_BUFFERS, &geom);
+    const lg::FrameLayout L = lg::frame_layout(R, width, height, -1, -1, lg::FRAME_SHELL);
+    lg::BinView bin; L.bin_carve(binning_buffer, &bin);
     lg::ImgView img; lg::img_carve(image_buffer, width, height, lg::make_grid(width, height, 4).num_tiles(), &img);
     lg::RenderFwdArgs ra;
     ra.fill.cnt = nullptr;                       // a shell's backward keeps the slot grid
-    ra.grid = grid; ra.ranges = img.ranges; ra.point_list = bin.val_a; ra.rec = geom.rec; ra.rowspan = geom.rowspan;
+    ra.grid = L.grid; ra.ranges = img.ranges; ra.point_list = bin.val_a; ra.rec = geom.rec; ra.rowspan = geom.rowspan;
     ra.coltab = img.coltab; ra.rowtab = img.rowtab; ra.bg = background; ra.T_in = T_in;
     ra.final_T = img.final_T; ra.T_pass = T_out;
     ra.out_color = out_color; ra.out_depth = out_depth; ra.out_occ = out_occ;
-    ra.seg = bin.seg; ra.S = S; ra.seg_len = plan.seg_len;
-    ra.seg_lo = 0; ra.seg_hi = S; ra.front = 0;
-    ra.alive = pass1_gated(plan, S) ? bin.alive : nullptr;        // written, like the flags, by the shell's phase 1
-    ra.flags = bin.flags; ra.R = Rp;             // written by the shell's phase 1 (lidargs_forward_shell)
+    ra.seg = bin.seg; ra.S = L.S; ra.seg_len = L.plan.seg_len;
+    ra.seg_lo = 0; ra.seg_hi = L.S; ra.front = 0;
+    ra.alive = L.gated ? bin.alive : nullptr;    // written, like the flags, by the shell's phase 1
+    ra.flags = bin.flags; ra.R = L.Rp;           // written by the shell's phase 1 (lidargs_forward_shell)
     ra.touched = geom.touched;                   // (a repeated T-only pass sets the same marks again)
     ra.run_pass1 = transmittance_pass ? 1 : 0;   // phase 2 reuses the Tpass planes the shell's phase 1 left behind
     ra.transmittance_only = transmittance_pass;
     ra.T_end_out = transmittance_pass ? nullptr : T_end_out;          // the combine writes it beside final_T
     if (!transmittance_pass && (!out_color || !out_depth || !out_occ)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "render_shell: NULL output%s");
-    if (ra.run_pass1) run_pass1_rounds(ra, plan, bin.alive, stream);
+    if (ra.run_pass1) run_pass1_rounds(ra, L.plan, bin.alive, stream);
     if (!transmittance_pass) lg::launch_render_pass2(ra, stream);
     lg::launch_render_combine(ra, stream);
     LG_STAGE_CHECK("render shell");

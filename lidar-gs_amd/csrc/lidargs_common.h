@@ -118,7 +118,7 @@ __device__ __forceinline__ uint2 span_unpack(uint32_t w) {            // -> (xsp
 #define LG_TOTALS_DIAG_WORD LG_TOTALS_READ_WORDS
 #define LG_TOTALS_WORDS (LG_TOTALS_DIAG_WORD + 4 * LG_INST_SLOTS)
 struct GeomView {
-    float4* rec;
+    float4* rec;                        // [4P] (surfel variant: [5P])
     uint32_t* rowspan;
     uint4* spans;                       // (rowspan, xspan, instances at 4-row tiles, reference tiles_touched)
     uint2* span_sorted;                 // (xspan, rowspan) of the i-th Gaussian in range order
@@ -126,7 +126,7 @@ struct GeomView {
     uint32_t* id_a; uint32_t* id_b;     // Gaussian ids ping/pong (id_sorted ends in id_a)
     uint32_t* block_off;                // [scan_blocks(P)] exclusive instance offset of each block of SCAN_BLOCK range-consecutive Gaussians
     uint32_t* totals;                   // [0]=#instances of the scan, [8..] instance-total slots
-    float* gacc;                        // [16P] packed per-Gaussian gradient accumulators (backward)
+    float* gacc;                        // [16P] (surfel variant: [32P]) packed per-Gaussian gradient accumulators (backward)
     uint8_t* touched;                   // [P] 1 = some pixel's walk took the Gaussian (the forward's contribution flags, a superset of what the
                                         //     backward blends): only these have a gradient, and only their gacc lines are ever zeroed, added to or read
     uint8_t* tlist; uint16_t* tcount;   // the backward's lists of them: per region of LG_REGION consecutive Gaussians, the touched ones' offsets
@@ -135,10 +135,16 @@ struct GeomView {
     size_t scratch_words;
 };
 
-inline size_t geom_carve(char* base, size_t P, GeomView* v) {
+// What the two rasterizers' buffers differ in: float4s of splat record and floats of gradient line per Gaussian, 64-float planes per
+// (patch, segment) slot of the forward blend, and whether the backward's work list is carved
+struct BufferWidths { int rec_f4, gacc_floats, seg_planes; bool work_list; };
+constexpr BufferWidths GAUSS_BUFFERS = {4, 16, LG_SEG_PLANES, true};
+constexpr BufferWidths SURFEL_BUFFERS = {5, 32, 16, false};     // (16: surfel.hip SF_SEG_PLANES, checked there)
+
+inline size_t geom_carve(char* base, size_t P, const BufferWidths& w, GeomView* v) {
     Carver c(base);
     GeomView g;
-    g.rec = c.take<float4>(4 * P);
+    g.rec = c.take<float4>((size_t)w.rec_f4 * P);
     g.rowspan = c.take<uint32_t>(P);
     g.spans = c.take<uint4>(P);
     g.span_sorted = c.take<uint2>(P);
@@ -146,7 +152,7 @@ inline size_t geom_carve(char* base, size_t P, GeomView* v) {
     g.id_a = c.take<uint32_t>(P); g.id_b = c.take<uint32_t>(P);
     g.block_off = c.take<uint32_t>(scan_blocks(P) + 64);
     g.totals = c.take<uint32_t>(LG_TOTALS_WORDS);
-    g.gacc = c.take<float>(16 * P);
+    g.gacc = c.take<float>((size_t)w.gacc_floats * P);
     g.touched = c.take<uint8_t>(P + 64);
     g.tlist = c.take<uint8_t>(P + LG_REGION); g.tcount = c.take<uint16_t>(P / LG_REGION + 64);
     g.scratch_words = sort_scratch_words(P, SORT_MAX_RADIX_BITS) + scan_scratch_words(P);
@@ -160,10 +166,10 @@ struct BinView {
     uint32_t* val_a; uint32_t* val_b;
     uint32_t* scratch;
     size_t scratch_words;
-    float* seg;                          // [patches][S][LG_SEG_PLANES][64]
+    float* seg;                          // [patches][S][seg_planes][64]
     uint8_t* flags;                      // [waves_per_tile][R]: pass 1 saw >= 1 pixel of the patch take this entry
     uint8_t* alive;                      // [patches]: number of list segments pass 1 walked (255 = all)
-    uint32_t* work;                      // the backward's work list (see WorkList): counters, then items [LG_WORK_REGIONS][cap]
+    uint32_t* work;                      // the backward's work list (see WorkList): counters, then items [LG_WORK_REGIONS][cap]; NULL if not carved
     uint32_t work_cap;                   // items per region
 };
 
@@ -216,7 +222,7 @@ inline int choose_segments(size_t R, int max_segments) {
     return max_segments < 1 ? 1 : max_segments;
 }
 
-inline size_t bin_carve(char* base, size_t R, size_t patches, int waves_per_tile, int S, BinView* v) {
+inline size_t bin_carve(char* base, size_t R, size_t patches, int waves_per_tile, int S, const BufferWidths& w, BinView* v) {
     Carver c(base);
     BinView b;
     size_t n = R ? R : 1;
@@ -224,11 +230,11 @@ inline size_t bin_carve(char* base, size_t R, size_t patches, int waves_per_tile
     b.val_a = c.take<uint32_t>(n); b.val_b = c.take<uint32_t>(n);
     b.scratch_words = sort_scratch_words(n);
     b.scratch = c.take<uint32_t>(b.scratch_words);
-    b.seg = c.take<float>(patches * (size_t)S * LG_SEG_PLANES * 64);
+    b.seg = c.take<float>(patches * (size_t)S * w.seg_planes * 64);
     b.flags = c.take<uint8_t>((size_t)waves_per_tile * n + 64);
     b.alive = c.take<uint8_t>(patches + 64);
-    b.work_cap = work_cap(patches, S);
-    b.work = c.take<uint32_t>(work_words(patches, S));
+    b.work_cap = w.work_list ? work_cap(patches, S) : 0;
+    b.work = w.work_list ? c.take<uint32_t>(work_words(patches, S)) : nullptr;
     if (v) *v = b;
     return (size_t)(c.p - base) + 128;
 }
@@ -315,27 +321,42 @@ void lane_stats_read(unsigned long long* out, int reset);              // render
 // helpers exported by api.hip for the other entry-point files
 int api_fail(int code, const char* msg);
 int api_check_launch(hipStream_t s, int debug, const char* what);
-int api_tile_rows();
-bool api_prune_footprints();
-int api_ceil_log2(uint32_t n);
-int api_range_sort_bits();
-struct SegPlan { int seg_len, max_segments, n_rounds, rounds[8]; int head; int fused; };   // api.hip plan_segments (head: walk round 1
-                                                                                          // completely; fused: one workgroup per patch does it all)
-SegPlan api_plan_segments(size_t R, int waves_per_tile, int surfel);
 // Device -> host read of `n` (<= 1024) words with `zero_bytes` at `zero` cleared BEHIND the copy on the same stream: the host waits
 // for the copy only.  Returns a hipError_t.
 int api_read_words_zero_behind(const uint32_t* dev, int n, uint32_t* out, void* zero, size_t zero_bytes, hipStream_t s);
-int api_read_words_begin(const uint32_t* dev, int n, hipStream_t s);    // the same read in two halves: queue the copy ...
-int api_read_words_end(int n, uint32_t* out);                           // ... and, with more work queued behind it, wait for it
-// num_rendered = instance capacity (multiple of 4) | tile-height code: all a later call on the forward's buffers needs (api.hip)
+int tile_rows();                 // list-tile height of the callers that do not choose one per frame
+bool prune_footprints();
 // per-stage HIP-event timing (lidargs_profile_*): kind 0 = forward-like call, 1 = backward
-void api_prof_begin(hipStream_t s, int kind);
-void api_prof_mark(const char* name, hipStream_t s);
-void api_note_forward(long long P, long long R, int TH, int tiles, int S, const void* spans, const uint8_t* flags, size_t flags_stride,
-                      int flags_planes, const uint8_t* touched, hipStream_t s);   // host-side counters; with lidargs_counters_enable(1) also queues the counting launches
-int api_encode_rendered(size_t R, int TH);
-size_t api_rendered_capacity(int num_rendered);
-int api_rendered_tile_rows(int num_rendered);
+void prof_begin(hipStream_t s, int kind);
+void prof_mark(const char* name, hipStream_t s);
+
+struct SegPlan { int seg_len, max_segments, n_rounds, rounds[8]; int head; int fused; };   // api.hip plan_segments (head: walk round 1
+                                                                                          // completely; fused: one workgroup per patch does it all)
+// Everything a call on a forward's buffers derives from its `num_rendered` (instance capacity | tile-height code), the image size, the
+// column wedge and the variant: the forward, its backward and a shell's phase 2 all take it from here (api.hip frame_layout).
+enum FrameVariant { FRAME_GAUSS, FRAME_SHELL, FRAME_SURFEL };   // a plain or column-wedge 3-D frame, a range shell's, a surfel frame
+struct FrameLayout {
+    int TH; size_t Rp;              // list-tile height, instance capacity of the binning buffer
+    TileGrid grid;                  // (with the wedge's tile columns)
+    size_t patches; SegPlan plan; int S;
+    bool fused;                     // the forward blend is the one launch of k_render_fused
+    bool gated, flags, work_list;   // a walk behind pass 1 sees its alive[] limits / its contribution flags / the backward's work list
+    BufferWidths buf;
+    size_t bin_carve(char* base, BinView* v) const { return lg::bin_carve(base, Rp, patches, grid.waves_per_tile, S, buf, v); }
+};
+FrameLayout frame_layout(int num_rendered, int W, int H, int col_lo, int col_hi, FrameVariant variant);   // col_lo < 0: no wedge
+
+// The binning of both forwards (api.hip bin_frame): from the copy of the preprocess' totals to the tile ranges.  What they differ in:
+struct BinSpec {
+    FrameVariant variant;     // FRAME_SURFEL: LIDARGS_TILE_KEY32 and LIDARGS_RANGE_SORT_FULL do not apply
+    int tile_rows;            // 0: chosen per frame (choose_tile_rows); else fixed (the surfel preprocess sums its instances in word 0 of each slot)
+    long long capacity;       // > 0: enqueue-only (3-D): no host read, the binning buffer holds this many instances
+    unsigned* status_host;    // enqueue-only: where the stream copies the status words, or NULL
+    const char* what;         // error-message prefix
+};
+struct BinnedFrame { FrameLayout L; BinView bin; size_t R; };   // R: instances sorted (enqueue-only: the capacity); lists in (tile_a, val_a)
+int bin_frame(const BinSpec& spec, const GeomView& geom, uint2* ranges, size_t P, int W, int H, int col_lo, int col_hi, bool compact,
+              char* (*binning_alloc)(void*, size_t), void* binning_user, int debug, hipStream_t s, BinnedFrame* out);   // -> num_rendered or an error
 // First launch of a backward (preprocess.hip k_zero_touched): clears the packed gradient line (`line_f4` float4: 4 = 64 bytes, the 3-D
 // variant; 8 = 128 bytes, the surfel variant) of every Gaussian the forward marked as touched -- nobody reads or adds to the others' --,
 // lists the touched Gaussians per region (tlist / tcount of the geometry view) and zeroes every row of the caller's gradient arrays.
@@ -534,6 +555,10 @@ struct RenderBwdArgs {
 };
 void launch_render_backward(const RenderBwdArgs& a, hipStream_t s);
 void launch_count_backward_entries(const RenderBwdArgs& a, unsigned long long* out, hipStream_t s);   // diagnostics: adds the list entries k_render_backward gathers to *out
+// diagnostics of a forward (lidargs_last_counters): host-side counters; with lidargs_counters_enable(1) also queues the counting launches.
+// view: the selection a backward on these buffers will make, or NULL
+void note_forward(size_t P, size_t R, const FrameLayout& L, const uint32_t* totals, const uint8_t* flags, const uint8_t* touched,
+                  const RenderBwdArgs* view, hipStream_t s);
 
 struct GaussBwdArgs {
     int P; float scale_modifier; const float* view;   // device pointer

@@ -6,43 +6,7 @@
 
 namespace lg {
 
-struct SfGeomView {
-    float4* rec;            // [5P]
-    uint32_t* rowspan; uint4* spans; uint2* span_sorted;
-    uint32_t* key_a; uint32_t* key_b; uint32_t* id_a; uint32_t* id_b;
-    uint32_t* block_off; uint32_t* totals;
-    float* gacc;            // [32P]
-    uint8_t* touched;       // [P] (GeomView::touched of the 3-D variant)
-    uint8_t* tlist; uint16_t* tcount;   // (GeomView::tlist / tcount)
-    uint32_t* scratch;
-};
-static size_t sf_geom_carve(char* base, size_t P, SfGeomView* v) {
-    Carver c(base);
-    SfGeomView g;
-    g.rec = c.take<float4>(5 * P);
-    g.rowspan = c.take<uint32_t>(P); g.spans = c.take<uint4>(P); g.span_sorted = c.take<uint2>(P);
-    g.key_a = c.take<uint32_t>(P); g.key_b = c.take<uint32_t>(P); g.id_a = c.take<uint32_t>(P); g.id_b = c.take<uint32_t>(P);
-    g.block_off = c.take<uint32_t>(scan_blocks(P) + 64); g.totals = c.take<uint32_t>(LG_TOTALS_WORDS);
-    g.gacc = c.take<float>(32 * P);
-    g.touched = c.take<uint8_t>(P + 64);
-    g.tlist = c.take<uint8_t>(P + LG_REGION); g.tcount = c.take<uint16_t>(P / LG_REGION + 64);
-    g.scratch = c.take<uint32_t>(sort_scratch_words(P, SORT_MAX_RADIX_BITS) + scan_scratch_words(P));
-    if (v) *v = g;
-    return (size_t)(c.p - base) + 128;
-}
-struct SfBinView { uint32_t* tile_a; uint32_t* tile_b; uint32_t* val_a; uint32_t* val_b; uint32_t* scratch; float* seg; uint8_t* flags; uint8_t* alive; };
-static size_t sf_bin_carve(char* base, size_t R, size_t patches, int waves_per_tile, int S, SfBinView* v) {
-    Carver c(base);
-    SfBinView b;
-    const size_t n = R ? R : 1;
-    b.tile_a = c.take<uint32_t>(n); b.tile_b = c.take<uint32_t>(n); b.val_a = c.take<uint32_t>(n); b.val_b = c.take<uint32_t>(n);
-    b.scratch = c.take<uint32_t>(sort_scratch_words(n));
-    b.seg = c.take<float>(patches * (size_t)S * SF_SEG_PLANES * 64);
-    b.flags = c.take<uint8_t>((size_t)waves_per_tile * n + 64);
-    b.alive = c.take<uint8_t>(patches + 64);
-    if (v) *v = b;
-    return (size_t)(c.p - base) + 128;
-}
+static_assert(SURFEL_BUFFERS.seg_planes == SF_SEG_PLANES, "lidargs_common.h SURFEL_BUFFERS carves the surfel blend's segment planes");
 struct SfImgView { float* accum; uint32_t* n_contrib; uint2* ranges; float2* coltab; float2* rowtab; };
 static size_t sf_img_carve(char* base, int W, int H, int tiles, SfImgView* v) {
     Carver c(base);
@@ -82,16 +46,16 @@ int lidargs_surfel_forward(lidargs_alloc_fn geometry_alloc, void* geometry_user,
         return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "surfel forward: NULL required pointer");
     if (!geometry_alloc || !binning_alloc || !image_alloc) return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "surfel forward: NULL allocator");
     if (P == 0) return 0;
-    const int TH = lg::api_tile_rows();
+    const int TH = lg::tile_rows();
     const lg::TileGrid grid = lg::make_grid(width, height, TH);
     lg::SfPreArgs pa = lg::SfPreArgs();
-    char* geom_p = geometry_alloc(geometry_user, lg::sf_geom_carve(nullptr, (size_t)P, nullptr));
+    char* geom_p = geometry_alloc(geometry_user, lg::geom_carve(nullptr, (size_t)P, lg::SURFEL_BUFFERS, nullptr));
     char* img_p = image_alloc(image_user, lg::sf_img_carve(nullptr, width, height, grid.num_tiles(), nullptr));
     if (!geom_p || !img_p) return lg::api_fail(LIDARGS_ERR_ALLOC, "surfel forward: allocator returned NULL");
-    lg::SfGeomView geom; lg::sf_geom_carve(geom_p, (size_t)P, &geom);
+    lg::GeomView geom; lg::geom_carve(geom_p, (size_t)P, lg::SURFEL_BUFFERS, &geom);
     lg::SfImgView img; lg::sf_img_carve(img_p, width, height, grid.num_tiles(), &img);
 
-    lg::api_prof_begin(stream, 0);
+    lg::prof_begin(stream, 0);
     lg::ImgView tabs = lg::ImgView(); tabs.coltab = img.coltab; tabs.rowtab = img.rowtab;
     lg::launch_setup_tables(beam_inclinations, width, height, tabs, stream);
     pa.P = P; pa.W = width; pa.H = height; pa.TH = TH; pa.tiles_x = grid.tiles_x;
@@ -104,96 +68,31 @@ int lidargs_surfel_forward(lidargs_alloc_fn geometry_alloc, void* geometry_user,
     pa.diag_slots = reinterpret_cast<unsigned long long*>(geom.totals + LG_TOTALS_DIAG_WORD);
     pa.key_span = geom.totals + LG_TOTALS_KEYSPAN_WORD;
     pa.compact = lg::compact_spans(grid.tiles_x, height) ? 1 : 0;
-    pa.touched = geom.touched; pa.prune = lg::api_prune_footprints() ? 1 : 0;
+    pa.touched = geom.touched; pa.prune = lg::prune_footprints() ? 1 : 0;
     SF_HIP(hipMemsetAsync(geom.totals, 0, LG_TOTALS_WORDS * sizeof(uint32_t), stream));
     lg::launch_sf_preprocess(pa, false, stream);
     SF_CHECK("surfel preprocess");
-    lg::api_prof_mark("preprocess", stream);
+    lg::prof_mark("preprocess", stream);
 
-    // the one host wait is for a copy queued BEFORE the sort (the preprocess has already summed the instance total): the device sorts
-    // while the host wakes up, sizes the binning buffer and queues the rest
-    SF_HIP((hipError_t)lg::api_read_words_begin(geom.totals, LG_TOTALS_READ_WORDS, stream));
-    lg::RadixTail span_tail;
-    span_tail.src = geom.spans; span_tail.dst = geom.span_sorted; span_tail.mode = pa.compact ? 1 : 2;
-    // the sort as in api.hip: the key's own low byte first (needs no host knowledge, queued behind the copy), then -- the host has read the
-    // frame's key span -- as many passes on key - kmin as the span has bits (2 m .. 80 m: three passes in all instead of four)
-    const bool buckets = lg::range_sort_buckets_ok((size_t)P);         // (api.hip: the bucketed range sort, whole behind the copy)
-    int first_side = 0;
-    if (buckets) lg::launch_range_sort_buckets(geom.key_a, geom.key_b, geom.id_a, geom.id_b, (size_t)P, geom.scratch, geom.totals + LG_TOTALS_KEYSPAN_WORD, span_tail, stream);
-    else first_side = lg::launch_radix_sort_pairs(geom.key_a, geom.key_b, geom.id_a, geom.id_b, (size_t)P, 8, geom.scratch, stream, 8, nullptr,
-                                                  lg::SORT_MAX_RADIX_BITS, true);   // 1: (key_b, id_b); 0: the single-launch form of small inputs ends on the a side
-    SF_CHECK("surfel range sort, first pass");
-    uint32_t totals_h[LG_TOTALS_READ_WORDS];
-    SF_HIP((hipError_t)lg::api_read_words_end(LG_TOTALS_READ_WORDS, totals_h));
-    const uint32_t* ids_sorted = geom.id_a;
-    if (!buckets) {
-        uint32_t kinv = 0u, kmax = 0u;
-        for (int slot = 0; slot < LG_INST_SLOTS; slot++) {
-            kinv = std::max(kinv, totals_h[LG_TOTALS_KEYSPAN_WORD + 2 * slot]); kmax = std::max(kmax, totals_h[LG_TOTALS_KEYSPAN_WORD + 2 * slot + 1]);
-        }
-        lg::KeyBias kb;
-        kb.kmin = (~kinv) & ~255u;                                      // a multiple of 256: (key - kmin) & 255 == key & 255
-        if (kmax < kb.kmin) { kb.kmin = 0u; kmax = 0u; }               // no visible surfel: every key is the culled one
-        kb.cull = ((kmax - kb.kmin) | 255u) + 1u;                       // above every valid key - kmin in the bits the later passes sort on
-        int bits = 32 - __builtin_clz(kb.cull | 1u);
-        if (bits < 9) bits = 9;
-        uint32_t* const k_in = first_side ? geom.key_b : geom.key_a; uint32_t* const k_out = first_side ? geom.key_a : geom.key_b;
-        uint32_t* const v_in = first_side ? geom.id_b : geom.id_a; uint32_t* const v_out = first_side ? geom.id_a : geom.id_b;
-        const int side = lg::launch_radix_sort_pairs(k_in, k_out, v_in, v_out, (size_t)P, bits, geom.scratch, stream,
-                                                     bits > 26 ? 8 : 9, nullptr, lg::SORT_MAX_RADIX_BITS, false, span_tail, 8, &kb);
-        ids_sorted = side ? v_out : v_in;
-    }
-    lg::api_prof_mark("range_sort", stream);
-    lg::launch_instance_offsets(geom.span_sorted, pa.compact != 0, TH, geom.block_off, geom.totals, (size_t)P, stream, false);   // (the emit adds the block sums up itself)
-    SF_CHECK("surfel instance scan");
-    unsigned long long total_h = 0;
-    for (int slot = 0; slot < LG_INST_SLOTS; slot++) {
-        unsigned long long v;
-        memcpy(&v, totals_h + LG_TOTALS_SLOT_WORD + 8 * slot, sizeof v);
-        total_h += v;
-    }
-    lg::api_prof_mark("scan+readback", stream);
-    const size_t R = total_h;
-    if (R > 0x7ffffffbu) return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "surfel forward: instance count overflows int");
-    const int rendered = lg::api_encode_rendered(R, TH);               // capacity | tile-height code: all the backward needs (api.hip)
-    const size_t Rp = lg::api_rendered_capacity(rendered);
-    const size_t patches = (size_t)grid.num_tiles() * grid.waves_per_tile;
-    const lg::SegPlan plan = lg::api_plan_segments(Rp, grid.waves_per_tile, 1);
-    const int S = lg::choose_segments(Rp, plan.max_segments);
-    char* bin_p = binning_alloc(binning_user, lg::sf_bin_carve(nullptr, Rp, patches, grid.waves_per_tile, S, nullptr));
-    if (!bin_p) return lg::api_fail(LIDARGS_ERR_ALLOC, "surfel forward: binning allocator returned NULL");
-    lg::SfBinView bin; lg::sf_bin_carve(bin_p, Rp, patches, grid.waves_per_tile, S, &bin);
-    const bool key16 = grid.num_tiles() <= 65536;                      // 16-bit tile keys (binning.hip launch_radix_sort_pairs16)
-    if (R) {
-        // as in api.hip: a sort that will end on the b side (an odd number of passes) gets its input there, so that the lists end on the a side
-        const int bits = lg::api_ceil_log2((uint32_t)grid.num_tiles());
-        const bool flip = lg::radix_sort_result_side(R, bits) != 0;
-        uint32_t* const k_in = flip ? bin.tile_b : bin.tile_a; uint32_t* const k_out = flip ? bin.tile_a : bin.tile_b;
-        uint32_t* const v_in = flip ? bin.val_b : bin.val_a; uint32_t* const v_out = flip ? bin.val_a : bin.val_b;
-        lg::launch_emit_instances(ids_sorted, geom.block_off, geom.span_sorted, pa.compact != 0, (size_t)P, grid, k_in, v_in, stream, 0xFFFFFFFFu, key16, img.ranges, true);
-        lg::api_prof_mark("emit", stream);
-        const int side = key16 ? lg::launch_radix_sort_pairs16(reinterpret_cast<uint16_t*>(k_in), reinterpret_cast<uint16_t*>(k_out), v_in, v_out, R, bits, bin.scratch, stream)
-                               : lg::launch_radix_sort_pairs(k_in, k_out, v_in, v_out, R, bits, bin.scratch, stream);
-        const int bside = side ^ (flip ? 1 : 0);
-        if (bside) {
-            SF_HIP(hipMemcpyAsync(bin.tile_a, bin.tile_b, R * (key16 ? sizeof(uint16_t) : sizeof(uint32_t)), hipMemcpyDeviceToDevice, stream));
-            SF_HIP(hipMemcpyAsync(bin.val_a, bin.val_b, R * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
-        }
-    }
-    lg::api_prof_mark("tile_bin", stream);
-    lg::launch_tile_ranges(bin.tile_a, R, img.ranges, grid.num_tiles(), stream, nullptr, key16, nullptr, 0, R != 0);
-    SF_CHECK("surfel binning");
-    lg::api_prof_mark("ranges", stream);
+    // the binning as the 3-D variant's (api.hip bin_frame), at the fixed tile height
+    const lg::BinSpec spec = {lg::FRAME_SURFEL, TH, 0, nullptr, "surfel forward"};
+    lg::BinnedFrame bf;
+    const int rendered = lg::bin_frame(spec, geom, img.ranges, (size_t)P, width, height, -1, -1, pa.compact != 0, binning_alloc, binning_user,
+                                       debug, stream, &bf);
+    if (rendered < 0) return rendered;
+    const lg::FrameLayout& L = bf.L;
+    const lg::BinView& bin = bf.bin;
+    const int S = L.S;
 
     lg::SfFwdArgs fa;
     fa.grid = grid; fa.ranges = img.ranges; fa.point_list = bin.val_a; fa.rec = geom.rec; fa.rowspan = geom.rowspan;
     fa.coltab = img.coltab; fa.rowtab = img.rowtab; fa.bg = background; fa.accum = img.accum; fa.n_contrib = img.n_contrib;
     fa.out_color = out_color; fa.out_others = out_others;
-    fa.seg = bin.seg; fa.S = S; fa.seg_len = plan.seg_len; fa.flags = bin.flags; fa.R = Rp; fa.touched = geom.touched;
+    fa.seg = bin.seg; fa.S = S; fa.seg_len = L.plan.seg_len; fa.flags = bin.flags; fa.R = L.Rp; fa.touched = geom.touched;
     // pass 1 in gated rounds (as the 3-D variant, api.hip run_pass1_rounds), pass 2 over what was walked, combine
     {
-        const int* rounds = plan.rounds;
-        const int nr = plan.n_rounds;
+        const int* rounds = L.plan.rounds;
+        const int nr = L.plan.n_rounds;
         fa.alive = nullptr; fa.front = 0;
         int lo = 0;
         for (int i = 0; i < nr && rounds[i] < S; i++) {
@@ -207,13 +106,13 @@ int lidargs_surfel_forward(lidargs_alloc_fn geometry_alloc, void* geometry_user,
         lg::launch_sf_render_pass1(fa, stream);
         fa.seg_lo = 0; fa.seg_hi = S;
     }
-    lg::api_prof_mark("render_pass1", stream);
+    lg::prof_mark("render_pass1", stream);
     lg::launch_sf_render_pass2(fa, stream);
-    lg::api_prof_mark("render_pass2", stream);
+    lg::prof_mark("render_pass2", stream);
     lg::launch_sf_combine(fa, stream);
     SF_CHECK("surfel render forward");
-    lg::api_prof_mark("render_combine", stream);
-    lg::api_note_forward(P, (long long)R, TH, grid.num_tiles(), S, geom.totals, bin.flags, Rp, grid.waves_per_tile, geom.touched, stream);
+    lg::prof_mark("render_combine", stream);
+    lg::note_forward((size_t)P, bf.R, L, geom.totals, bin.flags, geom.touched, nullptr, stream);
     return rendered;
 }
 
@@ -236,31 +135,25 @@ int lidargs_surfel_backward(int P, int D, int M, int R, const float* background,
     if (!means3D || !scales || !rotations || !viewmatrix || !beam_inclinations || !background || !radii || !dL_dpix || !dL_depths || !dL_dmean2D ||
         !dL_dopacity || !dL_dcolor || !dL_dmean3D || !dL_dscale || !dL_drot || !depth)   // dL_dnormal, dL_dtransMat, dL_dtransMat_2dtemp: optional
         return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "surfel backward: NULL required pointer");
-    const lg::TileGrid grid = lg::make_grid(width, height, lg::api_rendered_tile_rows(R));
-    const size_t Rp = lg::api_rendered_capacity(R);
-    lg::SfGeomView geom; lg::sf_geom_carve(geom_buffer, (size_t)P, &geom);
-    const size_t patches = (size_t)grid.num_tiles() * grid.waves_per_tile;
-    const lg::SegPlan plan = lg::api_plan_segments(Rp, grid.waves_per_tile, 1);
-    const int S = lg::choose_segments(Rp, plan.max_segments);
-    lg::SfBinView bin; lg::sf_bin_carve(binning_buffer, Rp, patches, grid.waves_per_tile, S, &bin);
-    lg::SfImgView img; lg::sf_img_carve(image_buffer, width, height, grid.num_tiles(), &img);
-    lg::api_prof_begin(stream, 1);
+    const lg::FrameLayout L = lg::frame_layout(R, width, height, -1, -1, lg::FRAME_SURFEL);
+    lg::GeomView geom; lg::geom_carve(geom_buffer, (size_t)P, lg::SURFEL_BUFFERS, &geom);
+    lg::BinView bin; L.bin_carve(binning_buffer, &bin);
+    lg::SfImgView img; lg::sf_img_carve(image_buffer, width, height, L.grid.num_tiles(), &img);
+    lg::prof_begin(stream, 1);
     lg::ZeroRows zr;                                                   // (depth is written for every surfel by k_sf_gaussian_backward)
     zr.add(dL_dmean2D, 4); zr.add(dL_dnormal, 3); zr.add(dL_dopacity, 1); zr.add(dL_dcolor, 2); zr.add(dL_dmean3D, 3); zr.add(dL_dtransMat, 9);
     zr.add(dL_dtransMat_2dtemp, 3); zr.add(dL_dscale, 2); zr.add(dL_drot, 4);
     lg::launch_zero_touched(geom.touched, reinterpret_cast<float4*>(geom.gacc), 8, (size_t)P, geom.tlist, geom.tcount, zr, stream);   // the touched surfels' lines + lists, every backward
-    lg::api_prof_mark("bwd_zero", stream);
+    lg::prof_mark("bwd_zero", stream);
     lg::SfBwdArgs ba;
-    ba.grid = grid; ba.ranges = img.ranges; ba.point_list = bin.val_a; ba.rec = geom.rec; ba.rowspan = geom.rowspan;
+    ba.grid = L.grid; ba.ranges = img.ranges; ba.point_list = bin.val_a; ba.rec = geom.rec; ba.rowspan = geom.rowspan;
     ba.coltab = img.coltab; ba.rowtab = img.rowtab; ba.bg = background; ba.accum = img.accum; ba.n_contrib = img.n_contrib;
     ba.dL_dpix = dL_dpix; ba.dL_dothers = dL_depths; ba.gacc = geom.gacc;
-    ba.seg = bin.seg; ba.S = S; ba.seg_len = plan.seg_len; ba.flags = bin.flags; ba.R = Rp;
-    {
-        ba.alive = (plan.n_rounds > 0 && plan.rounds[0] < S) ? bin.alive : nullptr;
-    }
+    ba.seg = bin.seg; ba.S = L.S; ba.seg_len = L.plan.seg_len; ba.flags = bin.flags; ba.R = L.Rp;
+    ba.alive = L.gated ? bin.alive : nullptr;
     lg::launch_sf_render_backward(ba, stream);
     SF_CHECK("surfel render backward");
-    lg::api_prof_mark("render_bwd", stream);
+    lg::prof_mark("render_bwd", stream);
     lg::SfGaussBwdArgs ga;
     ga.P = P; ga.W = width; ga.H = height; ga.view = viewmatrix; ga.means3D = means3D; ga.scales = scales; ga.rotations = rotations;
     ga.beams = beam_inclinations; ga.radii = radii; ga.transMat = transMat_precomp; ga.gacc = geom.gacc; ga.tlist = geom.tlist; ga.tcount = geom.tcount;
@@ -268,7 +161,7 @@ int lidargs_surfel_backward(int P, int D, int M, int R, const float* background,
     ga.dL_dtransMat = dL_dtransMat; ga.dL_dtransMat_2dtemp = dL_dtransMat_2dtemp; ga.dL_dscale = dL_dscale; ga.dL_drot = dL_drot; ga.depth = depth;
     lg::launch_sf_gaussian_backward(ga, stream);
     SF_CHECK("surfel gaussian backward");
-    lg::api_prof_mark("gaussian_bwd", stream);
+    lg::prof_mark("gaussian_bwd", stream);
     return 0;
 }
 
@@ -284,7 +177,7 @@ int lidargs_surfel_visible_filter(lidargs_alloc_fn geometry_alloc, void* geometr
     if (P == 0) return 0;
     if (!means3D || !scales || !rotations || !viewmatrix || !beam_inclinations || !radii || !radii_xy)
         return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "surfel visible_filter: NULL required pointer");
-    const lg::TileGrid grid = lg::make_grid(width, height, lg::api_tile_rows());
+    const lg::TileGrid grid = lg::make_grid(width, height, lg::tile_rows());
     lg::SfPreArgs pa = lg::SfPreArgs();
     pa.P = P; pa.W = width; pa.H = height; pa.TH = grid.TH; pa.tiles_x = grid.tiles_x;
     pa.scale_modifier = scale_modifier; pa.near_f = (float)lidar_near; pa.far_f = (float)lidar_far;
