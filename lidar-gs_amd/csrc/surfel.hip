@@ -107,7 +107,8 @@ struct SfPreArgs {
 // filter, :469).  So a taking pixel
 //   (3-D)  looks along a ray that hits the disc  D = { Tw + s_u Tu + s_v Tv : s_u^2 + s_v^2 <= 2 tau }  in front of the sensor: its
 //          (azimuth, elevation) is that of a point of D;
-//   (2-D)  or lies within |dx| <= sqrt(2 tau / 80), |dy| <= sqrt(2 tau / 200) of the projected centre: < 0.373 columns, < 0.236 rows.
+//   (2-D)  or lies within |dx| <= sqrt(2 tau / 80), |dy| <= sqrt(2 tau / 200) of the projected centre: for op <= 1 < 0.373 columns,
+//          < 0.236 rows; at op = 10 0.443 columns, 0.28 rows.
 // Bounds on the disc's azimuths and elevations from the sensor, with c = Tw, a = k Tu, b = k Tv (k = sqrt(2 tau)), e = c.xy / |c.xy|:
 //   horizontal distance of a disc point  >= rmin = |c.xy| - hypot(a.e, b.e),   <= rmax = |c.xy| + sqrt(|a.xy|^2 + |b.xy|^2)
 //   offset across the centre's azimuth   <= m = hypot(a x e, b x e)            =>  |d azimuth| <= atan(m / rmin) <= m / rmin
@@ -128,7 +129,12 @@ __device__ __forceinline__ SfPruned sf_prune(float3 c, float3 Tu, float3 Tv, flo
     const float uu = sdot(Tu, Tu), vv = sdot(Tv, Tv), d2 = dist * dist;
     const float rc = sqrtf(c.x * c.x + c.y * c.y);
     if (!(uu >= 1e-8f * d2 && vv >= 1e-8f * d2 && rc > 0.f)) return o;
-    const float k = sqrtf(2.f * (__logf(255.f * op) + 0.02f)) * 1.01f + 0.02f;
+    const float tau = __logf(255.f * op);
+    const float k = sqrtf(2.f * (tau + 0.02f)) * 1.01f + 0.02f;
+    // the 2-D filter's reach, sqrt(2 tau / 80) columns and sqrt(2 tau / 200) rows: the constants are its bound at op <= 1 (so that the
+    // spans of such surfels stay as they were); the C ABI does not bound the opacity, and above 1 the reach grows with tau
+    const float tau2 = 2.f * (tau + 0.01f);
+    const float f_col = fmaxf(0.373f, sqrtf(tau2 / 80.f) * 1.001f), f_row = fmaxf(0.24f, sqrtf(tau2 / 200.f) * 1.001f);
     const float ex = c.x / rc, ey = c.y / rc;
     const float a_par = Tu.x * ex + Tu.y * ey, a_prp = Tu.y * ex - Tu.x * ey, b_par = Tv.x * ex + Tv.y * ey, b_prp = Tv.y * ex - Tv.x * ey;
     const float rmin = (rc - k * sqrtf(a_par * a_par + b_par * b_par) * 1.0001f) * 0.9999f;
@@ -138,7 +144,7 @@ __device__ __forceinline__ SfPruned sf_prune(float3 c, float3 Tu, float3 Tv, flo
     // columns: pixel x is reachable iff |x - p_c + j W| <= dcol for a j in {-1, 0, 1} (the azimuth difference is the column difference
     // up to whole turns: a surfel next to the seam of the panorama is seen from its first AND its last columns, and the reference's
     // rect -- whose end points then project to the other side -- covers every tile column between them)
-    const float dcol = fmaxf(m / rmin / col_step, 0.373f) + 0.02f;
+    const float dcol = fmaxf(m / rmin / col_step, f_col) + 0.02f;
     if (2.f * dcol + 32.f < (float)W) {
         const float lo = pim.x - dcol, hi = pim.x + dcol;
         int n = 0, f0 = 0, f1 = 0, l0 = 0, l1 = 0;                    // first and last non-empty interval, in ascending tile order
@@ -163,7 +169,7 @@ __device__ __forceinline__ SfPruned sf_prune(float3 c, float3 Tu, float3 Tv, flo
     hi = H;                                                            // first beam > e_hi
     while (lo < hi) { const int md = (lo + hi) >> 1; if (beams[md] <= e_hi) lo = md + 1; else hi = md; }
     const int b_hi = lo;
-    int y0 = (int)ceilf(pim.y - 0.24f), y1 = (int)floorf(pim.y + 0.24f) + 1;         // the 2-D filter's rows [y0, y1)
+    int y0 = (int)ceilf(pim.y - f_row), y1 = (int)floorf(pim.y + f_row) + 1;       // the 2-D filter's rows [y0, y1)
     if (b_hi > b_lo) { y0 = min(y0, H - b_hi); y1 = max(y1, H - b_lo); }             // beams [b_lo, b_hi) = pixel rows [H - b_hi, H - b_lo)
     o.y0 = max(ymin, y0); o.y1 = min(ymax, y1);
     return o;

@@ -156,14 +156,23 @@ def _pack(rng, xyz, scales, rots, beams):
     )
 
 
-def make_scene(kind, P, H, seed, random_view=False, beams=None, opacity_scale=1.0):
+def make_scene(kind, P, H, seed, random_view=False, beams=None, opacity_scale=1.0, opacity=None):
     """beams: None / "uniform" (SURVEY 8d), "waymo", "neartie" (beam_table) or an explicit ascending float32[H] table.
     opacity_scale: the opacities U(0.1, 1) of SURVEY 8d times this factor.  1 = frames that saturate within a few entries (a trained
     scene); 0.1 / 0.03 = the semi-transparent frames training STARTS in (the reference's opacities are a tanh-MLP output masked > 0,
-    gaussian_renderer/__init__.py:60-70): no pixel reaches T < 1e-4 early, every list is walked to its end."""
+    gaussian_renderer/__init__.py:60-70): no pixel reaches T < 1e-4 early, every list is walked to its end.
+    opacity="bimodal": the opacities of a trained model instead, 70 % U(0.01, 0.1) and 30 % U(0.7, 1):
+    saturating and nearly transparent lists share a patch.  Drawn from a generator of their own, so every other array is the default
+    scene's, bit for bit."""
     s = shell_scene(P, H, seed, beams) if kind == "shell" else street_scene(P, H, seed, beams)
     if random_view:
         s["viewmatrix"] = rigid_viewmatrix(np.random.default_rng(seed + 7))
+    if opacity == "bimodal":
+        g = np.random.default_rng([seed, 0xB1])
+        high = g.random(P) < 0.3
+        s["opacities"] = np.where(high, g.uniform(0.7, 1.0, P), g.uniform(0.01, 0.1, P)).astype(np.float32).reshape(P, 1)
+    elif opacity is not None:
+        raise ValueError(f"unknown opacity distribution {opacity!r} (None or 'bimodal')")
     if opacity_scale != 1.0:
         s["opacities"] = (s["opacities"] * np.float32(opacity_scale)).astype(np.float32)
     return s

@@ -461,7 +461,7 @@ static void render_pixels(lgo_state* s, const float* colors_precomp, const float
                 float power = -0.5f * (co[0] * ddx * ddx + co[2] * ddy * ddy) - co[1] * ddx * ddy;
                 if (power > 0.0f) continue;
                 float a = co[3] * lgo_expf(power);
-                float alpha = 0.99f < a ? 0.99f : a;        /* min(0.99f, .) */
+                float alpha = fminf(0.99f, a);        /* min(0.99f, .): CUDA's float min is fminf, a NaN opacity gives 0.99 */
                 if (alpha < 1.0f / 255.0f) continue;
                 float test_T = T * (1 - alpha);
                 if (test_T < 0.0001f) { done = 1; T_break = test_T; continue; }
@@ -855,7 +855,7 @@ int lgo_backward_ex(const void* h, int P, int D, int M, int R, const float* back
                 if (power > 0.0f) continue;
                 const float G = lgo_expf(power);
                 const float aa = co[3] * G;
-                const float alpha = 0.99f < aa ? 0.99f : aa;
+                const float alpha = fminf(0.99f, aa);
                 if (alpha < 1.0f / 255.0f) continue;
 
                 if (lgo_accumulate_double >= 2) { Td = Td / (double)(1.f - alpha); T = (float)Td; } else T = T / (1.f - alpha);

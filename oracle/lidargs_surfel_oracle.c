@@ -434,7 +434,7 @@ void* sfo_forward_tm(int P, const float* background, int width, int height, cons
                 float power = -0.5f * q.rho;
                 if (power > 0.0f) continue;
                 float a = q.opa * sf_expf(power);
-                float alpha = 0.99f < a ? 0.99f : a;
+                float alpha = fminf(0.99f, a);                 /* CUDA's float min is fminf: a NaN opacity gives 0.99 */
                 if (alpha < 1.0f / 255.0f) continue;
                 float test_T = T * (1 - alpha);
                 if (test_T < 0.0001f) { done = 1; continue; }
@@ -542,7 +542,7 @@ int sfo_backward(const void* h, int P, int R, const float* background, int width
                 if (power > 0.0f) continue;
                 const float G = sf_expf(power);
                 const float aa = q.opa * G;
-                const float alpha = 0.99f < aa ? 0.99f : aa;
+                const float alpha = fminf(0.99f, aa);
                 if (alpha < 1.0f / 255.0f) continue;
                 if (sfo_accumulate_double >= 2) { Td = Td / (double)(1.f - alpha); T = (float)Td; } else T = T / (1.f - alpha);
                 const float dchannel_dcolor = alpha * T;

@@ -121,7 +121,7 @@ def _wedge_subset(scene, W, radii, c0, c1):
     return (pc >= c0 - reach) & (pc <= c1 + reach)
 
 
-@pytest.mark.parametrize("cfg", ["cfg2", "cfg3", "cfg4", "cfg3_waymo", "cfg2_neartie", "cfg3_thin"])
+@pytest.mark.parametrize("cfg", ["cfg2", "cfg3", "cfg4", "cfg3_waymo", "cfg2_neartie", "cfg3_thin", "cfg3_bimodal"])
 def test_fullsize_wedge_matches_oracle(cfg, hip_lib_built):
     """The headline frame's own code path, value by value (see the module docstring).  cfg4 (8 M Gaussians @ 128 x 4096) runs at
     the adaptive 16- or 32-row tile height; cfg2 / cfg3 on the fine segment plan (64-entry segments, 45 slots, gated first round).
@@ -129,15 +129,17 @@ def test_fullsize_wedge_matches_oracle(cfg, hip_lib_built):
     configs really read from the dataset json (scene/dataset_readers.py:358-359); radii must then agree with 0 mismatches.
     `cfg3_thin` (round 6): the 2 M-Gaussian frame with every opacity x 0.1 -- the semi-transparent state training starts in
     (gaussian_renderer/__init__.py:60-70): no pixel saturates early, every segment of every list is walked and handed over, the
-    `alive` gates stay open and the slot plan fills; the regime the saturating street scene never visits at this size."""
+    `alive` gates stay open and the slot plan fills; the regime the saturating street scene never visits at this size.
+    `cfg3_bimodal`: the same frame with a trained model's opacities (lidargs_scenes.make_scene opacity="bimodal": 70 % U(0.01, 0.1),
+    30 % U(0.7, 1)) -- saturating and nearly transparent lists in one patch, what the gated rounds and the slot plans see in training."""
     from diff_lidargs_rasterization import _C
     from util import GRAD_KEYS_SR, hip_forward_backward, oracle_forward_backward, parity
     cfg, _, table = cfg.partition("_")
-    thin = table == "thin"
-    if thin:
+    thin, bimodal = table == "thin", table == "bimodal"
+    if thin or bimodal:
         table = ""
     kind, P, H, W, seed = sc.BASELINE_CONFIGS[cfg]
-    scene = sc.make_scene(kind, P, H, seed, beams=table or None, opacity_scale=0.1 if thin else 1.0)
+    scene = sc.make_scene(kind, P, H, seed, beams=table or None, opacity_scale=0.1 if thin else 1.0, opacity="bimodal" if bimodal else None)
     grads = sc.upstream_grads(H, W, seed)
     hip = hip_forward_backward(scene, W, H, grads)                    # the FULL frame
     cnt = _C.last_counters()
@@ -172,7 +174,7 @@ def test_fullsize_wedge_matches_oracle(cfg, hip_lib_built):
         inside = (ref["radii"] > 0) & (hip["radii"][rows] > 0) & (x_lo >= c0) & (x_hi <= c1)
         assert inside.sum() > 2000, inside.sum()
         print(f"[wedge] {cfg} columns [{c0},{c1}): {int(inside.sum())} Gaussians with their whole rect inside")
-        if thin:    # opacities 0.01-0.1: a large share of the (pixel, Gaussian) pairs sits near the alpha >= 1/255 threshold (R3/cr/forward.cu:607),
+        if thin or bimodal:    # opacities 0.01-0.1: a large share of the (pixel, Gaussian) pairs sits near the alpha >= 1/255 threshold (R3/cr/forward.cu:607),
                     # and every gradient row is a long float32 sum: where the plain budget is exceeded the excess must be the oracle's
                     # summation error or lie in the reference's own band (util.parity_or_closer)
             from util import oracle_backward_exact_sums, oracle_envelope, parity_or_closer
@@ -185,7 +187,7 @@ def test_fullsize_wedge_matches_oracle(cfg, hip_lib_built):
                     env.update(lo=lo, hi=hi)
                 return env["lo"][k][inside], env["hi"][k][inside]
             for k in GRAD_KEYS_SR:
-                parity_or_closer(f"{cfg}_thin.{k}[wedge]", hip[k][rows[inside]], ref[k][inside], ref64[k][inside], band=lambda k=k: band(k))
+                parity_or_closer(f"{cfg}_{'thin' if thin else 'bimodal'}.{k}[wedge]", hip[k][rows[inside]], ref[k][inside], ref64[k][inside], band=lambda k=k: band(k))
             continue
         for k in GRAD_KEYS_SR:
             parity(f"{cfg}.{k}[wedge]", hip[k][rows[inside]], ref[k][inside])

@@ -273,3 +273,33 @@ def test_torch_cpu_preprocess_baseline_agrees_with_the_oracle():
         radii, tiles = pt.preprocess(t(s["means3D"]), t(s["scales"]), t(s["rotations"]), t(s["viewmatrix"]), t(s["beams"]), W, H)
         assert (radii.numpy() == f.radii).mean() > 0.999
         assert abs(int(tiles.sum()) - f.num_rendered) <= 1e-3 * f.num_rendered
+
+
+@pytest.mark.parametrize("op", [np.nan, np.inf], ids=["nan", "inf"])
+def test_nonfinite_opacity_blends_at_the_clamp(op):
+    """alpha = min(0.99f, o G) (R3/cr/forward.cu:607) is CUDA's float min, i.e. fminf: a NaN opacity gives alpha = 0.99, and so does +inf
+    (inf x G is inf, and NaN where G underflows to 0).  Every pixel of the binned rect takes the Gaussian at 0.99; its colour and opacity
+    gradients stay finite (dL/do = G dL/dalpha), its geometry gradients do not (dL/dG = o dL/dalpha)."""
+    from util import placed_scene
+    W, H = 64, 8
+    scene = placed_scene([27.3], [3.4], 10.0, 0.05, op, W, H)
+    scene["colors"][:] = 1.0
+    f = _run(scene, W, H)
+    lit = f.color[0] != 0
+    assert int(lit.sum()) == 16 * int(f.array("tiles_touched")[0]) > 0       # the whole rect: 16-column tiles, W a multiple of 16
+    assert (f.color[:, lit] == np.float32(0.99)).all() and (f.occ[0][lit] == np.float32(0.99)).all()
+    g = lgo.backward(f, *sc.upstream_grads(H, W, 0))
+    assert np.isfinite(g["dL_dcolors"]).all() and np.isfinite(g["dL_dopacity"]).all()
+    assert not np.isfinite(g["dL_dmeans3D"]).any()
+
+
+def test_bimodal_opacities_change_nothing_else():
+    base = sc.make_scene("street", 5000, 16, 11, random_view=True)
+    bi = sc.make_scene("street", 5000, 16, 11, random_view=True, opacity="bimodal")
+    for k in base:
+        if k != "opacities":
+            np.testing.assert_array_equal(bi[k], base[k])
+    o = bi["opacities"].ravel()
+    high = o >= 0.7
+    assert 0.27 < high.mean() < 0.33 and (o[~high] >= 0.01).all() and (o[~high] <= 0.1).all() and (o <= 1.0).all()
+    np.testing.assert_array_equal(sc.make_scene("street", 5000, 16, 11, opacity="bimodal")["opacities"], bi["opacities"])

@@ -258,6 +258,36 @@ print("OK")
     assert r.returncode == 0 and "OK" in r.stdout
 
 
+@pytest.mark.parametrize("env", [{"LIDARGS_HEAD": "1"}, {"LIDARGS_HEAD": "0", "LIDARGS_SEG_LEN": "128"}, {"LIDARGS_FUSED": "0"},
+                                 {"LIDARGS_FUSED": "0", "LIDARGS_WORK_LISTS": "0"}, {"LIDARGS_FUSED": "1", "LIDARGS_SEG_LEN": "128"}, {}],
+                         ids=["head5", "nohead_seg128", "five_launch_forward", "backward_on_the_slot_grid", "fused_on_128_entry_segments", "defaults"])
+def test_plan_variants_are_invisible_on_bimodal_opacities(env, hip_lib_built):
+    """test_plan_variants_are_invisible on a trained model's opacities (lidargs_scenes.make_scene opacity="bimodal": 70 % U(0.01, 0.1), 30 %
+    U(0.7, 1)): saturating and nearly transparent lists share every patch, so the gated rounds close some pixels of a patch early while
+    the others walk their whole lists -- the regime the head, the segment plans and the two backward schedules are tuned for least."""
+    import os, subprocess, sys
+    code = r"""
+import sys, numpy as np
+sys.path[:0] = [%r, %r, %r]
+import lidargs_scenes as sc
+from util import hip_forward_backward, oracle_forward_backward, parity, GRAD_KEYS_SR
+P, H, W, seed = 60000, 32, 800, 11
+scene = sc.make_scene("street", P, H, seed, random_view=True, opacity="bimodal")
+grads = sc.upstream_grads(H, W, seed)
+ref = oracle_forward_backward(scene, W, H, grads)
+hip = hip_forward_backward(scene, W, H, grads)
+assert int((hip["radii"] != ref["radii"]).sum()) <= 1
+for k in ("color", "depth", "occ") + GRAD_KEYS_SR:
+    parity("bimodal." + k, hip[k], ref[k])
+print("OK")
+"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = code % (root, os.path.join(root, "lidar-gs_amd"), os.path.join(root, "tests"))
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
+    print(r.stdout[-3000:], r.stderr[-3000:])
+    assert r.returncode == 0 and "OK" in r.stdout
+
+
 @pytest.mark.parametrize("H,W", [(16, 4128), (272, 512)], ids=["258_tile_columns", "272_rows"])
 def test_images_too_big_for_compact_span_records(H, W, hip_lib_built):
     """The per-Gaussian span record the tile lists are built from is ONE 32-bit word while the image has at most 256 tile columns

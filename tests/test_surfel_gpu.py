@@ -281,16 +281,19 @@ def test_surfel_config5_fullsize_properties():
     torch.cuda.synchronize()
 
 
-@pytest.mark.parametrize("opacity_scale", [1.0, 0.1], ids=["cfg5", "cfg5_thin"])
+@pytest.mark.parametrize("opacity_scale", [1.0, 0.1, "bimodal"], ids=["cfg5", "cfg5_thin", "cfg5_bimodal"])
 def test_surfel_config5_fullsize_wedge_matches_oracle(opacity_scale):
     """BASELINE config 5 at full size, value by value: the FULL 2 M-surfel frame is rendered on the GPU (the production segment plan:
     96-entry segments, 45 slots, gated first round), the oracle renders every surfel that can reach an azimuth wedge; the wedge's
     pixels and the gradients of the surfels whose whole rect lies inside it are compared under the rules of `_check`.
-    `cfg5_thin` (round 6): opacities x 0.1 -- the semi-transparent, early-training regime where no list saturates early."""
+    `cfg5_thin` (round 6): opacities x 0.1 -- the semi-transparent, early-training regime where no list saturates early.
+    `cfg5_bimodal`: a trained model's opacities (lidargs_scenes.make_scene opacity="bimodal"): saturating and transparent lists in one patch."""
     import lidargs_scenes as sc
     kind, P, H, W, seed = sc.BASELINE_CONFIGS["cfg5"]
-    scene = surfel_scene(kind, P, H, seed, random_view=False)
-    scene["opacities"] = (scene["opacities"] * np.float32(opacity_scale)).astype(np.float32)
+    bimodal = opacity_scale == "bimodal"
+    scene = surfel_scene(kind, P, H, seed, random_view=False, opacity="bimodal" if bimodal else None)
+    if not bimodal:
+        scene["opacities"] = (scene["opacities"] * np.float32(opacity_scale)).astype(np.float32)
     g = surfel_upstream_grads(H, W, seed)
     g[1][5] = 0.0            # the median-depth plane is a selection: its pixels are compared below, its gradient in the small cases
     hip = hip_surfel_forward_backward(scene, W, H, g)
@@ -331,7 +334,7 @@ def test_surfel_config5_fullsize_wedge_matches_oracle(opacity_scale):
             from util import oracle_backward_exact_sums, parity_or_closer
             ref64 = oracle_backward_exact_sums(ref, g, surfel=True)
             for k in GRAD_KEYS_SURFEL:
-                parity_or_closer(f"cfg5_thin.{k}[wedge]", hip[k][rows[inside]], ref[k][inside], ref64[k][inside])
+                parity_or_closer(f"cfg5_{'bimodal' if bimodal else 'thin'}.{k}[wedge]", hip[k][rows[inside]], ref[k][inside], ref64[k][inside])
             continue
         for k in GRAD_KEYS_SURFEL:
             parity(f"cfg5.{k}[wedge]", hip[k][rows[inside]], ref[k][inside])

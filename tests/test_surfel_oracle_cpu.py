@@ -153,3 +153,20 @@ def test_empty_input():
     e = {k: (v[:0] if k in ("means3D", "colors", "opacities", "scales", "rotations") else v) for k, v in sc.items()}
     f = _fwd(e)
     assert f.num_rendered == 0 and f.color.shape == (2, H, W) and (f.others == 0).all()
+
+
+@pytest.mark.parametrize("op", [np.nan, np.inf], ids=["nan", "inf"])
+def test_nonfinite_opacity_blends_at_the_clamp(op):
+    """alpha = min(0.99f, opa exp(power)) (R2/cr/forward.cu:484) is CUDA's float min, fminf: a NaN or +inf opacity takes every pixel of the
+    binned rect at 0.99 (for +inf where G underflows too: inf x 0 is NaN), with finite colour and opacity gradients."""
+    from util import placed_scene
+    W_, H_ = 64, 8
+    scene = placed_scene([27.3], [3.4], 20.0, 0.02, op, W_, H_, surfel=True)
+    scene["colors"][:] = 1.0
+    f = lgo_surfel.forward(scene["means3D"], scene["colors"], scene["opacities"], scene["scales"], scene["rotations"], scene["viewmatrix"],
+                           scene["beams"], W_, H_, bg=scene["bg"])
+    lit = f.color[0] != 0
+    assert int(lit.sum()) == 16 * int(f.array("tiles_touched")[0]) > 0
+    assert (f.color[:, lit] == np.float32(0.99)).all()
+    g = lgo_surfel.backward(f, *surfel_upstream_grads(H_, W_, 0))
+    assert np.isfinite(g["dL_dcolors"]).all() and np.isfinite(g["dL_dopacity"]).all()

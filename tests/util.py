@@ -188,9 +188,9 @@ GRAD_KEYS_SR = ("dL_dmeans3D", "dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_d
 GRAD_KEYS_SURFEL = ("dL_dmeans3D", "dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dscales", "dL_drotations")
 
 
-def surfel_scene(kind, P, H, seed, random_view=True):
+def surfel_scene(kind, P, H, seed, random_view=True, **kw):
     import lidargs_scenes as sc
-    s = sc.make_scene(kind, P, H, seed, random_view=random_view)
+    s = sc.make_scene(kind, P, H, seed, random_view=random_view, **kw)
     s["scales"] = np.ascontiguousarray(s["scales"][:, :2])
     return s
 
@@ -328,3 +328,50 @@ def envelope_residue(hip, base, lo, hi, k, rtol=RTOL, floor=FLOOR):
     return dict(n=int(r.size), hip_over=int(off.sum()), oracle_band_over=int((band > rtol).sum()),
                 hip_over_where_oracle_moves=int((off & (band > rtol)).sum()), hip_over_where_oracle_moves_half=int((off & (band > 0.5 * rtol)).sum()),
                 worst_outside_in_widths=float(rel_out[off].max()) if off.any() else 0.0, worst_outside_anywhere=float(rel_out.max()))
+
+
+# ---- scenes built pixel by pixel (tests/test_opacity_domain_gpu.py, tests/test_oracle_cpu.py) ---------------------------------------
+def pixel_direction(pc, py, W, H, beams):
+    """Unit view-space direction whose projection is (column pc, row py), fractional, as the forward projects a centre: azimuth
+    pi - pc 2 pi / W (column x looks along beta = pi - x 2 pi / W, R3/cr/forward.cu:589), elevation interpolated linearly between the
+    beams of the rows around py (row y is beam H - 1 - y).  float64 arrays."""
+    pc, py = np.asarray(pc, np.float64), np.asarray(py, np.float64)
+    b = np.asarray(beams, np.float64)
+    pr = (H - 1) - py
+    i = np.clip(np.floor(pr).astype(np.int64), 0, H - 2)
+    el = b[i] + (pr - i) * (b[i + 1] - b[i])
+    az = np.pi - pc * (2.0 * np.pi / W)
+    return np.stack([np.cos(el) * np.cos(az), np.cos(el) * np.sin(az), np.sin(el)], axis=-1)
+
+
+def _quat_from_matrix(R):
+    """(r, x, y, z) unit quaternions of the proper rotations R [n, 3, 3] (columns = the images of the local axes)."""
+    tr = R[:, 0, 0] + R[:, 1, 1] + R[:, 2, 2]
+    r = np.sqrt(np.maximum(1.0 + tr, 1e-12)) / 2.0
+    q = np.stack([r, (R[:, 2, 1] - R[:, 1, 2]) / (4 * r), (R[:, 0, 2] - R[:, 2, 0]) / (4 * r), (R[:, 1, 0] - R[:, 0, 1]) / (4 * r)], axis=1)
+    return q / np.linalg.norm(q, axis=1, keepdims=True)
+
+
+def placed_scene(pc, py, dist, sigma, opacity, W, H, beams=None, surfel=False, seed=0):
+    """Gaussians (surfel=False: isotropic, scales [P,3]) or surfels facing the sensor (scales [P,2]) centred at the given fractional pixel
+    coordinates (pixel_direction) and distances; sigma = the scale in metres, per entry or one for all.  Identity view, background 0,
+    colours U(0.2, 1)."""
+    import lidargs_scenes as sc
+    beams = sc.beam_inclinations(H) if beams is None else np.asarray(beams, np.float32)
+    d = pixel_direction(pc, py, W, H, beams)
+    P = d.shape[0]
+    rng = np.random.default_rng(seed)
+    sigma = np.broadcast_to(np.asarray(sigma, np.float64), (P,))
+    if surfel:
+        n = -d                                                        # the normal points back at the sensor
+        e1 = np.cross(np.array([0.0, 0.0, 1.0]), n); e1 /= np.linalg.norm(e1, axis=1, keepdims=True)
+        e2 = np.cross(n, e1)
+        rots = _quat_from_matrix(np.stack([e1, e2, n], axis=2))
+        scales = np.stack([sigma, sigma], axis=1)
+    else:
+        rots = np.tile(np.array([[1.0, 0.0, 0.0, 0.0]]), (P, 1))
+        scales = np.stack([sigma, sigma, sigma], axis=1)
+    return dict(means3D=(d * np.asarray(dist, np.float64).reshape(-1, 1)).astype(np.float32), scales=scales.astype(np.float32),
+                rotations=rots.astype(np.float32), opacities=np.broadcast_to(np.asarray(opacity, np.float32), (P,)).reshape(P, 1).copy(),
+                colors=rng.uniform(0.2, 1.0, (P, 2)).astype(np.float32), beams=beams, bg=np.zeros(2, np.float32),
+                viewmatrix=sc.rigid_viewmatrix(None))
