@@ -333,3 +333,41 @@ def anchor_scene(N, k, seed, voxel=0.01, feat_dim=32):
     return dict(N=N, k=k, voxel=voxel, anchor=anchor, offset=rng.uniform(-1, 1, (N, k, 3)).astype(np.float32),
                 scaling=np.log(rng.uniform(0.02, 0.4, (N, 6))).astype(np.float32), feat=rng.normal(size=(N, feat_dim)).astype(np.float32),
                 grads=rng.exponential(0.0002, N * k).astype(np.float32), offset_mask=rng.random(N * k) > 0.3)
+
+
+def accumulated_scan(P, seed, poses=8, dup_frac=0.03, n_outliers=8):
+    """An accumulated LiDAR scan (the point cloud GaussianModel.create_from_pcd starts from; tests/test_knn_gpu.py, tools/time_knn.py):
+    rays cast from `poses` sensor positions 1.8 m above a road along x (every 30 m) into a ground plane z = 0 and two walls y = +-12
+    (0 <= z <= 8, all along the road), with directions uniform over the beam fan (elevation -25..+5 deg, any azimuth): the point
+    density falls like 1 / r^2 around every pose, from millimetres at the sensor to metres at 80 m.  Hits beyond 120 m are dropped;
+    ranges carry 1 cm of noise.  Then `dup_frac` of the rows are exact copies of others and `n_outliers` rows lie 1e3 - 1e6 m away.
+    Rows in random order; float32 [P, 3].  Its own generator: no other scene changes."""
+    rng = np.random.default_rng([seed, 0x5CA7])
+    n_out = min(n_outliers, P)
+    n_dup = min(int(dup_frac * P), P - n_out)
+    n_hit = P - n_out - n_dup
+    hits, got = [], 0
+    while got < n_hit:
+        m = max(1024, int(1.6 * (n_hit - got)))
+        k = rng.integers(0, poses, m)
+        o = np.stack([30.0 * k, np.zeros(m), np.full(m, 1.8)], 1)
+        az = rng.uniform(-np.pi, np.pi, m)
+        el = np.deg2rad(rng.uniform(-25.0, 5.0, m))
+        d = np.stack([np.cos(el) * np.cos(az), np.cos(el) * np.sin(az), np.sin(el)], 1)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            t_g = np.where(d[:, 2] < 0, -o[:, 2] / d[:, 2], np.inf)
+            t_w = np.where(np.abs(d[:, 1]) > 1e-9, (12.0 * np.sign(d[:, 1]) - o[:, 1]) / d[:, 1], np.inf)
+        z_w = o[:, 2] + t_w * d[:, 2]
+        t_w = np.where((z_w <= 8.0) & (z_w >= 0.0), t_w, np.inf)
+        t = np.minimum(t_g, t_w)
+        ok = t < 120.0
+        t = t[ok] + rng.normal(0.0, 0.01, int(ok.sum()))
+        h = o[ok] + t[:, None] * d[ok]
+        hits.append(h[: n_hit - got]); got += min(h.shape[0], n_hit - got)
+    xyz = np.concatenate(hits, 0) if hits else np.zeros((0, 3))
+    if n_dup:
+        xyz = np.concatenate([xyz, xyz[rng.integers(0, max(n_hit, 1), n_dup)]], 0) if n_hit else np.concatenate([xyz, np.zeros((n_dup, 3))], 0)
+    if n_out:
+        u = rng.normal(size=(n_out, 3)); u /= np.linalg.norm(u, axis=1, keepdims=True)
+        xyz = np.concatenate([xyz, u * 10.0 ** rng.uniform(3.0, 6.0, (n_out, 1))], 0)
+    return xyz[rng.permutation(P)].astype(np.float32)
