@@ -31,6 +31,7 @@ SOURCES = {
     "surfel.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],   # ray/plane hit point cancels ~3 digits: round as the reference writes it
     "anchor_growing.hip": ["-ffp-contract=off"],   # anchor + offset * scaling is two roundings in torch: the voxel an offset falls into is compared bit for bit
     "knn.hip": ["-ffp-contract=off"],              # the 3-NN squared distances and the voxel quotients are compared bit for bit; the box bound prunes exactly only without contraction
+    "metrics.hip": ["-ffp-contract=off"],          # the SSIM map and the float32 means round as scikit-image / torch write them
 }
 
 
