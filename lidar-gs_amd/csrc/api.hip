@@ -678,6 +678,50 @@ int backward_impl(int P, int R, const float* background, int width, int height, 
     return 0;
 }
 
+// The first steps of a two-step or an enqueue-only selection, either cut: check the scratch (`too_small`: the caller's message), carve
+// flags / offsets / total / scan scratch out of it, run the cut's flags launch (`launch_flags(flags)`), then the exclusive scan.
+struct SelectScan { uint32_t* flags; uint32_t* offs; uint32_t* total; };
+template <class LaunchFlags>
+int select_scan(int P, char* scratch, size_t scratch_bytes, const char* too_small, hipStream_t stream, SelectScan& s, LaunchFlags launch_flags) {
+    if (scratch_bytes < lidargs_shell_select_scratch_bytes(P)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, too_small);
+    lg::Carver c(scratch);
+    s.flags = c.take<uint32_t>((size_t)P);
+    s.offs = c.take<uint32_t>((size_t)P);
+    s.total = c.take<uint32_t>(64);
+    uint32_t* scan_scratch = c.take<uint32_t>(lg::scan_scratch_words((size_t)P));
+    launch_flags(s.flags);
+    lg::launch_exclusive_scan(s.flags, s.offs, (size_t)P, s.total, scan_scratch, stream);
+    return 0;
+}
+
+// the count step: the scan, then the one host read of its total
+template <class LaunchFlags>
+int select_count(int P, char* scratch, size_t scratch_bytes, const char* too_small, hipStream_t stream, LaunchFlags launch_flags) {
+    SelectScan s;
+    if (const int rc = select_scan(P, scratch, scratch_bytes, too_small, stream, s, launch_flags)) return rc;
+    uint32_t total_h = 0;
+    LG_HIP((hipError_t)lg::api_read_words_zero_behind(s.total, 1, &total_h, nullptr, 0, stream));
+    return (int)total_h;
+}
+
+// Enqueue-only selections (no host read): flags + scan as above, then the gather into CAPACITY rows.  idx_out's tail is filled with
+// 0x7F7F7F7F (above every index: the array stays ascending, and every consumer skips indices >= P); n_valid_dev[0] = rows gathered =
+// min(selected, capacity), [1] = rows selected; both words go to status_host (pinned, optional) behind the launches.
+template <class LaunchFlags>
+int select_enqueue(int P, const float* means3D, const float* colors, const float* opacities, const float* scales, const float* rotations,
+                   int capacity, int* idx_out, float* out_means3D, float* out_colors, float* out_opacities, float* out_scales, float* out_rotations,
+                   unsigned* n_valid_dev, unsigned* status_host, char* scratch, size_t scratch_bytes, const char* too_small, int chunk_rows,
+                   int world, float* chunk_counts, hipStream_t stream, LaunchFlags launch_flags) {
+    SelectScan s;
+    if (const int rc = select_scan(P, scratch, scratch_bytes, too_small, stream, s, launch_flags)) return rc;
+    if (chunk_counts && (chunk_rows <= 0 || world <= 0 || world > 256)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "select (enqueue-only): chunk counts need chunk_rows > 0 and 1 <= world <= 256%s");
+    LG_HIP(hipMemsetAsync(idx_out, 0x7F, sizeof(int) * (size_t)capacity, stream));
+    lg::launch_shell_gather(P, s.flags, s.offs, means3D, colors, opacities, scales, rotations, idx_out, out_means3D, out_colors, out_opacities,
+                            out_scales, out_rotations, stream, (uint32_t)capacity, s.total, n_valid_dev, chunk_rows, world, chunk_counts);
+    if (status_host) LG_HIP(hipMemcpyAsync(status_host, n_valid_dev, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+    return check_launch(stream, 0, "select gather (enqueue-only)");
+}
+
 }  // namespace
 
 extern "C" {
@@ -867,25 +911,6 @@ int lidargs_backward_wedge(int P, int R, const float* background, int width, int
                          dL_dscale, dL_drot, debug, (hipStream_t)stream, col_lo, col_hi);
 }
 
-int lidargs_wedge_select_count(int P, const float* means3D, const float* scales, const float* rotations, float scale_modifier,
-                               const float* viewmatrix, int width, int col_lo, int col_hi, char* scratch, size_t scratch_bytes, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (P < 0 || width <= 0 || col_lo < 0 || col_hi <= col_lo) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "wedge_select: bad sizes%s");
-    if (P == 0) return 0;
-    if (!means3D || !viewmatrix || !scratch) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "wedge_select: NULL pointer%s");
-    if (scratch_bytes < lidargs_shell_select_scratch_bytes(P)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "wedge_select: scratch too small%s");
-    lg::Carver c(scratch);
-    uint32_t* flags = c.take<uint32_t>((size_t)P);
-    uint32_t* offs = c.take<uint32_t>((size_t)P);
-    uint32_t* total = c.take<uint32_t>(64);
-    uint32_t* scan_scratch = c.take<uint32_t>(lg::scan_scratch_words((size_t)P));
-    lg::launch_wedge_flags(P, means3D, scales, rotations, scale_modifier, viewmatrix, width, col_lo, col_hi, flags, stream);
-    lg::launch_exclusive_scan(flags, offs, (size_t)P, total, scan_scratch, stream);
-    uint32_t total_h = 0;
-    LG_HIP((hipError_t)lg::api_read_words_zero_behind(total, 1, &total_h, nullptr, 0, stream));
-    return (int)total_h;
-}
-
 int lidargs_wedge_pack_columns(int height, int width, int col_lo, int col_hi, int wmax, const float* color, const float* depth, const float* occ,
                                float* out, void* stream) {
     if (height <= 0 || width <= 0 || col_lo < 0 || col_hi <= col_lo || col_hi > width || wmax < col_hi - col_lo || !color || !depth || !occ || !out)
@@ -1055,17 +1080,20 @@ int lidargs_shell_select_count(int P, const float* means3D, const float* viewmat
     if (P < 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "shell_select: P < 0%s");
     if (P == 0) return 0;
     if (!means3D || !viewmatrix || !scratch) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "shell_select: NULL pointer%s");
-    if (scratch_bytes < lidargs_shell_select_scratch_bytes(P)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "shell_select: scratch too small%s");
-    lg::Carver c(scratch);
-    uint32_t* flags = c.take<uint32_t>((size_t)P);
-    uint32_t* offs = c.take<uint32_t>((size_t)P);
-    uint32_t* total = c.take<uint32_t>(64);
-    uint32_t* scan_scratch = c.take<uint32_t>(lg::scan_scratch_words((size_t)P));
-    lg::launch_shell_flags(P, means3D, viewmatrix, shell_lo, shell_hi, flags, stream);
-    lg::launch_exclusive_scan(flags, offs, (size_t)P, total, scan_scratch, stream);
-    uint32_t total_h = 0;
-    LG_HIP((hipError_t)lg::api_read_words_zero_behind(total, 1, &total_h, nullptr, 0, stream));
-    return (int)total_h;
+    return select_count(P, scratch, scratch_bytes, "shell_select: scratch too small%s", stream, [&](uint32_t* flags) {
+        lg::launch_shell_flags(P, means3D, viewmatrix, shell_lo, shell_hi, flags, stream);
+    });
+}
+
+int lidargs_wedge_select_count(int P, const float* means3D, const float* scales, const float* rotations, float scale_modifier,
+                               const float* viewmatrix, int width, int col_lo, int col_hi, char* scratch, size_t scratch_bytes, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (P < 0 || width <= 0 || col_lo < 0 || col_hi <= col_lo) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "wedge_select: bad sizes%s");
+    if (P == 0) return 0;
+    if (!means3D || !viewmatrix || !scratch) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "wedge_select: NULL pointer%s");
+    return select_count(P, scratch, scratch_bytes, "wedge_select: scratch too small%s", stream, [&](uint32_t* flags) {
+        lg::launch_wedge_flags(P, means3D, scales, rotations, scale_modifier, viewmatrix, width, col_lo, col_hi, flags, stream);
+    });
 }
 
 int lidargs_shell_select_gather(int P, const float* means3D, const float* colors, const float* opacities, const float* scales,
@@ -1092,23 +1120,6 @@ int lidargs_shell_select_gather(int P, const float* means3D, const float* colors
     return check_launch(stream, 0, "shell select gather");
 }
 
-// Enqueue-only selections (no host read): flags + scan as above, then the gather into CAPACITY rows.  idx_out's tail is filled with
-// 0x7F7F7F7F (above every index: the array stays ascending, and every consumer skips indices >= P); n_valid_dev[0] = rows gathered =
-// min(selected, capacity), [1] = rows selected; both words go to status_host (pinned, optional) behind the launches.
-namespace {
-int select_gather_capped(int P, const float* means3D, const float* colors, const float* opacities, const float* scales, const float* rotations,
-                         int capacity, int* idx_out, float* out_means3D, float* out_colors, float* out_opacities, float* out_scales,
-                         float* out_rotations, unsigned* n_valid_dev, unsigned* status_host, const uint32_t* flags, const uint32_t* offs,
-                         const uint32_t* total, int chunk_rows, int world, float* chunk_counts, hipStream_t stream) {
-    if (chunk_counts && (chunk_rows <= 0 || world <= 0 || world > 256)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "select (enqueue-only): chunk counts need chunk_rows > 0 and 1 <= world <= 256%s");
-    LG_HIP(hipMemsetAsync(idx_out, 0x7F, sizeof(int) * (size_t)capacity, stream));
-    lg::launch_shell_gather(P, flags, offs, means3D, colors, opacities, scales, rotations, idx_out, out_means3D, out_colors, out_opacities,
-                            out_scales, out_rotations, stream, (uint32_t)capacity, total, n_valid_dev, chunk_rows, world, chunk_counts);
-    if (status_host) LG_HIP(hipMemcpyAsync(status_host, n_valid_dev, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, stream));
-    return check_launch(stream, 0, "select gather (enqueue-only)");
-}
-}  // namespace
-
 int lidargs_shell_select_enqueue(int P, const float* means3D, const float* colors, const float* opacities, const float* scales,
                                  const float* rotations, const float* viewmatrix, float shell_lo, float shell_hi, int capacity, int* idx_out,
                                  float* out_means3D, float* out_colors, float* out_opacities, float* out_scales, float* out_rotations,
@@ -1119,16 +1130,11 @@ int lidargs_shell_select_enqueue(int P, const float* means3D, const float* color
     if (!means3D || !colors || !opacities || !scales || !rotations || !viewmatrix || !idx_out || !out_means3D || !out_colors || !out_opacities ||
         !out_scales || !out_rotations || !n_valid_dev || !scratch)
         return fail(LIDARGS_ERR_INVALID_ARGUMENT, "shell_select_enqueue: NULL pointer%s");
-    if (scratch_bytes < lidargs_shell_select_scratch_bytes(P)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "shell_select_enqueue: scratch too small%s");
-    lg::Carver c(scratch);
-    uint32_t* flags = c.take<uint32_t>((size_t)P);
-    uint32_t* offs = c.take<uint32_t>((size_t)P);
-    uint32_t* total = c.take<uint32_t>(64);
-    uint32_t* scan_scratch = c.take<uint32_t>(lg::scan_scratch_words((size_t)P));
-    lg::launch_shell_flags(P, means3D, viewmatrix, shell_lo, shell_hi, flags, stream);
-    lg::launch_exclusive_scan(flags, offs, (size_t)P, total, scan_scratch, stream);
-    return select_gather_capped(P, means3D, colors, opacities, scales, rotations, capacity, idx_out, out_means3D, out_colors, out_opacities,
-                                out_scales, out_rotations, n_valid_dev, status_host, flags, offs, total, chunk_rows, world, chunk_counts, stream);
+    return select_enqueue(P, means3D, colors, opacities, scales, rotations, capacity, idx_out, out_means3D, out_colors, out_opacities, out_scales,
+                          out_rotations, n_valid_dev, status_host, scratch, scratch_bytes, "shell_select_enqueue: scratch too small%s", chunk_rows,
+                          world, chunk_counts, stream, [&](uint32_t* flags) {
+                              lg::launch_shell_flags(P, means3D, viewmatrix, shell_lo, shell_hi, flags, stream);
+                          });
 }
 
 int lidargs_wedge_select_enqueue(int P, const float* means3D, const float* colors, const float* opacities, const float* scales,
@@ -1141,16 +1147,11 @@ int lidargs_wedge_select_enqueue(int P, const float* means3D, const float* color
     if (!means3D || !colors || !opacities || !scales || !rotations || !viewmatrix || !idx_out || !out_means3D || !out_colors || !out_opacities ||
         !out_scales || !out_rotations || !n_valid_dev || !scratch)
         return fail(LIDARGS_ERR_INVALID_ARGUMENT, "wedge_select_enqueue: NULL pointer%s");
-    if (scratch_bytes < lidargs_shell_select_scratch_bytes(P)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "wedge_select_enqueue: scratch too small%s");
-    lg::Carver c(scratch);
-    uint32_t* flags = c.take<uint32_t>((size_t)P);
-    uint32_t* offs = c.take<uint32_t>((size_t)P);
-    uint32_t* total = c.take<uint32_t>(64);
-    uint32_t* scan_scratch = c.take<uint32_t>(lg::scan_scratch_words((size_t)P));
-    lg::launch_wedge_flags(P, means3D, scales, rotations, scale_modifier, viewmatrix, width, col_lo, col_hi, flags, stream);
-    lg::launch_exclusive_scan(flags, offs, (size_t)P, total, scan_scratch, stream);
-    return select_gather_capped(P, means3D, colors, opacities, scales, rotations, capacity, idx_out, out_means3D, out_colors, out_opacities,
-                                out_scales, out_rotations, n_valid_dev, status_host, flags, offs, total, chunk_rows, world, chunk_counts, stream);
+    return select_enqueue(P, means3D, colors, opacities, scales, rotations, capacity, idx_out, out_means3D, out_colors, out_opacities, out_scales,
+                          out_rotations, n_valid_dev, status_host, scratch, scratch_bytes, "wedge_select_enqueue: scratch too small%s", chunk_rows,
+                          world, chunk_counts, stream, [&](uint32_t* flags) {
+                              lg::launch_wedge_flags(P, means3D, scales, rotations, scale_modifier, viewmatrix, width, col_lo, col_hi, flags, stream);
+                          });
 }
 
 namespace {

@@ -8,7 +8,8 @@ only per-pixel planes (and, if the caller wants index-sharded gradients, the she
 cross xGMI:
 
   forward   0. every rank compacts the (replicated) Gaussians of its shell into dense arrays
-               (lidargs_shell_select: one pass over the means, ~P/N rows survive) -- everything below runs on those
+               (lidargs_shell_select_count + _gather, or the enqueue-only / one-launch forms: ~P/N rows survive) -- everything
+               below runs on those
             1. bin them and walk the lists once for transmittance only   -> T_pass_g   [N]
             2. all_gather(T_pass)  (N floats/rank; 0.68 MB at 64x2650) -> T_in_g = prod_{h<g} T_pass_h
             3. composite the shell from T_in_g (the reference's global T < 1e-4 early-out is applied to the
@@ -28,10 +29,12 @@ cross xGMI:
                "all_reduce"            every rank ends with all rows (dense all-reduce)
                "none"                  every rank keeps only its own shell's rows
 
-The per-rank compute is behind a small backend protocol (select / forward / transmittance / render / compose /
-backward) so the collective logic above can be exercised on CPU with gloo (tests inject a CPU backend); the product
-backend is HipShellBackend (C ABI: lidargs_shell_select / lidargs_forward_shell / lidargs_render_shell /
-lidargs_shell_compose / lidargs_backward_shell).
+The per-rank compute is behind a backend protocol so the collective logic above can be exercised on CPU with gloo (tests
+inject a CPU backend): select / forward / transmittance / render / compose / backward for the shells, select_wedge /
+forward_wedge / backward_plain / pack_columns / unpack_columns for the column wedges below, and the row helpers of the
+gradient exchange both share (scatter_radii, chunk_counts, pack_rows, unpack_rows, unpack_rows_add, unpack_rows_chunk, and
+the live-row pair count_rows_live / pack_rows_live).  The product backend is HipShellBackend (C ABI: lidargs_{shell,wedge}_select_*,
+lidargs_forward_{shell,wedge}, lidargs_render_shell, lidargs_shell_compose, lidargs_backward_{shell,wedge}, ...).
 """
 import contextlib
 import ctypes as C
@@ -234,100 +237,69 @@ class HipShellBackend:
         rows, world, out = chunks
         return C.c_int(int(rows)), C.c_int(int(world)), C.c_void_p(out.data_ptr())
 
-    def _select_enqueue(self, inp, plan, call, chunks=None):
-        """Enqueue-only selection into plan.rows rows (no host read): (idx [cap], capacity-row inputs + the device row count)."""
-        _C = self._C
-        m3 = inp["means3D"]
-        _C._require_device(m3, "means3D")
-        dev, P, cap = m3.device, int(m3.shape[0]), int(plan.rows)
-        key = (dev, P)
-        scr = self._scratch.get(key)
-        if scr is None:
-            nb = int(self.lib.lidargs_shell_select_scratch_bytes(C.c_int(P)))
-            scr = (torch.empty(nb, dtype=torch.uint8, device=dev), nb)
-            self._scratch = {key: scr}
-        f = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
-        idx = torch.empty(cap, dtype=torch.int32, device=dev)
-        sel = dict(inp)
-        sel.update(means3D=f(cap, 3), colors=f(cap, 2), opacities=f(cap, 1), scales=f(cap, 3), rotations=f(cap, 4),
-                   n_valid=torch.empty(2, dtype=torch.int32, device=dev))
-        p = _C._ptr
-        with self._on(dev):
-            rc = call(p, C.c_int(P), C.c_int(cap), p(idx), p(sel["means3D"]), p(sel["colors"]), p(sel["opacities"]), p(sel["scales"]),
-                      p(sel["rotations"]), p(sel["n_valid"]), C.c_void_p(plan.status.data_ptr() + 64), p(scr[0]), C.c_size_t(scr[1]),
-                      *self._chunk_args(chunks), self._st(dev))
-        if rc < 0:
-            _C._raise(rc, "select (enqueue-only)")
-        return idx, sel
-
-    def _select_sync(self, inp, call, chunks, what):
-        """An ordinary frame's selection in one launch (round 6): P-row arrays per call (the caching allocator hands them out without a
-        device malloc; only the first M rows are written and kept as views), one host read for M."""
-        _C = self._C
-        m3 = inp["means3D"]
-        dev, P = m3.device, int(m3.shape[0])
-        key = (dev, P)
-        scr = self._scratch.get(key)
-        if scr is None:
-            nb = int(self.lib.lidargs_shell_select_scratch_bytes(C.c_int(P)))
-            scr = (torch.empty(nb, dtype=torch.uint8, device=dev), nb)
-            self._scratch = {key: scr}
-        f = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
-        idx = torch.empty(P, dtype=torch.int32, device=dev)
-        rows = dict(means3D=f(P, 3), colors=f(P, 2), opacities=f(P, 1), scales=f(P, 3), rotations=f(P, 4))
-        n_valid = torch.empty(2, dtype=torch.int32, device=dev)
-        p = _C._ptr
-        with self._on(dev):
-            M = call(p, C.c_int(P), C.c_int(P), p(idx), p(rows["means3D"]), p(rows["colors"]), p(rows["opacities"]), p(rows["scales"]), p(rows["rotations"]),
-                     p(n_valid), p(scr[0]), C.c_size_t(scr[1]), *self._chunk_args(chunks), self._st(dev))
-        if M < 0:
-            _C._raise(M, what)
-        sel = dict(inp)
-        sel.update({k: v[:M] for k, v in rows.items()})
-        return idx[:M], sel
-
     def select(self, inp, lo, hi, plan=None, chunks=None):
-        """Step 0: dense copies of the Gaussians with range in [lo, hi) + their indices (ascending).
+        """Step 0: dense copies of the Gaussians with range in [lo, hi) + their indices (ascending); see _select."""
+        test = (self._C._ptr(inp["viewmatrix"]), C.c_float(lo), C.c_float(hi))
+        return self._select("shell", ("means3D",), test, inp, plan, chunks)
+
+    def select_wedge(self, inp, c0, c1, plan=None, chunks=None):
+        """Dense copies of the Gaussians whose rect can reach pixel columns [c0, c1) + their indices (ascending); see _select."""
+        test = (C.c_float(inp["scale_modifier"]), self._C._ptr(inp["viewmatrix"]), C.c_int(inp["W"]), C.c_int(c0), C.c_int(c1))
+        return self._select("wedge", ("means3D", "scales", "rotations"), test, inp, plan, chunks)
+
+    def _select(self, cut, count_keys, test, inp, plan, chunks):
+        """The selection of either cut.  `test`: the cut's test arguments, as lidargs_<cut>_select_enqueue / _sync take them behind the five
+        input rows; lidargs_<cut>_select_count takes the inputs `count_keys` in front of them.
 
         The M-row tensors are allocated PER CALL (caching allocator: no device malloc in steady state): a forward's selection
         is saved for its backward, and a second forward before that backward (several views per step, gradient accumulation,
-        an eval render) must not overwrite it.  Only the flags/offsets scratch, dead when this returns, is persistent."""
-        _C, lib = self._C, self.lib
+        an eval render) must not overwrite it.  Only the flags/offsets scratch, dead when this returns, is persistent.
+          plan (enqueue-only frames): plan.rows capacity rows, no host read -- the row count stays on the device (sel["n_valid"]);
+          _SELECT_FUSED (round 6): one launch into P-row arrays (only the first M rows are written and kept as views), one host read for M;
+          otherwise count (one host read for M), then the gather into M rows."""
+        _C, lib, p = self._C, self.lib, self._C._ptr
         m3 = inp["means3D"]
-        if plan is not None and int(m3.shape[0]):
-            return self._select_enqueue(inp, plan, lambda p, cP, ccap, *rest: lib.lidargs_shell_select_enqueue(
-                cP, p(m3), p(inp["colors"]), p(inp["opacities"]), p(inp["scales"]), p(inp["rotations"]), p(inp["viewmatrix"]),
-                C.c_float(lo), C.c_float(hi), ccap, *rest), chunks)
         _C._require_device(m3, "means3D")
         dev, P = m3.device, int(m3.shape[0])
-        if _SELECT_FUSED and P:
-            return self._select_sync(inp, lambda p, cP, *rest: lib.lidargs_shell_select_sync(
-                cP, p(m3), p(inp["colors"]), p(inp["opacities"]), p(inp["scales"]), p(inp["rotations"]), p(inp["viewmatrix"]),
-                C.c_float(lo), C.c_float(hi), *rest), chunks, "lidargs_shell_select_sync")
         key = (dev, P)
         scr = self._scratch.get(key)
         if scr is None:
             nb = int(lib.lidargs_shell_select_scratch_bytes(C.c_int(P)))
             scr = (torch.empty(nb, dtype=torch.uint8, device=dev), nb)
             self._scratch = {key: scr}
-        p = _C._ptr
+        f = lambda n: dict((k, torch.empty((n, w), dtype=torch.float32, device=dev)) for k, w in zip(ROW_KEYS, (3, 2, 1, 3, 4)))   # n rows of each input
+        if P and (plan is not None or _SELECT_FUSED):
+            cap = int(plan.rows) if plan is not None else P
+            name = f"lidargs_{cut}_select_enqueue" if plan is not None else f"lidargs_{cut}_select_sync"
+            status = (C.c_void_p(plan.status.data_ptr() + 64),) if plan is not None else ()
+            idx = torch.empty(cap, dtype=torch.int32, device=dev)
+            rows = f(cap)
+            n_valid = torch.empty(2, dtype=torch.int32, device=dev)
+            with self._on(dev):
+                M = getattr(lib, name)(C.c_int(P), *(p(inp[k]) for k in ROW_KEYS), *test, C.c_int(cap), p(idx), *(p(rows[k]) for k in ROW_KEYS),
+                                       p(n_valid), *status, p(scr[0]), C.c_size_t(scr[1]), *self._chunk_args(chunks), self._st(dev))
+            if M < 0:
+                _C._raise(M, name)
+            sel = dict(inp)
+            if plan is not None:
+                sel.update(rows, n_valid=n_valid)
+                return idx, sel
+            sel.update({k: v[:M] for k, v in rows.items()})
+            return idx[:M], sel
         M = 0
         if P:
+            name = f"lidargs_{cut}_select_count"
             with self._on(dev):
-                M = lib.lidargs_shell_select_count(C.c_int(P), p(m3), p(inp["viewmatrix"]), C.c_float(lo), C.c_float(hi), p(scr[0]),
-                                                   C.c_size_t(scr[1]), self._st(dev))
+                M = getattr(lib, name)(C.c_int(P), *(p(inp[k]) for k in count_keys), *test, p(scr[0]), C.c_size_t(scr[1]), self._st(dev))
             if M < 0:
-                _C._raise(M, "lidargs_shell_select_count")
-        f = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
+                _C._raise(M, name)
         idx = torch.empty(M, dtype=torch.int32, device=dev)
         sel = dict(inp)
-        sel.update(means3D=f(M, 3), colors=f(M, 2), opacities=f(M, 1), scales=f(M, 3), rotations=f(M, 4))
+        sel.update(f(M))
         if M:
             with self._on(dev):
-                rc = lib.lidargs_shell_select_gather(C.c_int(P), p(m3), p(inp["colors"]), p(inp["opacities"]), p(inp["scales"]),
-                                                     p(inp["rotations"]), p(idx), p(sel["means3D"]), p(sel["colors"]), p(sel["opacities"]),
-                                                     p(sel["scales"]), p(sel["rotations"]), p(scr[0]), C.c_size_t(scr[1]),
-                                                     *self._chunk_args(chunks), self._st(dev))
+                rc = lib.lidargs_shell_select_gather(C.c_int(P), *(p(inp[k]) for k in ROW_KEYS), p(idx), *(p(sel[k]) for k in ROW_KEYS),
+                                                     p(scr[0]), C.c_size_t(scr[1]), *self._chunk_args(chunks), self._st(dev))
             if rc < 0:
                 _C._raise(rc, "lidargs_shell_select_gather")
         elif chunks is not None:
@@ -335,38 +307,63 @@ class HipShellBackend:
         return idx, sel
 
     def forward(self, inp, lo, hi, plan=None, T_pass=None):
-        _C, lib = self._C, self.lib
-        m3 = inp["means3D"]
-        dev, P, H, W = m3.device, int(m3.shape[0]), inp["H"], inp["W"]
+        """Step 1: bin the shell's rows and walk its lists for transmittance only -> (state for steps 3 and 5, T_pass [N])."""
+        st = self._state(inp)
+        dev, N = st["radii"].device, inp["H"] * inp["W"]
+        if T_pass is None:
+            T_pass = torch.empty(N, dtype=torch.float32, device=dev)
+        if not st["P"]:
+            T_pass.fill_(1.0)                                              # (with rows, the library writes every pixel)
+        dummy = torch.empty(4 * N, dtype=torch.float32, device=dev)
+        p = self._C._ptr
+        self._forward(st, "lidargs_forward_shell", None, plan, C.c_float(lo), C.c_float(hi), None, C.c_int(1), p(dummy), p(dummy[2 * N:]),
+                      p(dummy[3 * N:]), p(T_pass))
+        return st, T_pass
+
+    def _state(self, inp):
+        """A forward's state, kept for its backward: the inputs, the library's three scratch buffers, the radii."""
+        _C = self._C
+        dev, P = inp["means3D"].device, int(inp["means3D"].shape[0])
         st = dict(inp=inp, P=P, geom=_C._Scratch(dev), binning=_C._Scratch(dev), img=_C._Scratch(dev))
         st["radii"] = torch.empty(P, dtype=torch.int32, device=dev)          # the library writes every row
         st["radii_xy"] = torch.empty(2 * P, dtype=torch.int32, device=dev)
-        if T_pass is None:
-            T_pass = torch.empty(H * W, dtype=torch.float32, device=dev)
-        if not P:
-            T_pass.fill_(1.0)                                              # (with rows, the library writes every pixel)
-        dummy = torch.empty(4 * H * W, dtype=torch.float32, device=dev)
-        n = 0
-        if P:
-            p = _C._ptr
-            common = (_C._alloc_cb, st["geom"].user, _C._alloc_cb, st["binning"].user, _C._alloc_cb, st["img"].user, C.c_int(P), None,
-                      C.c_int(W), C.c_int(H),
-                      p(m3), p(inp["colors"]), p(inp["opacities"]), p(inp["scales"]), C.c_float(inp["scale_modifier"]),
-                      p(inp["rotations"]), None, p(inp["viewmatrix"]), p(inp["beams"]), C.c_int(inp["far"]), C.c_int(inp["near"]),
-                      C.c_float(lo), C.c_float(hi), None, C.c_int(1), p(dummy), p(dummy[2 * H * W:]), p(dummy[3 * H * W:]), p(T_pass),
-                      p(st["radii"]), p(st["radii_xy"]), C.c_int(0))
+        return st
+
+    def _forward(self, st, name, bg, plan, *cut_args):
+        """lidargs_forward_<cut> on the state's rows (nothing to launch without rows); `cut_args` = the cut's own arguments between the
+        near plane and the radii.  With a plan, the enqueue-only form: nothing is read back, capacities from the plan, the row count
+        stays on the device."""
+        _C, inp, n = self._C, st["inp"], 0
+        if st["P"]:
+            dev, p = inp["means3D"].device, _C._ptr
+            args = (_C._alloc_cb, st["geom"].user, _C._alloc_cb, st["binning"].user, _C._alloc_cb, st["img"].user, C.c_int(st["P"]), bg,
+                    C.c_int(inp["W"]), C.c_int(inp["H"]), p(inp["means3D"]), p(inp["colors"]), p(inp["opacities"]), p(inp["scales"]),
+                    C.c_float(inp["scale_modifier"]), p(inp["rotations"]), None, p(inp["viewmatrix"]), p(inp["beams"]), C.c_int(inp["far"]),
+                    C.c_int(inp["near"]), *cut_args, p(st["radii"]), p(st["radii_xy"]), C.c_int(0))
             with self._on(dev):
                 if plan is None:
-                    n = lib.lidargs_forward_shell(*common, self._st(dev))
-                else:       # nothing is read back: capacities from the plan, the row count stays on the device
-                    n = lib.lidargs_forward_shell_enqueue(*common, p(inp.get("n_valid")), C.c_int(plan.instances), C.c_int(plan.tile_rows),
-                                                          C.c_void_p(plan.status.data_ptr()), self._st(dev))
+                    n = getattr(self.lib, name)(*args, self._st(dev))
+                else:
+                    n = getattr(self.lib, name + "_enqueue")(*args, p(inp.get("n_valid")), C.c_int(plan.instances), C.c_int(plan.tile_rows),
+                                                             C.c_void_p(plan.status.data_ptr()), self._st(dev))
             if n < 0:
-                _C._raise(n, "lidargs_forward_shell")
+                _C._raise(n, name)
         for k in ("geom", "binning", "img"):       # keep only the tensors: nothing holds the registry entries alive
             st[k] = st[k].take()
         st["R"] = n
-        return st, T_pass
+
+    def _backward_setup(self, st, dev):
+        """The six gradients (GRAD_WIDTHS' keys) and dL/dcov3D, [P, w] views of one allocation (the library writes every row), and the
+        arguments every backward entry point starts with."""
+        inp, P, p = st["inp"], st["P"], self._C._ptr
+        slab = torch.empty(P * (GRAD_COLS + 6), dtype=torch.float32, device=dev)
+        g, o = {}, 0
+        for k, w in GRAD_WIDTHS + (("cov3D", 6),):
+            g[k] = slab[o:o + P * w].view(P, w); o += P * w
+        args = (C.c_int(P), C.c_int(st["R"]), p(inp["bg"]), C.c_int(inp["W"]), C.c_int(inp["H"]), p(inp["means3D"]), p(inp["colors"]),
+                p(inp["scales"]), C.c_float(inp["scale_modifier"]), p(inp["rotations"]), None, p(inp["viewmatrix"]), p(inp["beams"]),
+                p(st["radii"]), p(st["geom"]), p(st["binning"]), p(st["img"]))
+        return g, g.pop("cov3D"), args
 
     def transmittance(self, allT, rank):
         """Step 2: T_in = product of the hand-over transmittances of the shells in front.  allT: [G, N]."""
@@ -419,137 +416,41 @@ class HipShellBackend:
         return color.view(2, H, W), depth.view(1, H, W), occ.view(1, H, W), T_final, behind.view(3, N)
 
     def backward(self, st, behind, T_final, grads):
-        _C, lib = self._C, self.lib
-        inp = st["inp"]
-        P, H, W = st["P"], inp["H"], inp["W"]
-        dev = behind.device
-        widths = (3, 4, 2, 1, 3, 4, 6)                             # the six returned gradients + dL/dcov3D
-        slab = torch.empty(P * sum(widths), dtype=torch.float32, device=dev)      # the library writes every row
-        parts, o = [], 0
-        for w in widths:
-            parts.append(slab[o:o + P * w].view(P, w)); o += P * w
-        (g_m3, g_m2, g_col, g_op, g_sc, g_rot, g_cov) = parts
-        g_con = g_dep = g_sph = g_u1 = g_u2 = None                 # the reference's scratch gradients: not materialised
-        if P:
-            p = _C._ptr
-            gc, gd, go = (g.contiguous() for g in grads)
-            with self._on(dev):
-                rc = lib.lidargs_backward_shell(
-                    C.c_int(P), C.c_int(st["R"]), p(inp["bg"]), C.c_int(W), C.c_int(H), p(inp["means3D"]), p(inp["colors"]), p(inp["scales"]),
-                    C.c_float(inp["scale_modifier"]), p(inp["rotations"]), None, p(inp["viewmatrix"]), p(inp["beams"]), p(st["radii"]),
-                    p(st["geom"]), p(st["binning"]), p(st["img"]), p(behind.contiguous()), p(T_final.contiguous()),
-                    p(gc), p(gd), p(go), p(g_m2), p(g_con), p(g_op), p(g_col), p(g_dep), p(g_m3), p(g_sph), p(g_u1), p(g_u2), p(g_cov),
-                    p(g_sc), p(g_rot), C.c_int(0), self._st(dev))
-            if rc < 0:
-                _C._raise(rc, "lidargs_backward_shell")
-        return dict(means3D=g_m3, means2D=g_m2, colors=g_col, opacities=g_op, scales=g_sc, rotations=g_rot)
+        """Step 5: the shell's local back-to-front pass, seeded with the behind-sums -> the six gradients of its rows, [M, w]."""
+        dev, p = behind.device, self._C._ptr
+        g, g_cov, args = self._backward_setup(st, dev)
+        if st["P"]:
+            gc, gd, go = (t.contiguous() for t in grads)
+            self._call("lidargs_backward_shell", dev, *args, p(behind.contiguous()), p(T_final.contiguous()), p(gc), p(gd), p(go), p(g["means2D"]),
+                       None, p(g["opacities"]), p(g["colors"]), None, p(g["means3D"]), None, None, None, p(g_cov), p(g["scales"]),
+                       p(g["rotations"]), C.c_int(0))           # (the Nones: the reference's scratch gradients, not materialised)
+        return g
 
 
     # ---- column wedges -------------------------------------------------------------------------------------------------
-    def select_wedge(self, inp, c0, c1, plan=None, chunks=None):
-        """Dense copies of the Gaussians whose rect can reach pixel columns [c0, c1) + their indices (ascending); M rows per call."""
-        _C, lib = self._C, self.lib
-        m3 = inp["means3D"]
-        if plan is not None and int(m3.shape[0]):
-            return self._select_enqueue(inp, plan, lambda p, cP, ccap, *rest: lib.lidargs_wedge_select_enqueue(
-                cP, p(m3), p(inp["colors"]), p(inp["opacities"]), p(inp["scales"]), p(inp["rotations"]), C.c_float(inp["scale_modifier"]),
-                p(inp["viewmatrix"]), C.c_int(inp["W"]), C.c_int(c0), C.c_int(c1), ccap, *rest), chunks)
-        _C._require_device(m3, "means3D")
-        dev, P = m3.device, int(m3.shape[0])
-        if _SELECT_FUSED and P:
-            return self._select_sync(inp, lambda p, cP, *rest: lib.lidargs_wedge_select_sync(
-                cP, p(m3), p(inp["colors"]), p(inp["opacities"]), p(inp["scales"]), p(inp["rotations"]), C.c_float(inp["scale_modifier"]),
-                p(inp["viewmatrix"]), C.c_int(inp["W"]), C.c_int(c0), C.c_int(c1), *rest), chunks, "lidargs_wedge_select_sync")
-        key = (dev, P)
-        scr = self._scratch.get(key)
-        if scr is None:
-            nb = int(lib.lidargs_shell_select_scratch_bytes(C.c_int(P)))
-            scr = (torch.empty(nb, dtype=torch.uint8, device=dev), nb)
-            self._scratch = {key: scr}
-        p = _C._ptr
-        M = 0
-        if P:
-            with self._on(dev):
-                M = lib.lidargs_wedge_select_count(C.c_int(P), p(m3), p(inp["scales"]), p(inp["rotations"]), C.c_float(inp["scale_modifier"]),
-                                                   p(inp["viewmatrix"]), C.c_int(inp["W"]), C.c_int(c0), C.c_int(c1), p(scr[0]), C.c_size_t(scr[1]),
-                                                   self._st(dev))
-            if M < 0:
-                _C._raise(M, "lidargs_wedge_select_count")
-        f = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
-        idx = torch.empty(M, dtype=torch.int32, device=dev)
-        sel = dict(inp)
-        sel.update(means3D=f(M, 3), colors=f(M, 2), opacities=f(M, 1), scales=f(M, 3), rotations=f(M, 4))
-        if M:
-            with self._on(dev):
-                rc = lib.lidargs_shell_select_gather(C.c_int(P), p(m3), p(inp["colors"]), p(inp["opacities"]), p(inp["scales"]),
-                                                     p(inp["rotations"]), p(idx), p(sel["means3D"]), p(sel["colors"]), p(sel["opacities"]),
-                                                     p(sel["scales"]), p(sel["rotations"]), p(scr[0]), C.c_size_t(scr[1]),
-                                                     *self._chunk_args(chunks), self._st(dev))
-            if rc < 0:
-                _C._raise(rc, "lidargs_shell_select_gather")
-        elif chunks is not None:
-            chunks[2].zero_()
-        return idx, sel
-
     def forward_wedge(self, inp, c0, c1, plan=None):
         """lidargs_forward_wedge on the selected rows -> state for the backward, planes [4, H, W] (colour 0/1, depth, occupancy;
         only columns [c0, c1) are this rank's)."""
-        _C, lib = self._C, self.lib
-        m3 = inp["means3D"]
-        dev, P, H, W = m3.device, int(m3.shape[0]), inp["H"], inp["W"]
-        st = dict(inp=inp, P=P, geom=_C._Scratch(dev), binning=_C._Scratch(dev), img=_C._Scratch(dev))
-        st["radii"] = torch.empty(P, dtype=torch.int32, device=dev)
-        st["radii_xy"] = torch.empty(2 * P, dtype=torch.int32, device=dev)
-        planes = torch.empty(4 * H * W, dtype=torch.float32, device=dev)
-        n = 0
-        if P:
-            p = _C._ptr
-            N = H * W
-            common = (_C._alloc_cb, st["geom"].user, _C._alloc_cb, st["binning"].user, _C._alloc_cb, st["img"].user, C.c_int(P), p(inp["bg"]),
-                      C.c_int(W), C.c_int(H), p(m3), p(inp["colors"]), p(inp["opacities"]), p(inp["scales"]), C.c_float(inp["scale_modifier"]),
-                      p(inp["rotations"]), None, p(inp["viewmatrix"]), p(inp["beams"]), C.c_int(inp["far"]), C.c_int(inp["near"]),
-                      C.c_int(c0), C.c_int(c1), p(planes), p(planes[2 * N:]), p(planes[3 * N:]), p(st["radii"]), p(st["radii_xy"]), C.c_int(0))
-            with self._on(dev):
-                if plan is None:
-                    n = lib.lidargs_forward_wedge(*common, self._st(dev))
-                else:
-                    n = lib.lidargs_forward_wedge_enqueue(*common, p(inp.get("n_valid")), C.c_int(plan.instances), C.c_int(plan.tile_rows),
-                                                          C.c_void_p(plan.status.data_ptr()), self._st(dev))
-            if n < 0:
-                _C._raise(n, "lidargs_forward_wedge")
-        else:       # no Gaussian can reach the wedge: background only
-            pl = planes.view(4, H * W)
+        st = self._state(inp)
+        dev, N = st["radii"].device, inp["H"] * inp["W"]
+        planes = torch.empty(4 * N, dtype=torch.float32, device=dev)
+        p = self._C._ptr
+        self._forward(st, "lidargs_forward_wedge", p(inp["bg"]), plan, C.c_int(c0), C.c_int(c1), p(planes), p(planes[2 * N:]), p(planes[3 * N:]))
+        if not st["P"]:       # no Gaussian can reach the wedge: background only
+            pl = planes.view(4, N)
             pl[0] = inp["bg"][0]; pl[1] = inp["bg"][1]; pl[2] = 0; pl[3] = 0
-        for k in ("geom", "binning", "img"):
-            st[k] = st[k].take()
-        st["R"] = n
         st["cols"] = (c0, c1)
         return st, planes
 
     def backward_plain(self, st, grads):
         """lidargs_backward_wedge on a wedge's forward state; grads = (colour [2,N], depth [N], occ [N]), full-size planes."""
-        _C, lib = self._C, self.lib
-        inp = st["inp"]
-        P, H, W = st["P"], inp["H"], inp["W"]
-        dev = grads[0].device
-        widths = (3, 4, 2, 1, 3, 4, 6)
-        slab = torch.empty(P * sum(widths), dtype=torch.float32, device=dev)
-        parts, o = [], 0
-        for w in widths:
-            parts.append(slab[o:o + P * w].view(P, w)); o += P * w
-        (g_m3, g_m2, g_col, g_op, g_sc, g_rot, g_cov) = parts
-        if P:
-            p = _C._ptr
-            gc, gd, go = (g.contiguous() for g in grads)
-            with self._on(dev):
-                rc = lib.lidargs_backward_wedge(
-                    C.c_int(P), C.c_int(st["R"]), p(inp["bg"]), C.c_int(W), C.c_int(H), p(inp["means3D"]), p(inp["colors"]), p(inp["scales"]),
-                    C.c_float(inp["scale_modifier"]), p(inp["rotations"]), None, p(inp["viewmatrix"]), p(inp["beams"]), p(st["radii"]),
-                    p(st["geom"]), p(st["binning"]), p(st["img"]), C.c_int(st["cols"][0]), C.c_int(st["cols"][1]), p(gc), p(gd), p(go),
-                    p(g_m2), p(g_op), p(g_col), p(g_m3), p(g_cov), p(g_sc), p(g_rot), C.c_int(0), self._st(dev))
-            if rc < 0:
-                _C._raise(rc, "lidargs_backward_wedge")
-        return dict(means3D=g_m3, means2D=g_m2, colors=g_col, opacities=g_op, scales=g_sc, rotations=g_rot)
+        dev, p = grads[0].device, self._C._ptr
+        g, g_cov, args = self._backward_setup(st, dev)
+        if st["P"]:
+            gc, gd, go = (t.contiguous() for t in grads)
+            self._call("lidargs_backward_wedge", dev, *args, C.c_int(st["cols"][0]), C.c_int(st["cols"][1]), p(gc), p(gd), p(go), p(g["means2D"]),
+                       p(g["opacities"]), p(g["colors"]), p(g["means3D"]), p(g_cov), p(g["scales"]), p(g["rotations"]), C.c_int(0))
+        return g
 
     def pack_columns(self, planes, H, W, c0, c1, wmax, out):
         """out f32[4*H*wmax (+ tail)]: this rank's columns of the four planes, zero padded to wmax columns."""
@@ -618,7 +519,8 @@ class HipShellBackend:
                 C.c_int(int(P)), C.c_int(int(chunk_rows)), C.c_int(int(world)))
 
     def count_rows_live(self, g, idx, P, chunk_rows, world):
-        """Rows that carry a gradient, per destination chunk (round 6): float32 [world] ON THE DEVICE, no host read (exact: < 2^24 rows per chunk)."""
+        """Rows that carry a gradient, per destination chunk (round 6): int32 [2 * world] ON THE DEVICE, no host read -- the first world
+        words are the counts, the other world are pack_rows_live's cursor."""
         dev = idx.device
         cnt = torch.empty(2 * world, dtype=torch.int32, device=dev)
         with self._on(dev):
@@ -738,115 +640,95 @@ def _chunk_rows(P, world):
     return (P + world - 1) // world
 
 
-def _shell_forward(module, means3D, colors, opacities, scales, rotations):
-    """Steps 0-4 of the module docstring.  Returns ((color, depth, occ, radii), saved-for-backward)."""
-    rs, comm, be = module.raster_settings, module.comm, module.backend
-    H, W = int(rs.image_height), int(rs.image_width)
-    N = H * W
-    dev = means3D.device
-    P = int(means3D.shape[0])
-    f32 = lambda t: t.detach() if (t.dtype == torch.float32 and t.is_contiguous()) else t.detach().to(torch.float32).contiguous()
-    inp = dict(means3D=f32(means3D), colors=f32(colors), opacities=f32(opacities), scales=f32(scales), rotations=f32(rotations),
-               viewmatrix=f32(rs.viewmatrix), beams=f32(rs.beam_inclinations), H=H, W=W, scale_modifier=float(rs.scale_modifier),
-               far=int(rs.lidar_far), near=int(rs.lidar_near), bg=rs.bg.to(torch.float32).to(dev).contiguous())
-    edges = module.edges
-    if edges is None:
-        edges = shell_edges(inp["means3D"], inp["viewmatrix"], comm.world, rs.lidar_near, rs.lidar_far)
-        edges = comm.broadcast(edges, 0)       # every rank must cut at the same ranges
-    if not isinstance(edges, (list, tuple)):
-        edges = [float(e) for e in edges.tolist()]
-        if module.edges is not None:
-            module.edges = edges               # static cut: convert once, no device read per frame
-    lo, hi = edges[comm.rank], edges[comm.rank + 1]
+def shard_rows(P, world, rank):
+    """(first row, number of rows) of rank's index chunk: the rows whose gradients it receives under grad_sync "reduce_scatter" / "shard"."""
+    rows = _chunk_rows(P, world)
+    lo = min(P, rank * rows)
+    return lo, min(P, lo + rows) - lo
 
-    exchange = comm.world > 1 and module.grad_sync in ("reduce_scatter", "shard")
-    fused = getattr(be, "fused_chunk_counts", False)                              # (the HIP backend; the framework-op backend of the CPU tests is not)
-    enqueue_only = module.enqueue_only and fused
-    plan = module.plan.next() if enqueue_only else None                           # None: an ordinary frame (two host reads)
-    tail = ship = None
-    if exchange:
-        # split sizes of the gradient all-to-all: the selection is index-sorted, so the rows bound for index chunk d are
-        # contiguous.  They ride on the T_pass all-gather (exact as floats: < 2^24 rows per chunk) instead of a collective
-        # of their own, and are read back at the end of the forward, off the backward's critical path.
-        rows = _chunk_rows(P, comm.world)
-        assert rows < (1 << 24)
-        ship = torch.empty(N + comm.world, dtype=torch.float32, device=dev)      # what the all-gather ships: T_pass, then the split sizes
-        tail = ship[N:]
-    if fused:       # (the selection's own gather launch leaves the split sizes in `tail`, the forward writes T_pass in place)
-        idx, sel = be.select(inp, lo, hi, plan, chunks=(rows, comm.world, tail) if exchange else None)   # 0   [M], M-row inputs
+
+# ---- one rank's frame, either cut ------------------------------------------------------------------------------------
+def _frame_of(be, dev):
+    f = getattr(be, "frame", None)
+    return f(dev) if f is not None else _NULL_CTX
+
+
+def _rank_inputs(module, means3D, colors, opacities, scales, rotations):
+    """The rank's inputs as float32 contiguous tensors (detached: the autograd Function hands the gradients back), with the settings the
+    backend reads."""
+    rs = module.raster_settings
+    f32 = lambda t: t.detach() if (t.dtype == torch.float32 and t.is_contiguous()) else t.detach().to(torch.float32).contiguous()
+    return dict(means3D=f32(means3D), colors=f32(colors), opacities=f32(opacities), scales=f32(scales), rotations=f32(rotations),
+                viewmatrix=f32(rs.viewmatrix), beams=f32(rs.beam_inclinations), H=int(rs.image_height), W=int(rs.image_width),
+                scale_modifier=float(rs.scale_modifier), far=int(rs.lidar_far), near=int(rs.lidar_near),
+                bg=rs.bg.to(torch.float32).to(means3D.device).contiguous())
+
+
+def _exchanges(module):
+    """The gradient rows go to their index-chunk owners in one variable-split all-to-all (grad_sync "reduce_scatter" / "shard")."""
+    return module.comm.world > 1 and module.grad_sync in ("reduce_scatter", "shard")
+
+
+def _fused(be):
+    """The backend's selection takes a plan and leaves the all-to-all's split sizes itself, and its forward takes a plan (the HIP backend;
+    the framework-op backend of the CPU tests does neither: its frames are never enqueue-only)."""
+    return getattr(be, "fused_chunk_counts", False)
+
+
+def _enqueue_only(module):
+    return module.enqueue_only and _fused(module.backend)
+
+
+def _open_frame(module, inp, head, select, *part):
+    """The start of a rank's frame once its part of the frame is known (`part`: what `select` takes after the inputs): (plan, ship, idx, sel).
+    `plan` is None for an ordinary frame (two host reads), which teaches an enqueue-only module its plan.  `ship` is what the frame's
+    image all-gather ships: `head` floats of the cut's own, then, when the gradients are exchanged, the split sizes of the all-to-all.
+    `idx, sel` is step 0: the rank's rows, [M] and M-row inputs.  The selection is index-sorted, so the rows bound for index chunk d are
+    contiguous; they are counted into the tail, where they ride on the all-gather (exact as floats: < 2^24 rows per chunk) instead of a
+    collective of their own, and are read back at the end of the forward, off the backward's critical path."""
+    comm, be = module.comm, module.backend
+    P = int(inp["means3D"].shape[0])
+    plan = module.plan.next() if _enqueue_only(module) else None
+    chunks, tail = None, comm.world if _exchanges(module) else 0
+    ship = torch.empty(head + tail, dtype=torch.float32, device=inp["means3D"].device)
+    if tail:
+        chunks = (_chunk_rows(P, comm.world), comm.world, ship[head:])
+        assert chunks[0] < (1 << 24)
+    if _fused(be):      # (the selection's own gather launch counts them)
+        idx, sel = select(inp, *part, plan, chunks=chunks)
     else:
-        idx, sel = be.select(inp, lo, hi)
-        if exchange:
-            be.chunk_counts(idx, rows, comm.world, tail)
-    # `sel` already holds exactly this shell's rows: the shell test is NOT repeated inside the forward (two kernels need not
-    # round the same range expression identically; a Gaussian one ulp from an edge could be selected here and culled there)
-    if fused:
-        st, T_pass = be.forward(sel, float("-inf"), float("inf"), plan, T_pass=None if ship is None else ship[:N])   # 1
-    else:
-        st, T_pass = be.forward(sel, float("-inf"), float("inf"))
-        if exchange:
-            ship[:N] = T_pass
-    radii = be.scatter_radii(idx, st["radii"], P)
-    wait_radii = comm.all_reduce_async(radii) if comm.world > 1 else (lambda: None)   # overlaps the rendering
-    allT = comm.all_gather(T_pass if ship is None else ship)                       # 2   [G, N (+G)]
-    counts = allT[:, N:] if exchange else None
-    T_in = be.transmittance(allT[:, :N] if exchange else allT, comm.rank)
-    planes = comm.all_gather(be.render(st, T_in))                                 # 3, 4   [G, 5, N]
-    color, depth, occ, T_final, behind = be.compose(planes, comm.rank, inp["bg"], H, W)
-    saved = dict(st=st, behind=behind, T_final=T_final, idx=idx, P=P)
-    if exchange:
-        saved.update(counts=_HostCounts(counts))                                  # [src, dst], read in the backward
-    if enqueue_only:
+        idx, sel = select(inp, *part)
+        if chunks is not None:
+            be.chunk_counts(idx, *chunks)
+    return plan, ship, idx, sel
+
+
+def _scatter_radii(module, idx, st, P, reduce_async):
+    """radii i32[P] at their global rows; `reduce_async` (the cut's: sum or max) starts the all-reduce, which overlaps the rendering."""
+    radii = module.backend.scatter_radii(idx, st["radii"], P)
+    return radii, (reduce_async(radii) if module.comm.world > 1 else (lambda: None))
+
+
+def _close_frame(module, plan, saved, gathered, head, wait_radii):
+    """The end of a rank's frame: the split sizes off the gathered tail ([src, dst], read in the backward), the plan learns from an
+    ordinary frame or records an enqueue-only one, the radii all-reduce is waited for.  Returns `saved`."""
+    if _exchanges(module):
+        saved.update(counts=_HostCounts(gathered[:, head:]))
+    if _enqueue_only(module):
         if plan is None:
-            module.plan.learn(int(idx.shape[0]), st["R"])
+            module.plan.learn(int(saved["idx"].shape[0]), saved["st"]["R"])
         else:
             module.plan.submitted()
     wait_radii()
-    return (color, depth, occ, radii), saved
+    return saved
 
 
-def _shell_backward(module, saved, g_color, g_depth, g_occ):
-    """Steps 5-6.  Returns {means3D, means2D, colors, opacities, scales, rotations} gradients, dense [P, w]."""
-    st, idx, P = saved["st"], saved["idx"], saved["P"]
-    comm, be = module.comm, module.backend
-    inp = st["inp"]
-    H, W = inp["H"], inp["W"]
-    dev = g_color.device
-    # d(color)/d(T_final) for the background is inside the blend: (-T_final/(1-alpha)) * bg.g  (R3/cr/backward.cu:727)
-    g = be.backward(st, saved["behind"], saved["T_final"], (g_color.reshape(2, H * W), g_depth.reshape(H * W), g_occ.reshape(H * W)))
-    sync = module.grad_sync if comm.world > 1 else "none"
-    blocked = sync != "reduce_scatter_dense"
-    if module.grad_sync == "shard":
-        return _shard_grads(module, saved, g, idx, P, add=False)
-    if sync == "reduce_scatter":
-        # 6: the shell's rows go straight to their index-chunk owners; the row index travels as an 18th column (bit pattern)
-        got = _exchange_rows(module, saved, g, idx, P)                  # (every sync mode: a frame over its capacities raises in its own backward, plan.check())
-        dense = be.unpack_rows(got, P, blocked=True)
-    else:
-        packed = be.pack_rows(g, idx)                                                 # [M, 18]: gradients + the row's global index
-        module.plan.check()
-        dense = be.unpack_rows(packed, P, blocked=blocked)
-        if sync == "all_reduce":
-            dense = comm.all_reduce(dense)
-        elif sync == "reduce_scatter_dense":
-            rows = _chunk_rows(P, comm.world)
-            pad = rows * comm.world - P
-            if pad:
-                dense = torch.cat([dense, dense.new_zeros(pad, GRAD_COLS)], 0)
-            mine = comm.reduce_scatter_rows(dense)
-            dense = dense.new_zeros(rows * comm.world, GRAD_COLS)
-            dense[comm.rank * rows:(comm.rank + 1) * rows] = mine
-            dense = dense[:P]
-    o, out = 0, {}
-    for k, w in GRAD_WIDTHS:
-        if blocked:
-            out[k] = dense[o * P:(o + w) * P].view(P, w)
-        else:
-            out[k] = dense[:, o:o + w]
-        o += w
-    return out
+def _pixel_grads(saved, g_color, g_depth, g_occ):
+    N = saved["st"]["inp"]["H"] * saved["st"]["inp"]["W"]
+    return g_color.reshape(2, N), g_depth.reshape(N), g_occ.reshape(N)
 
 
+# ---- step 6, either cut --------------------------------------------------------------------------------------------
 SHIP_LIVE_BYTES = 32 << 20      # "auto": live rows only when a rank's share of the full exchange (72 B x P / world) is at least this
 
 
@@ -858,19 +740,20 @@ def _ship_live_default():
 def _ships_live(module, P):
     """The same answer on every rank (it depends on P and the world size only: the live form has a collective of its own).  Shipping only the
     live rows costs one host read in the backward and a 4 x world-byte all-gather; it pays when the full exchange is large: 8 M Gaussians over
-    8 ranks ship 84 MB per rank otherwise (0.1 MB live), 2 M ship 18 MB (0.6 MB live) -- there the read costs what the bytes save."""
+    8 ranks ship 84 MB per rank otherwise (0.1 MB live), 2 M ship 18 MB (0.6 MB live) -- there the read costs what the bytes save.  An empty
+    model has no index chunks to count rows into: it ships every (no) row."""
     live = getattr(module, "ship_live", False)
     if live == "auto":
         live = 72 * P // max(1, module.comm.world) >= SHIP_LIVE_BYTES
-    return bool(live) and not module.enqueue_only and hasattr(module.backend, "pack_rows_live")
+    return P > 0 and bool(live) and not module.enqueue_only and hasattr(module.backend, "pack_rows_live")
 
 
-def _exchange_rows(module, saved, g, idx, P):
+def _exchange_rows(module, saved, g):
     """The rows this rank receives for its index chunk: [n, 18] (17 gradient columns + the bit pattern of the row's global index).
     Round 6 (module.ship_live; "auto" = for large exchanges, _ships_live): only the rows that carry a gradient travel -- each rank counts them per destination, the counts
     cross in one small all-gather, then the variable-split all-to-all ships exactly those (cfg4, world 8: 84 MB per rank and frame -> 0.1 MB;
     cfg3: a fifth).  Otherwise (enqueue-only frames: no host read): every selected row, split sizes from the forward's selection."""
-    comm, be = module.comm, module.backend
+    comm, be, idx, P = module.comm, module.backend, saved["idx"], saved["P"]
     if _ships_live(module, P):
         chunk = _chunk_rows(P, comm.world)
         cnt = be.count_rows_live(g, idx, P, chunk, comm.world)          # on the device
@@ -885,125 +768,93 @@ def _exchange_rows(module, saved, g, idx, P):
     return comm.all_to_all_rows(packed[:sum(send)], send, recv)
 
 
-def shard_rows(P, world, rank):
-    """(first row, number of rows) of rank's index chunk: the rows whose gradients it receives under grad_sync "reduce_scatter" / "shard"."""
-    rows = _chunk_rows(P, world)
-    lo = min(P, rank * rows)
-    return lo, min(P, lo + rows) - lo
-
-
-def _shard_grads(module, saved, g, idx, P, add):
-    """grad_sync = "shard" (round 6): the rank's own chunk of every gradient, [rows_r, w] each -- what a rank that optimises only its shard
-    of the (replicated) Gaussians needs.  The rows travel as under "reduce_scatter" (one variable-split all-to-all); they are unpacked into
-    a [17, rows_r] block instead of a zero-filled dense [P, 17] one."""
-    comm, be = module.comm, module.backend
-    base, n = shard_rows(P, comm.world, comm.rank)
-    if comm.world > 1:
-        got = _exchange_rows(module, saved, g, idx, P)
+def _sync_grads(module, saved, g, add):
+    """The rank's gradient rows g [M, w] -> {means3D, means2D, colors, opacities, scales, rotations} as `grad_sync` asks:
+       "reduce_scatter"        rank r's index chunk (one all-to-all, _exchange_rows), zeros elsewhere, dense [P, w]
+       "shard"                 the same rows, [rows_r, w] only (what a rank that optimises only its shard of the Gaussians needs)
+       "reduce_scatter_dense"  rank r's index chunk through RCCL reduce_scatter on the dense [P, 17] tensor (shells)
+       "all_reduce"            every row on every rank; "none" (and any mode at world 1): the rank's own rows
+    `add`: rows of equal index are added on arrival (wedges: a Gaussian straddling a boundary has partial rows on both sides)
+    instead of written (shells: a Gaussian is in exactly one shell)."""
+    comm, be, idx, P = module.comm, module.backend, saved["idx"], saved["P"]
+    sync = module.grad_sync if comm.world > 1 else "none"
+    if _exchanges(module):
+        rows = _exchange_rows(module, saved, g)
     else:
-        got = be.pack_rows(g, idx)
-        module.plan.check()
-    dense = be.unpack_rows_chunk(got, base, n, add=add)
+        rows = be.pack_rows(g, idx)                                   # [M, 18]: gradients + the row's global index
+        module.plan.check()                        # (every sync mode: a frame over its capacities raises in its own backward)
+    if module.grad_sync == "shard":
+        base, n = shard_rows(P, comm.world, comm.rank)
+        return _split_grads(be.unpack_rows_chunk(rows, base, n, add=add), n)
+    if sync == "reduce_scatter_dense":
+        dense = be.unpack_rows(rows, P)
+        chunk = _chunk_rows(P, comm.world)
+        pad = chunk * comm.world - P
+        if pad:
+            dense = torch.cat([dense, dense.new_zeros(pad, GRAD_COLS)], 0)
+        mine = comm.reduce_scatter_rows(dense)
+        dense = dense.new_zeros(chunk * comm.world, GRAD_COLS)
+        dense[comm.rank * chunk:(comm.rank + 1) * chunk] = mine
+        return _split_grads(dense[:P], P, blocked=False)
+    dense = be.unpack_rows_add(rows, P) if add else be.unpack_rows(rows, P, blocked=True)
+    if sync == "all_reduce":
+        dense = comm.all_reduce(dense)
+    return _split_grads(dense, P)
+
+
+def _split_grads(dense, n, blocked=True):
+    """The six named gradients [n, w] of a dense block: flat [17 n] holding them as six contiguous blocks, or (not blocked) [n, 17]."""
     o, out = 0, {}
     for k, w in GRAD_WIDTHS:
-        out[k] = dense[o * n:(o + w) * n].view(n, w)
+        out[k] = dense[o * n:(o + w) * n].view(n, w) if blocked else dense[:, o:o + w]
         o += w
     return out
 
 
-def _frame_of(be, dev):
-    f = getattr(be, "frame", None)
-    return f(dev) if f is not None else _NULL_CTX
+# ---- range shells --------------------------------------------------------------------------------------------------
+def _shell_range(module, inp):
+    comm, edges = module.comm, module.edges
+    if edges is None:
+        edges = shell_edges(inp["means3D"], inp["viewmatrix"], comm.world, module.raster_settings.lidar_near, module.raster_settings.lidar_far)
+        edges = comm.broadcast(edges, 0)       # every rank must cut at the same ranges
+    if not isinstance(edges, (list, tuple)):
+        edges = [float(e) for e in edges.tolist()]
+        if module.edges is not None:
+            module.edges = edges               # static cut: convert once, no device read per frame
+    return edges[comm.rank], edges[comm.rank + 1]
 
 
 def shell_forward(module, means3D, colors, opacities, scales, rotations):
-    with _frame_of(module.backend, means3D.device):
-        return _shell_forward(module, means3D, colors, opacities, scales, rotations)
+    """Steps 0-4 of the module docstring.  Returns ((color, depth, occ, radii), saved-for-backward)."""
+    comm, be, P = module.comm, module.backend, int(means3D.shape[0])
+    with _frame_of(be, means3D.device):
+        inp = _rank_inputs(module, means3D, colors, opacities, scales, rotations)
+        lo, hi = _shell_range(module, inp)
+        H, W = inp["H"], inp["W"]
+        N = H * W
+        plan, ship, idx, sel = _open_frame(module, inp, N, be.select, lo, hi)              # 0   [M], M-row inputs
+        # `sel` already holds exactly this shell's rows: the shell test is NOT repeated inside the forward (two kernels need not
+        # round the same range expression identically; a Gaussian one ulp from an edge could be selected here and culled there)
+        if _fused(be):
+            st, _ = be.forward(sel, float("-inf"), float("inf"), plan, T_pass=ship[:N])    # 1   T_pass straight into what the all-gather ships
+        else:
+            st, T_pass = be.forward(sel, float("-inf"), float("inf"))
+            ship[:N] = T_pass
+        radii, wait_radii = _scatter_radii(module, idx, st, P, comm.all_reduce_async)
+        allT = comm.all_gather(ship)                                                       # 2   [G, N (+G)]
+        T_in = be.transmittance(allT[:, :N], comm.rank)
+        planes = comm.all_gather(be.render(st, T_in))                                      # 3, 4   [G, 5, N]
+        color, depth, occ, T_final, behind = be.compose(planes, comm.rank, inp["bg"], H, W)
+        saved = _close_frame(module, plan, dict(st=st, behind=behind, T_final=T_final, idx=idx, P=P), allT, N, wait_radii)
+        return (color, depth, occ, radii), saved
 
 
 def shell_backward(module, saved, g_color, g_depth, g_occ):
+    """Steps 5-6.  Returns the six gradients as `grad_sync` asks (_sync_grads)."""
     with _frame_of(module.backend, g_color.device):
-        return _shell_backward(module, saved, g_color, g_depth, g_occ)
-
-
-def wedge_forward(module, means3D, colors, opacities, scales, rotations):
-    with _frame_of(module.backend, means3D.device):
-        return _wedge_forward(module, means3D, colors, opacities, scales, rotations)
-
-
-def wedge_backward(module, saved, g_color, g_depth, g_occ):
-    with _frame_of(module.backend, g_color.device):
-        return _wedge_backward(module, saved, g_color, g_depth, g_occ)
-
-
-class _ShellRasterize(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, means3D, means2D, colors, opacities, scales, rotations, module):
-        outs, saved = shell_forward(module, means3D, colors, opacities, scales, rotations)
-        ctx.module, ctx.saved = module, saved
-        ctx.mark_non_differentiable(outs[3])
-        return outs
-
-    @staticmethod
-    def backward(ctx, g_color, g_depth, g_occ, _g_radii):
-        g = shell_backward(ctx.module, ctx.saved, g_color, g_depth, g_occ)
-        return g["means3D"], g["means2D"], g["colors"], g["opacities"], g["scales"], g["rotations"], None
-
-
-class _ShardRasterize(torch.autograd.Function):
-    """grad_sync = "shard": the frame is rendered from the REPLICATED tensors (no gradient flows to them); the gradients come back for the
-    rank's own shard leaves [rows_r, w] -- rows [r * rows, r * rows + rows_r) of the replicated ones, which the caller keeps equal to them."""
-
-    @staticmethod
-    def forward(ctx, means3D, colors, opacities, scales, rotations, s_means3D, s_means2D, s_colors, s_opacities, s_scales, s_rotations, module, wedges):
-        outs, saved = (wedge_forward if wedges else shell_forward)(module, means3D, colors, opacities, scales, rotations)
-        ctx.module, ctx.saved, ctx.wedges = module, saved, wedges
-        ctx.mark_non_differentiable(outs[3])
-        return outs
-
-    @staticmethod
-    def backward(ctx, g_color, g_depth, g_occ, _g_radii):
-        g = (wedge_backward if ctx.wedges else shell_backward)(ctx.module, ctx.saved, g_color, g_depth, g_occ)
-        return (None, None, None, None, None, g["means3D"], g["means2D"], g["colors"], g["opacities"], g["scales"], g["rotations"], None, None)
-
-
-def _shard_apply(module, wedges, means3D, opacities, colors, scales, rotations, shard):
-    P = int(means3D.shape[0])
-    base, n = shard_rows(P, module.comm.world, module.comm.rank)
-    keys = ("means3D", "means2D", "colors", "opacities", "scales", "rotations")
-    if shard is None or any(k not in shard for k in keys):
-        raise ValueError('grad_sync="shard": pass shard=dict(means3D, means2D, colors, opacities, scales, rotations) -- this rank\'s own rows as leaves')
-    for k, w in GRAD_WIDTHS:
-        if tuple(shard[k].shape) != (n, w):
-            raise ValueError(f'grad_sync="shard": shard["{k}"] must be [{n}, {w}] (rows {base}..{base + n} of the replicated tensor), got {tuple(shard[k].shape)}')
-    d = lambda t: t.detach()
-    return _ShardRasterize.apply(d(means3D), d(colors), d(opacities), d(scales), d(rotations), shard["means3D"], shard["means2D"], shard["colors"],
-                                 shard["opacities"], shard["scales"], shard["rotations"], module, wedges)
-
-
-class ShellRasterizer(nn.Module):
-    """Range-shell sharded counterpart of GaussianRasterizer.forward (colors_precomp + scales/rotations path,
-    the one gaussian_renderer.render() uses).  Inputs are REPLICATED on every rank; outputs are identical
-    on every rank; gradients follow `grad_sync`."""
-
-    def __init__(self, raster_settings, comm=None, backend=None, grad_sync="reduce_scatter", edges=None):
-        super().__init__()
-        assert grad_sync in ("reduce_scatter", "reduce_scatter_dense", "all_reduce", "none", "shard")
-        self.raster_settings = raster_settings
-        self.comm = comm if comm is not None else SingleComm()
-        self.backend = backend if backend is not None else HipShellBackend()
-        self.grad_sync = grad_sync
-        self.edges = edges
-        self.enqueue_only = os.environ.get("LIDARGS_ENQUEUE_ONLY", "0") == "1"     # see _RankPlan; off by default
-        self.ship_live = _ship_live_default()      # the gradient exchange ships only rows with a gradient: True / False / "auto" (_exchange_rows)
-        self.plan = _RankPlan()
-
-    def forward(self, means3D, means2D, opacities, colors_precomp, scales, rotations, shard=None):
-        """grad_sync "shard" (round 6): `shard` = this rank's own rows of the six tensors as leaves (shard_rows(P, world, rank)); the
-        replicated arguments only feed the rendering and receive no gradient."""
-        if self.grad_sync == "shard":
-            return _shard_apply(self, False, means3D, opacities, colors_precomp, scales, rotations, shard)
-        return _ShellRasterize.apply(means3D, means2D, colors_precomp, opacities, scales, rotations, self)
+        # d(color)/d(T_final) for the background is inside the blend: (-T_final/(1-alpha)) * bg.g  (R3/cr/backward.cu:727)
+        g = module.backend.backward(saved["st"], saved["behind"], saved["T_final"], _pixel_grads(saved, g_color, g_depth, g_occ))
+        return _sync_grads(module, saved, g, add=False)
 
 
 # ======================================================================================================================
@@ -1057,115 +908,98 @@ def wedge_edges(means3D, viewmatrix, W, world, scales=None, shares=None):
     return edges
 
 
-def _wedge_forward(module, means3D, colors, opacities, scales, rotations):
+def wedge_forward(module, means3D, colors, opacities, scales, rotations):
     """Returns ((color, depth, occ, radii), saved-for-backward)."""
-    rs, comm, be = module.raster_settings, module.comm, module.backend
-    H, W = int(rs.image_height), int(rs.image_width)
-    dev = means3D.device
-    P = int(means3D.shape[0])
-    f32 = lambda t: t.detach() if (t.dtype == torch.float32 and t.is_contiguous()) else t.detach().to(torch.float32).contiguous()
-    inp = dict(means3D=f32(means3D), colors=f32(colors), opacities=f32(opacities), scales=f32(scales), rotations=f32(rotations),
-               viewmatrix=f32(rs.viewmatrix), beams=f32(rs.beam_inclinations), H=H, W=W, scale_modifier=float(rs.scale_modifier),
-               far=int(rs.lidar_far), near=int(rs.lidar_near), bg=rs.bg.to(torch.float32).to(dev).contiguous())
-    edges = module.edges
-    if edges is None:
-        e = torch.tensor(wedge_edges(inp["means3D"], inp["viewmatrix"], W, comm.world, scales=inp["scales"]), dtype=torch.int32, device=dev)
-        edges = [int(x) for x in comm.broadcast(e, 0).tolist()]          # every rank must cut at the same columns
-    c0, c1 = int(edges[comm.rank]), int(edges[comm.rank + 1])
-    wmax = max(int(edges[g + 1]) - int(edges[g]) for g in range(comm.world))
-
-    exchange = comm.world > 1 and module.grad_sync in ("reduce_scatter", "shard")
-    fused = getattr(be, "fused_chunk_counts", False)
-    enqueue_only = module.enqueue_only and fused
-    plan = module.plan.next() if enqueue_only else None
-    block = torch.empty(4 * H * wmax + (comm.world if exchange else 0), dtype=torch.float32, device=dev)
-    chunks = None
-    if exchange:
-        rows = _chunk_rows(P, comm.world)
-        assert rows < (1 << 24)
-        chunks = (rows, comm.world, block[4 * H * wmax:])                          # the all-to-all's split sizes ride on the image gather
-    if fused:
-        idx, sel = be.select_wedge(inp, c0, c1, plan, chunks=chunks)               # [M], M-row inputs
-        st, planes = be.forward_wedge(sel, c0, c1, plan)
-    else:
-        idx, sel = be.select_wedge(inp, c0, c1)
-        if exchange:
-            be.chunk_counts(idx, *chunks)
-        st, planes = be.forward_wedge(sel, c0, c1)
-    radii = be.scatter_radii(idx, st["radii"], P)
-    wait_radii = comm.all_reduce_max_async(radii) if comm.world > 1 else (lambda: None)   # a boundary Gaussian reports the same radius twice
-    be.pack_columns(planes, H, W, c0, c1, wmax, block)
-    blocks = comm.all_gather(block)                                                # [G, 4 H wmax (+ G)]
-    color, depth, occ = be.unpack_columns(blocks, edges, H, W, wmax)
-    saved = dict(st=st, idx=idx, P=P)
-    if exchange:
-        saved.update(counts=_HostCounts(blocks[:, 4 * H * wmax:]))                 # [src, dst], read in the backward
-    if enqueue_only:
-        if plan is None:
-            module.plan.learn(int(idx.shape[0]), st["R"])
-        else:
-            module.plan.submitted()
-    wait_radii()
-    return (color, depth, occ, radii), saved
+    comm, be, P = module.comm, module.backend, int(means3D.shape[0])
+    with _frame_of(be, means3D.device):
+        inp = _rank_inputs(module, means3D, colors, opacities, scales, rotations)
+        H, W = inp["H"], inp["W"]
+        edges = module.edges
+        if edges is None:
+            e = torch.tensor(wedge_edges(inp["means3D"], inp["viewmatrix"], W, comm.world, scales=inp["scales"]), dtype=torch.int32, device=means3D.device)
+            edges = [int(x) for x in comm.broadcast(e, 0).tolist()]          # every rank must cut at the same columns
+        c0, c1 = int(edges[comm.rank]), int(edges[comm.rank + 1])
+        wmax = max(int(edges[g + 1]) - int(edges[g]) for g in range(comm.world))
+        plan, ship, idx, sel = _open_frame(module, inp, 4 * H * wmax, be.select_wedge, c0, c1)   # [M], M-row inputs
+        st, planes = be.forward_wedge(sel, c0, c1) if plan is None else be.forward_wedge(sel, c0, c1, plan)
+        radii, wait_radii = _scatter_radii(module, idx, st, P, comm.all_reduce_max_async)  # a boundary Gaussian reports the same radius twice
+        be.pack_columns(planes, H, W, c0, c1, wmax, ship)
+        blocks = comm.all_gather(ship)                                                     # [G, 4 H wmax (+ G)]
+        color, depth, occ = be.unpack_columns(blocks, edges, H, W, wmax)
+        saved = _close_frame(module, plan, dict(st=st, idx=idx, P=P), blocks, 4 * H * wmax, wait_radii)
+        return (color, depth, occ, radii), saved
 
 
-def _wedge_backward(module, saved, g_color, g_depth, g_occ):
-    st, idx, P = saved["st"], saved["idx"], saved["P"]
-    comm, be = module.comm, module.backend
-    inp = st["inp"]
-    H, W = inp["H"], inp["W"]
-    g = be.backward_plain(st, (g_color.reshape(2, H * W), g_depth.reshape(H * W), g_occ.reshape(H * W)))
-    sync = module.grad_sync if comm.world > 1 else "none"
-    if module.grad_sync == "shard":
-        return _shard_grads(module, saved, g, idx, P, add=True)
-    if sync == "reduce_scatter":
-        dense = be.unpack_rows_add(_exchange_rows(module, saved, g, idx, P), P)
-    else:
-        packed = be.pack_rows(g, idx)
-        module.plan.check()                        # every sync mode (see _shell_backward)
-        dense = be.unpack_rows_add(packed, P)
-        if sync == "all_reduce":
-            dense = comm.all_reduce(dense)
-    o, out = 0, {}
-    for k, w in GRAD_WIDTHS:
-        out[k] = dense[o * P:(o + w) * P].view(P, w)
-        o += w
-    return out
+def wedge_backward(module, saved, g_color, g_depth, g_occ):
+    """The wedge's purely local backward, then the gradient rows as `grad_sync` asks (_sync_grads): boundary Gaussians' rows are added."""
+    with _frame_of(module.backend, g_color.device):
+        g = module.backend.backward_plain(saved["st"], _pixel_grads(saved, g_color, g_depth, g_occ))
+        return _sync_grads(module, saved, g, add=True)
 
 
-class _WedgeRasterize(torch.autograd.Function):
+# ---- the autograd Function and the modules, either cut -------------------------------------------------------------
+class _Rasterize(torch.autograd.Function):
+    """A rank's frame through the module's cut (`module.passes`: its forward and backward).  The gradients go to the replicated inputs,
+    or under grad_sync "shard" to the six shard leaves behind them: the rank's own rows [rows_r, w] -- rows [r * rows, r * rows + rows_r)
+    of the replicated tensors, which the caller keeps equal to them; the replicated tensors then come detached and receive none."""
+
     @staticmethod
-    def forward(ctx, means3D, means2D, colors, opacities, scales, rotations, module):
-        outs, saved = wedge_forward(module, means3D, colors, opacities, scales, rotations)
-        ctx.module, ctx.saved = module, saved
+    def forward(ctx, module, means3D, means2D, colors, opacities, scales, rotations, *shard):
+        outs, saved = module.passes[0](module, means3D, colors, opacities, scales, rotations)
+        ctx.module, ctx.saved, ctx.sharded = module, saved, bool(shard)
         ctx.mark_non_differentiable(outs[3])
         return outs
 
     @staticmethod
     def backward(ctx, g_color, g_depth, g_occ, _g_radii):
-        g = wedge_backward(ctx.module, ctx.saved, g_color, g_depth, g_occ)
-        return g["means3D"], g["means2D"], g["colors"], g["opacities"], g["scales"], g["rotations"], None
+        g = ctx.module.passes[1](ctx.module, ctx.saved, g_color, g_depth, g_occ)
+        g = tuple(g[k] for k, _ in GRAD_WIDTHS)                       # means3D, means2D, colors, opacities, scales, rotations
+        return (None,) + ((None,) * 6 + g if ctx.sharded else g)
 
 
-class WedgeRasterizer(nn.Module):
-    """Column-wedge sharded counterpart of GaussianRasterizer.forward (colors_precomp + scales/rotations path).  Inputs are
-    REPLICATED on every rank; outputs are identical on every rank and, for the image, equal to the single-GPU forward's up to the
-    grouping of the per-segment partial sums (bit-identical whenever the rank's segment plan is the single-GPU one);
-    gradients follow `grad_sync` ("reduce_scatter": rank r ends with rows [r*P/N, (r+1)*P/N); "all_reduce"; "none")."""
+class _ShardedRasterizer(nn.Module):
+    """The body ShellRasterizer and WedgeRasterizer share; a subclass names its cut's `passes` and the `grad_syncs` it accepts."""
 
     def __init__(self, raster_settings, comm=None, backend=None, grad_sync="reduce_scatter", edges=None):
         super().__init__()
-        assert grad_sync in ("reduce_scatter", "all_reduce", "none", "shard")
+        assert grad_sync in self.grad_syncs
         self.raster_settings = raster_settings
         self.comm = comm if comm is not None else SingleComm()
         self.backend = backend if backend is not None else HipShellBackend()
         self.grad_sync = grad_sync
         self.edges = edges
         self.enqueue_only = os.environ.get("LIDARGS_ENQUEUE_ONLY", "0") == "1"     # see _RankPlan; off by default
-        self.ship_live = _ship_live_default()      # (see ShellRasterizer)
+        self.ship_live = _ship_live_default()      # the gradient exchange ships only rows with a gradient: True / False / "auto" (_exchange_rows)
         self.plan = _RankPlan()
 
     def forward(self, means3D, means2D, opacities, colors_precomp, scales, rotations, shard=None):
-        if self.grad_sync == "shard":                # (see ShellRasterizer.forward)
-            return _shard_apply(self, True, means3D, opacities, colors_precomp, scales, rotations, shard)
-        return _WedgeRasterize.apply(means3D, means2D, colors_precomp, opacities, scales, rotations, self)
+        """grad_sync "shard" (round 6): `shard` = this rank's own rows of the six tensors as leaves (shard_rows(P, world, rank)); the
+        replicated arguments only feed the rendering and receive no gradient."""
+        if self.grad_sync != "shard":
+            return _Rasterize.apply(self, means3D, means2D, colors_precomp, opacities, scales, rotations)
+        P = int(means3D.shape[0])
+        base, n = shard_rows(P, self.comm.world, self.comm.rank)
+        if shard is None or any(k not in shard for k, _ in GRAD_WIDTHS):
+            raise ValueError('grad_sync="shard": pass shard=dict(means3D, means2D, colors, opacities, scales, rotations) -- this rank\'s own rows as leaves')
+        for k, w in GRAD_WIDTHS:
+            if tuple(shard[k].shape) != (n, w):
+                raise ValueError(f'grad_sync="shard": shard["{k}"] must be [{n}, {w}] (rows {base}..{base + n} of the replicated tensor), got {tuple(shard[k].shape)}')
+        d = lambda t: t.detach()
+        return _Rasterize.apply(self, d(means3D), None, d(colors_precomp), d(opacities), d(scales), d(rotations), *(shard[k] for k, _ in GRAD_WIDTHS))
+
+
+class ShellRasterizer(_ShardedRasterizer):
+    """Range-shell sharded counterpart of GaussianRasterizer.forward (colors_precomp + scales/rotations path,
+    the one gaussian_renderer.render() uses).  Inputs are REPLICATED on every rank; outputs are identical
+    on every rank; gradients follow `grad_sync`."""
+    passes = (shell_forward, shell_backward)
+    grad_syncs = ("reduce_scatter", "reduce_scatter_dense", "all_reduce", "none", "shard")
+
+
+class WedgeRasterizer(_ShardedRasterizer):
+    """Column-wedge sharded counterpart of GaussianRasterizer.forward (colors_precomp + scales/rotations path).  Inputs are
+    REPLICATED on every rank; outputs are identical on every rank and, for the image, equal to the single-GPU forward's up to the
+    grouping of the per-segment partial sums (bit-identical whenever the rank's segment plan is the single-GPU one);
+    gradients follow `grad_sync` ("reduce_scatter": rank r ends with rows [r*P/N, (r+1)*P/N); "all_reduce"; "none"; "shard")."""
+    passes = (wedge_forward, wedge_backward)
+    grad_syncs = ("reduce_scatter", "all_reduce", "none", "shard")

@@ -1,7 +1,7 @@
 """CPU stand-in for lidargs_dist.HipShellBackend built on the ORACLE (test infrastructure only).
 
 It lets the world_size-2 gloo tests drive the product's collective / compositing logic
-(lidargs_dist._ShellRasterize) without a GPU: same protocol, numpy oracle underneath."""
+(lidargs_dist._Rasterize) without a GPU: same protocol, numpy oracle underneath."""
 import numpy as np
 import torch
 

@@ -1,6 +1,6 @@
 """world_size-2 (and 3) gloo tests of the range-shell multi-GPU path on CPU.
 
-The product code under test is lidargs_dist._ShellRasterize (shell edges, the two all-gathers, the
+The product code under test is lidargs_dist._Rasterize over range shells (shell edges, the two all-gathers, the
 transmittance products, T_final selection, behind-sums, gradient reduce-scatter).  The per-rank
 renderer is the oracle-backed stand-in of tests/dist_backend_oracle.py, and the expected result is
 the plain single-process oracle on the whole scene."""
@@ -191,7 +191,7 @@ WEDGE_CASES = [
 
 @pytest.mark.parametrize("case", WEDGE_CASES, ids=[c[0] for c in WEDGE_CASES])
 def test_wedge_sharding_matches_single_process(case, tmp_path):
-    """lidargs_dist._WedgeRasterize over gloo: edges, selection bound, image gather, radii max-reduce, gradient all-to-all with
+    """lidargs_dist._Rasterize over column wedges and gloo: edges, selection bound, image gather, radii max-reduce, gradient all-to-all with
     addition of the boundary Gaussians' partial rows -- against the plain single-process oracle.  The image must be EXACTLY the
     single-process one (a rank's lists are the complete lists of its tiles)."""
     from util import GRAD_KEYS_SR, oracle_forward_backward, parity

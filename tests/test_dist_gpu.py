@@ -88,7 +88,7 @@ class ThreadComm:
         return full[self.rank * rows:(self.rank + 1) * rows].clone()
 
 
-def _run_rank(shared, rank, scene, W, H, grads, grad_sync, results, wedges=False, edges=None, frames=1, enqueue=False):
+def _run_rank(shared, rank, scene, W, H, grads, grad_sync, results, wedges=False, edges=None, frames=1, enqueue=False, ship_live=None):
     """Drives lidargs_dist.shell_forward / shell_backward (or the wedge pair) directly: torch's autograd engine executes all
     CUDA nodes on ONE worker thread per device, which would serialise (and deadlock) the virtual ranks."""
     comm = None
@@ -105,7 +105,9 @@ def _run_rank(shared, rank, scene, W, H, grads, grad_sync, results, wedges=False
             mod = lidargs_dist.ShellRasterizer(make_settings(st, W, H), comm, grad_sync=grad_sync)
             fwd, bwd = lidargs_dist.shell_forward, lidargs_dist.shell_backward
         mod.enqueue_only = enqueue
-        if int(st["means3D"].shape[0]) < 1_000_000:
+        if ship_live is not None:
+            mod.ship_live = ship_live
+        elif int(st["means3D"].shape[0]) < 1_000_000:
             mod.ship_live = int(st["means3D"].shape[0]) % 2 == 1      # both forms of the gradient exchange at test sizes ("auto" turns the live form on for the full-size cfg4 frames only)
         for _ in range(frames):          # (enqueue-only: the first frame is an ordinary one and teaches the plan its capacities)
             (color, depth, occ, radii), saved = fwd(mod, st["means3D"], st["colors"], st["opacities"], st["scales"], st["rotations"])
@@ -465,10 +467,10 @@ def test_cfg4_sharded_over_8_virtual_ranks_at_full_size(hip_lib_built):
 
 
 # ---- column wedges -------------------------------------------------------------------------------------------------------------
-def _virtual_ranks(world, scene, W, H, grads, grad_sync, wedges, edges=None, timeout=900, frames=1, enqueue=False):
+def _virtual_ranks(world, scene, W, H, grads, grad_sync, wedges, edges=None, timeout=900, frames=1, enqueue=False, ship_live=None):
     shared = ThreadComm.Shared(world)
     results = [None] * world
-    threads = [threading.Thread(target=_run_rank, args=(shared, r, scene, W, H, grads, grad_sync, results, wedges, edges, frames, enqueue)) for r in range(world)]
+    threads = [threading.Thread(target=_run_rank, args=(shared, r, scene, W, H, grads, grad_sync, results, wedges, edges, frames, enqueue, ship_live)) for r in range(world)]
     for t in threads: t.start()
     for t in threads: t.join(timeout=timeout)
     assert not any(t.is_alive() for t in threads), "virtual ranks hung"
@@ -632,6 +634,24 @@ def test_wedge_with_no_gaussian_in_reach(hip_lib_built):
     full = _assemble(results, plain, P, world, grad_sync)
     for k in GRAD_KEYS_SR:
         parity(f"{k} vs plain", full[k], plain[k], verbose=False)
+
+
+@pytest.mark.parametrize("wedges", [False, True], ids=["shells", "wedges"])
+def test_empty_model_with_live_rows_forced_on(wedges, hip_lib_built):
+    """P = 0 with `ship_live` forced on: an empty model has no index chunks to count live rows into (lidargs_shell_pack_grad_rows_live_count
+    refuses chunk_rows = 0), so its exchange ships every selected row -- none.  Every rank: the background image, no radii, empty gradients."""
+    world, H, W, seed = 2, 16, 512, 97
+    scene = sc.make_scene("street", 1000, H, seed, random_view=True)
+    for k in ("means3D", "scales", "rotations", "opacities", "colors"):
+        scene[k] = np.ascontiguousarray(scene[k][:0])
+    scene["bg"] = np.array([0.3, 0.6], np.float32)
+    results = _virtual_ranks(world, scene, W, H, sc.upstream_grads(H, W, seed), "reduce_scatter", wedges, ship_live=True)
+    bg = np.broadcast_to(scene["bg"].reshape(2, 1, 1), (2, H, W))
+    for r in range(world):
+        assert results[r]["radii"].shape == (0,)
+        assert np.array_equal(results[r]["color"], bg) and not results[r]["depth"].any() and not results[r]["occ"].any()
+        for k, w in zip(GRAD_KEYS_SR, (3, 4, 2, 1, 3, 4)):
+            assert results[r][k].shape == (0, w), (k, r)
 
 
 # ---- bench.py's sharded legs ------------------------------------------------------------------------------------------------------
