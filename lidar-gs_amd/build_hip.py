@@ -7,7 +7,8 @@ Output: lidar-gs_amd/diff_lidargs_rasterization/liblidargs_hip.so  (git-ignored,
 Per-file flags: the per-Gaussian kernels (preprocess.hip) are HBM-bound, so they are built with
 -ffp-contract=off: every expression rounds as written, which keeps the unit vectors s = p/|p| that
 feed the cancellation-prone blend difference (s - q) bit-identical to an un-fused evaluation.
-The blend kernels (render.hip) keep FMA contraction.
+The blend kernels (render.hip) keep FMA contraction.  The sharded path's file (shard.hip) holds kernels of both kinds and says
+which is which by `#pragma clang fp contract` in front of each part: a flag would speak for the whole file.
 """
 import os
 import subprocess
@@ -24,6 +25,7 @@ SOURCES = {
     "api.hip": [],
     "preprocess.hip": ["-ffp-contract=off"],
     "binning.hip": [],
+    "shard.hip": [],   # pragmas, not a flag: its selection and gradient-row kernels round as written (the selection must agree with k_preprocess bit for bit), its image folds fuse
     "render.hip": ["-fno-slp-vectorize"],  # the packed-fp32 pairs are written out (v2f); the SLP vectorizer pairs the rest up at the price of moves
     "neural_gaussians.hip": [],
     "lidar_loss.hip": [],

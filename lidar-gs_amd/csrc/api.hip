@@ -1,6 +1,8 @@
 // api.hip -- extern "C" entry points of include/lidargs_rasterizer.h and the host-side
 // stage sequence (the counterpart of CudaRasterizer::Rasterizer::{forward,backward,...},
-// R3/cr/rasterizer_impl.cu:202-549).
+// R3/cr/rasterizer_impl.cu:202-549): forward_impl / backward_impl and every frame that goes
+// through them, the sharded path's (range shells, column wedges) included.  What the sharded
+// path launches around a rank's frame -- selection, gradient rows, image folds -- is shard.hip.
 //
 // Differences from the reference's host sequence, all behind the same interface:
 //   - everything is enqueued on the caller's stream; there is no device-wide synchronise
@@ -493,25 +495,36 @@ int bin_frame(const BinSpec& spec, const GeomView& geom, uint2* ranges, size_t P
 
 namespace {
 
+// Which kind of frame a forward entry point asks forward_impl for: filled by field name, so that no mode hangs on an argument's position.
+struct FrameMode {
+    // > 0: ENQUEUE-ONLY mode.  Nothing is read back: the binning buffer is sized for `instance_capacity` instances at the caller's
+    // tile height (fixed_tile_rows: 4, 8, 16 or 32), every count the later stages need stays on the device, and the 16 status words
+    // (binning.hip k_finish_totals: instances needed / binned, totals per tile height, overflow flag) are copied to `status_host`
+    // (pinned, optional) by the stream.  The call can therefore be captured in a HIP graph.
+    long long instance_capacity = 0;
+    int fixed_tile_rows = 0;
+    unsigned* status_host = nullptr;
+    int col_lo = -1, col_hi = -1;        // >= 0: a column wedge, only the tile columns of pixel columns [col_lo, col_hi) are binned and rendered
+    // The call comes from lidargs_forward_shell*.  Its backward (lidargs_backward_shell) walks the slot grid with the flags and limits of
+    // the segmented launches, whatever T_in / T_out / transmittance_pass were -- a first or only shell passes none of them -- so the
+    // mode is the entry point's, not inferred from those arguments (round-3 advisor finding: a direct ABI caller of a single shell got
+    // the fused blend and a work list here, and a backward that read planes and flags the fused blend never wrote).
+    bool is_shell = false;
+    // device word, optional: the P rows are a capacity-sized selection of which only the first *n_valid exist (enqueue-only rank frames
+    // of the sharded path): the preprocess culls the rest before reading them, everything behind it sees culled Gaussians.
+    const uint32_t* n_valid = nullptr;
+};
+
 int forward_impl(lidargs_alloc_fn geometry_alloc, void* geometry_user, lidargs_alloc_fn binning_alloc, void* binning_user,
                  lidargs_alloc_fn image_alloc, void* image_user, int P, const float* background, int width, int height,
                  const float* means3D, const float* colors_precomp, const float* opacities, const float* scales,
                  float scale_modifier, const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
                  const float* beams, float near_f, float far_f, float shell_lo, float shell_hi, const float* T_in,
                  int transmittance_pass, float* out_color, float* out_depth, float* out_occ, float* T_out, int* radii,
-                 int* radii_xy, int debug, hipStream_t stream, long long instance_capacity = 0, int fixed_tile_rows = 0,
-                 unsigned* status_host = nullptr, int col_lo = -1, int col_hi = -1, bool is_shell = false,
-                 const uint32_t* n_valid = nullptr) {
-    // n_valid (device word, optional): the P rows are a capacity-sized selection of which only the first *n_valid exist (enqueue-only
-    // rank frames of the sharded path): the preprocess culls the rest before reading them, everything behind it sees culled Gaussians.
-    // is_shell: the call comes from lidargs_forward_shell.  Its backward (lidargs_backward_shell) walks the slot grid with the flags and
-    // limits of the segmented launches, whatever T_in / T_out / transmittance_pass were -- a first or only shell passes none of them
-    // -- so the mode is the entry point's, not inferred from those arguments (round-3 advisor finding: a direct ABI caller of a single
-    // shell got the fused blend and a work list here, and a backward that read planes and flags the fused blend never wrote).
-    // instance_capacity > 0: ENQUEUE-ONLY mode.  Nothing is read back: the binning buffer is sized for `instance_capacity`
-    // instances at the caller's tile height, every count the later stages need stays on the device, and the 16 status words
-    // (binning.hip k_finish_totals: instances needed / binned, totals per tile height, overflow flag) are copied to
-    // `status_host` (pinned, optional) by the stream.  The call can therefore be captured in a HIP graph.
+                 int* radii_xy, int debug, hipStream_t stream, const FrameMode& mode) {
+    const long long instance_capacity = mode.instance_capacity;
+    const int fixed_tile_rows = mode.fixed_tile_rows, col_lo = mode.col_lo, col_hi = mode.col_hi;
+    const bool is_shell = mode.is_shell;
     const bool enqueue_only = instance_capacity > 0;
     if (enqueue_only && !(fixed_tile_rows == 4 || fixed_tile_rows == 8 || fixed_tile_rows == 16 || fixed_tile_rows == 32))
         return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward (enqueue-only): tile_rows must be 4, 8, 16 or 32%s");
@@ -553,14 +566,14 @@ int forward_impl(lidargs_alloc_fn geometry_alloc, void* geometry_user, lidargs_a
     pp.col_step = 2 * pi_f / width; pp.inv_col_step = (1.f / pp.col_step) * 1.000001f;                                    // R3/cr/forward.cu:334
     pp.tan_col_step = tanf(2 * pi_f / width);                          // R3/cr/forward.cu:362
     pp.view = viewmatrix;
-    pp.n_valid = n_valid;
+    pp.n_valid = mode.n_valid;
 
     lg::launch_preprocess(pp, means3D, scales, rotations, opacities, colors_precomp, cov3D_precomp, beams, radii, radii_xy,
                           geom, &img, false, stream);                  // also fills the pixel-ray tables of the image buffer
     LG_STAGE_CHECK("preprocess");
     lg::prof_mark("preprocess", stream);
 
-    const lg::BinSpec spec = {is_shell ? lg::FRAME_SHELL : lg::FRAME_GAUSS, fixed_tile_rows, instance_capacity, status_host, "forward"};
+    const lg::BinSpec spec = {is_shell ? lg::FRAME_SHELL : lg::FRAME_GAUSS, fixed_tile_rows, instance_capacity, mode.status_host, "forward"};
     lg::BinnedFrame bf;
     const int rendered = lg::bin_frame(spec, geom, img.ranges, (size_t)P, width, height, col_lo, col_hi, pp.compact != 0, binning_alloc, binning_user,
                                        debug, stream, &bf);
@@ -616,15 +629,23 @@ int forward_impl(lidargs_alloc_fn geometry_alloc, void* geometry_user, lidargs_a
     return rendered;
 }
 
+// The same for backward_impl: which forward made the buffers (its layout must be carved the same way) and what lies behind a shell.
+struct BackMode {
+    bool is_shell = false;                       // the buffers are lidargs_forward_shell*'s
+    const float* behind = nullptr;               // shell: the colour / depth sums of the shells behind this one, per pixel
+    const float* T_final_global = nullptr;       // shell: the frame's final transmittance, per pixel
+    int col_lo = -1, col_hi = -1;                // >= 0: the buffers are a column wedge's
+};
+
 int backward_impl(int P, int R, const float* background, int width, int height, const float* means3D,
                   const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
                   const float* cov3D_precomp, const float* viewmatrix, const float* beams, const int* radii, char* geom_buffer,
-                  char* binning_buffer, char* image_buffer, const float* behind, const float* T_final_global, int shell_mode,
-                  const float* dL_dpix, const float* dL_dout_depth, const float* dL_dout_occ, float* dL_dmean2D,
+                  char* binning_buffer, char* image_buffer, const BackMode& mode, const float* dL_dpix, const float* dL_dout_depth, const float* dL_dout_occ, float* dL_dmean2D,
                   float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_ddepths, float* dL_dmean3D,
                   float* dL_dsphere_means3D, float* dL_dbasis_u1, float* dL_dbasis_u2, float* dL_dcov3D, float* dL_dscale,
-                  float* dL_drot, int debug, hipStream_t stream, int col_lo = -1, int col_hi = -1) {
+                  float* dL_drot, int debug, hipStream_t stream) {
     (void)colors_precomp; (void)beams;
+    const int col_lo = mode.col_lo, col_hi = mode.col_hi;
     if (P < 0 || R < 0 || width <= 0 || height <= 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "backward: bad sizes%s");
     if (P == 0) return 0;   // R3/rasterize_points.cu:177
     if (!geom_buffer || !binning_buffer || !image_buffer) return fail(LIDARGS_ERR_STATE, "backward: missing forward buffers%s");
@@ -636,7 +657,7 @@ int backward_impl(int P, int R, const float* background, int width, int height, 
     lg::GeomView geom; lg::geom_carve(geom_buffer, (size_t)P, lg::GAUSS_BUFFERS, &geom);
     // a column wedge's buffers: only its own patches were rendered
     if (col_lo >= 0 && (col_lo % LG_TILE_W || col_hi <= col_lo || col_hi > width)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "backward: bad column wedge%s");
-    const lg::FrameLayout L = lg::frame_layout(R, width, height, col_lo, col_hi, shell_mode ? lg::FRAME_SHELL : lg::FRAME_GAUSS);   // (from the forward's num_rendered)
+    const lg::FrameLayout L = lg::frame_layout(R, width, height, col_lo, col_hi, mode.is_shell ? lg::FRAME_SHELL : lg::FRAME_GAUSS);   // (from the forward's num_rendered)
     lg::BinView bin; L.bin_carve(binning_buffer, &bin);
     lg::ImgView img; lg::img_carve(image_buffer, width, height, lg::make_grid(width, height, 4).num_tiles(), &img);
     lg::prof_begin(stream, 1);
@@ -656,7 +677,7 @@ int backward_impl(int P, int R, const float* background, int width, int height, 
     rb.seg = bin.seg; rb.S = L.S; rb.seg_len = L.plan.seg_len;
     rb.alive = L.gated ? bin.alive : nullptr;
     rb.flags = L.flags ? bin.flags : nullptr; rb.R = L.Rp;
-    rb.T_final_global = T_final_global; rb.behind = behind;
+    rb.T_final_global = mode.T_final_global; rb.behind = mode.behind;
     rb.dL_dpix = dL_dpix; rb.dL_ddepth = dL_dout_depth; rb.dL_docc = dL_dout_occ; rb.gacc = geom.gacc;
     if (L.work_list) rb.walk = lg::work_list(bin);
     lg::launch_render_backward(rb, stream);
@@ -678,50 +699,6 @@ int backward_impl(int P, int R, const float* background, int width, int height, 
     return 0;
 }
 
-// The first steps of a two-step or an enqueue-only selection, either cut: check the scratch (`too_small`: the caller's message), carve
-// flags / offsets / total / scan scratch out of it, run the cut's flags launch (`launch_flags(flags)`), then the exclusive scan.
-struct SelectScan { uint32_t* flags; uint32_t* offs; uint32_t* total; };
-template <class LaunchFlags>
-int select_scan(int P, char* scratch, size_t scratch_bytes, const char* too_small, hipStream_t stream, SelectScan& s, LaunchFlags launch_flags) {
-    if (scratch_bytes < lidargs_shell_select_scratch_bytes(P)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, too_small);
-    lg::Carver c(scratch);
-    s.flags = c.take<uint32_t>((size_t)P);
-    s.offs = c.take<uint32_t>((size_t)P);
-    s.total = c.take<uint32_t>(64);
-    uint32_t* scan_scratch = c.take<uint32_t>(lg::scan_scratch_words((size_t)P));
-    launch_flags(s.flags);
-    lg::launch_exclusive_scan(s.flags, s.offs, (size_t)P, s.total, scan_scratch, stream);
-    return 0;
-}
-
-// the count step: the scan, then the one host read of its total
-template <class LaunchFlags>
-int select_count(int P, char* scratch, size_t scratch_bytes, const char* too_small, hipStream_t stream, LaunchFlags launch_flags) {
-    SelectScan s;
-    if (const int rc = select_scan(P, scratch, scratch_bytes, too_small, stream, s, launch_flags)) return rc;
-    uint32_t total_h = 0;
-    LG_HIP((hipError_t)lg::api_read_words_zero_behind(s.total, 1, &total_h, nullptr, 0, stream));
-    return (int)total_h;
-}
-
-// Enqueue-only selections (no host read): flags + scan as above, then the gather into CAPACITY rows.  idx_out's tail is filled with
-// 0x7F7F7F7F (above every index: the array stays ascending, and every consumer skips indices >= P); n_valid_dev[0] = rows gathered =
-// min(selected, capacity), [1] = rows selected; both words go to status_host (pinned, optional) behind the launches.
-template <class LaunchFlags>
-int select_enqueue(int P, const float* means3D, const float* colors, const float* opacities, const float* scales, const float* rotations,
-                   int capacity, int* idx_out, float* out_means3D, float* out_colors, float* out_opacities, float* out_scales, float* out_rotations,
-                   unsigned* n_valid_dev, unsigned* status_host, char* scratch, size_t scratch_bytes, const char* too_small, int chunk_rows,
-                   int world, float* chunk_counts, hipStream_t stream, LaunchFlags launch_flags) {
-    SelectScan s;
-    if (const int rc = select_scan(P, scratch, scratch_bytes, too_small, stream, s, launch_flags)) return rc;
-    if (chunk_counts && (chunk_rows <= 0 || world <= 0 || world > 256)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "select (enqueue-only): chunk counts need chunk_rows > 0 and 1 <= world <= 256%s");
-    LG_HIP(hipMemsetAsync(idx_out, 0x7F, sizeof(int) * (size_t)capacity, stream));
-    lg::launch_shell_gather(P, s.flags, s.offs, means3D, colors, opacities, scales, rotations, idx_out, out_means3D, out_colors, out_opacities,
-                            out_scales, out_rotations, stream, (uint32_t)capacity, s.total, n_valid_dev, chunk_rows, world, chunk_counts);
-    if (status_host) LG_HIP(hipMemcpyAsync(status_host, n_valid_dev, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, stream));
-    return check_launch(stream, 0, "select gather (enqueue-only)");
-}
-
 }  // namespace
 
 extern "C" {
@@ -741,7 +718,7 @@ int lidargs_forward(lidargs_alloc_fn geometry_alloc, void* geometry_user, lidarg
     return forward_impl(geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user, P, background, width,
                         height, means3D, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix,
                         beam_inclinations, (float)lidar_near, (float)lidar_far, -inf, inf, nullptr, 0, out_color, out_depth,
-                        out_occ, nullptr, radii, radii_xy, debug, (hipStream_t)stream);
+                        out_occ, nullptr, radii, radii_xy, debug, (hipStream_t)stream, FrameMode());
 }
 
 int lidargs_forward_enqueue(lidargs_alloc_fn geometry_alloc, void* geometry_user, lidargs_alloc_fn binning_alloc, void* binning_user,
@@ -754,10 +731,12 @@ int lidargs_forward_enqueue(lidargs_alloc_fn geometry_alloc, void* geometry_user
     (void)D; (void)M; (void)shs; (void)projmatrix; (void)cam_pos; (void)prefiltered;
     if (instance_capacity <= 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward_enqueue: instance_capacity must be positive%s");
     const float inf = std::numeric_limits<float>::infinity();
+    FrameMode mode;
+    mode.instance_capacity = instance_capacity; mode.fixed_tile_rows = tile_rows; mode.status_host = status_host;
     return forward_impl(geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user, P, background, width,
                         height, means3D, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix,
                         beam_inclinations, (float)lidar_near, (float)lidar_far, -inf, inf, nullptr, 0, out_color, out_depth,
-                        out_occ, nullptr, radii, radii_xy, debug, (hipStream_t)stream, (long long)instance_capacity, tile_rows, status_host);
+                        out_occ, nullptr, radii, radii_xy, debug, (hipStream_t)stream, mode);
 }
 
 int lidargs_backward(int P, int D, int M, int R, const float* background, int width, int height, const float* means3D,
@@ -771,7 +750,7 @@ int lidargs_backward(int P, int D, int M, int R, const float* background, int wi
                      int debug, void* stream) {
     (void)D; (void)M; (void)shs; (void)projmatrix; (void)campos; (void)tan_fovx; (void)tan_fovy; (void)dL_dsh;
     return backward_impl(P, R, background, width, height, means3D, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
-                         viewmatrix, beam_inclinations, radii, geom_buffer, binning_buffer, image_buffer, nullptr, nullptr, 0, dL_dpix,
+                         viewmatrix, beam_inclinations, radii, geom_buffer, binning_buffer, image_buffer, BackMode(), dL_dpix,
                          dL_dout_depth, dL_dout_occ, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_ddepths, dL_dmean3D,
                          dL_dsphere_means3D, dL_dbasis_u1, dL_dbasis_u2, dL_dcov3D, dL_dscale, dL_drot, debug, (hipStream_t)stream);
 }
@@ -839,10 +818,12 @@ int lidargs_forward_shell(lidargs_alloc_fn geometry_alloc, void* geometry_user, 
                           const float* beam_inclinations, int lidar_far, int lidar_near, float shell_lo, float shell_hi,
                           const float* T_in, int transmittance_pass, float* out_color, float* out_depth, float* out_occ,
                           float* T_out, int* radii, int* radii_xy, int debug, void* stream) {
+    FrameMode mode;
+    mode.is_shell = true;
     return forward_impl(geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user, P, background, width,
                         height, means3D, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix,
                         beam_inclinations, (float)lidar_near, (float)lidar_far, shell_lo, shell_hi, T_in, transmittance_pass,
-                        out_color, out_depth, out_occ, T_out, radii, radii_xy, debug, (hipStream_t)stream, 0, 0, nullptr, -1, -1, true);
+                        out_color, out_depth, out_occ, T_out, radii, radii_xy, debug, (hipStream_t)stream, mode);
 }
 
 int lidargs_forward_shell_enqueue(lidargs_alloc_fn geometry_alloc, void* geometry_user, lidargs_alloc_fn binning_alloc, void* binning_user,
@@ -854,11 +835,13 @@ int lidargs_forward_shell_enqueue(lidargs_alloc_fn geometry_alloc, void* geometr
                                   float* T_out, int* radii, int* radii_xy, int debug, const unsigned* n_valid, int instance_capacity,
                                   int tile_rows, unsigned* status_host, void* stream) {
     if (instance_capacity <= 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward_shell_enqueue: instance_capacity must be positive%s");
+    FrameMode mode;
+    mode.is_shell = true; mode.n_valid = n_valid;
+    mode.instance_capacity = instance_capacity; mode.fixed_tile_rows = tile_rows; mode.status_host = status_host;
     return forward_impl(geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user, P, background, width,
                         height, means3D, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix,
                         beam_inclinations, (float)lidar_near, (float)lidar_far, shell_lo, shell_hi, T_in, transmittance_pass,
-                        out_color, out_depth, out_occ, T_out, radii, radii_xy, debug, (hipStream_t)stream, (long long)instance_capacity,
-                        tile_rows, status_host, -1, -1, true, n_valid);
+                        out_color, out_depth, out_occ, T_out, radii, radii_xy, debug, (hipStream_t)stream, mode);
 }
 
 // ---- column wedges (multi-GPU): rank g bins and renders the tile columns of pixel columns [col_lo, col_hi) only --------------------
@@ -873,10 +856,12 @@ int lidargs_forward_wedge(lidargs_alloc_fn geometry_alloc, void* geometry_user, 
     // there, and a wedge rendered from an under-selected set would silently miss its boundary Gaussians
     if (cov3D_precomp) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward_wedge: cov3D_precomp is not supported on the column-wedge path (give scales + rotations)%s");
     const float inf = std::numeric_limits<float>::infinity();
+    FrameMode mode;
+    mode.col_lo = col_lo; mode.col_hi = col_hi;
     return forward_impl(geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user, P, background, width,
                         height, means3D, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix,
                         beam_inclinations, (float)lidar_near, (float)lidar_far, -inf, inf, nullptr, 0, out_color, out_depth, out_occ,
-                        nullptr, radii, radii_xy, debug, (hipStream_t)stream, 0, 0, nullptr, col_lo, col_hi);
+                        nullptr, radii, radii_xy, debug, (hipStream_t)stream, mode);
 }
 
 int lidargs_forward_wedge_enqueue(lidargs_alloc_fn geometry_alloc, void* geometry_user, lidargs_alloc_fn binning_alloc, void* binning_user,
@@ -890,11 +875,13 @@ int lidargs_forward_wedge_enqueue(lidargs_alloc_fn geometry_alloc, void* geometr
     if (cov3D_precomp) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward_wedge: cov3D_precomp is not supported on the column-wedge path (give scales + rotations)%s");
     if (instance_capacity <= 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward_wedge_enqueue: instance_capacity must be positive%s");
     const float inf = std::numeric_limits<float>::infinity();
+    FrameMode mode;
+    mode.col_lo = col_lo; mode.col_hi = col_hi; mode.n_valid = n_valid;
+    mode.instance_capacity = instance_capacity; mode.fixed_tile_rows = tile_rows; mode.status_host = status_host;
     return forward_impl(geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user, P, background, width,
                         height, means3D, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix,
                         beam_inclinations, (float)lidar_near, (float)lidar_far, -inf, inf, nullptr, 0, out_color, out_depth, out_occ,
-                        nullptr, radii, radii_xy, debug, (hipStream_t)stream, (long long)instance_capacity, tile_rows, status_host,
-                        col_lo, col_hi, false, n_valid);
+                        nullptr, radii, radii_xy, debug, (hipStream_t)stream, mode);
 }
 
 int lidargs_backward_wedge(int P, int R, const float* background, int width, int height, const float* means3D, const float* colors_precomp,
@@ -905,36 +892,12 @@ int lidargs_backward_wedge(int P, int R, const float* background, int width, int
                            void* stream) {
     if (col_lo < 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "backward_wedge: col_lo < 0%s");
     if (cov3D_precomp) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "backward_wedge: cov3D_precomp is not supported on the column-wedge path (give scales + rotations)%s");
+    BackMode mode;
+    mode.col_lo = col_lo; mode.col_hi = col_hi;
     return backward_impl(P, R, background, width, height, means3D, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix,
-                         beam_inclinations, radii, geom_buffer, binning_buffer, image_buffer, nullptr, nullptr, 0, dL_dpix, dL_dout_depth,
+                         beam_inclinations, radii, geom_buffer, binning_buffer, image_buffer, mode, dL_dpix, dL_dout_depth,
                          dL_dout_occ, dL_dmean2D, nullptr, dL_dopacity, dL_dcolor, nullptr, dL_dmean3D, nullptr, nullptr, nullptr, dL_dcov3D,
-                         dL_dscale, dL_drot, debug, (hipStream_t)stream, col_lo, col_hi);
-}
-
-int lidargs_wedge_pack_columns(int height, int width, int col_lo, int col_hi, int wmax, const float* color, const float* depth, const float* occ,
-                               float* out, void* stream) {
-    if (height <= 0 || width <= 0 || col_lo < 0 || col_hi <= col_lo || col_hi > width || wmax < col_hi - col_lo || !color || !depth || !occ || !out)
-        return fail(LIDARGS_ERR_INVALID_ARGUMENT, "wedge_pack_columns: bad argument%s");
-    lg::launch_wedge_pack_columns(height, width, col_lo, col_hi, wmax, color, depth, occ, out, (hipStream_t)stream);
-    return check_launch((hipStream_t)stream, 0, "wedge pack columns");
-}
-int lidargs_wedge_unpack_columns(int G, int height, int width, int wmax, size_t block_stride, const int* edges_host, const float* blocks,
-                                 float* color, float* depth, float* occ, void* stream) {
-    if (G < 1 || G > 64 || height <= 0 || width <= 0 || wmax <= 0 || !edges_host || !blocks || !color || !depth || !occ || block_stride < (size_t)4 * height * wmax)
-        return fail(LIDARGS_ERR_INVALID_ARGUMENT, "wedge_unpack_columns: bad argument%s");
-    if (edges_host[0] != 0 || edges_host[G] != width) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "wedge_unpack_columns: edges must run from 0 to width%s");
-    for (int g = 0; g < G; g++)
-        if (edges_host[g + 1] <= edges_host[g] || edges_host[g + 1] - edges_host[g] > wmax) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "wedge_unpack_columns: bad edges%s");
-    lg::launch_wedge_unpack_columns(G, height, width, wmax, block_stride, edges_host, blocks, color, depth, occ, (hipStream_t)stream);
-    return check_launch((hipStream_t)stream, 0, "wedge unpack columns");
-}
-int lidargs_wedge_unpack_grad_rows_add(int n, const float* rows, int P, float* dense, void* stream) {
-    if (n < 0 || P < 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "wedge_unpack_grad_rows_add: bad sizes%s");
-    if (P == 0) return 0;
-    if (!dense || (n > 0 && !rows)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "wedge_unpack_grad_rows_add: NULL pointer%s");
-    LG_HIP(hipMemsetAsync(dense, 0, sizeof(float) * 17 * (size_t)P, (hipStream_t)stream));
-    if (n) lg::launch_shell_unpack_rows_add(n, rows, P, dense, (hipStream_t)stream);
-    return check_launch((hipStream_t)stream, 0, "wedge unpack rows");
+                         dL_dscale, dL_drot, debug, (hipStream_t)stream);
 }
 
 int lidargs_render_shell(int P, int R, const float* background, int width, int height, char* geom_buffer, char* binning_buffer,
@@ -976,8 +939,10 @@ int lidargs_backward_shell(int P, int R, const float* background, int width, int
                            float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_ddepths,
                            float* dL_dmean3D, float* dL_dsphere_means3D, float* dL_dbasis_u1, float* dL_dbasis_u2,
                            float* dL_dcov3D, float* dL_dscale, float* dL_drot, int debug, void* stream) {
+    BackMode mode;
+    mode.is_shell = true; mode.behind = behind; mode.T_final_global = T_final_global;
     return backward_impl(P, R, background, width, height, means3D, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
-                         viewmatrix, beam_inclinations, radii, geom_buffer, binning_buffer, image_buffer, behind, T_final_global, 1,
+                         viewmatrix, beam_inclinations, radii, geom_buffer, binning_buffer, image_buffer, mode,
                          dL_dpix, dL_dout_depth, dL_dout_occ, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_ddepths, dL_dmean3D,
                          dL_dsphere_means3D, dL_dbasis_u1, dL_dbasis_u2, dL_dcov3D, dL_dscale, dL_drot, debug, (hipStream_t)stream);
 }
@@ -1065,276 +1030,6 @@ int lidargs_last_counters(long long* out, int n) {
     int k = 0;
     for (; k < n && k < 10; k++) out[k] = g_counters[k];
     return k;
-}
-
-size_t lidargs_shell_select_scratch_bytes(int P) {
-    const size_t n = P > 0 ? (size_t)P : 1;
-    return sizeof(uint32_t) * (2 * n + lg::scan_scratch_words(n) + 64) + 256;
-}
-
-// Two steps, so that the caller can allocate exactly M output rows per frame (the selection a forward saves for its backward must
-// not be overwritten by the next forward's): count = flags + scan + the one host read; gather = the dense copies.
-int lidargs_shell_select_count(int P, const float* means3D, const float* viewmatrix, float shell_lo, float shell_hi, char* scratch,
-                               size_t scratch_bytes, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (P < 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "shell_select: P < 0%s");
-    if (P == 0) return 0;
-    if (!means3D || !viewmatrix || !scratch) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "shell_select: NULL pointer%s");
-    return select_count(P, scratch, scratch_bytes, "shell_select: scratch too small%s", stream, [&](uint32_t* flags) {
-        lg::launch_shell_flags(P, means3D, viewmatrix, shell_lo, shell_hi, flags, stream);
-    });
-}
-
-int lidargs_wedge_select_count(int P, const float* means3D, const float* scales, const float* rotations, float scale_modifier,
-                               const float* viewmatrix, int width, int col_lo, int col_hi, char* scratch, size_t scratch_bytes, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (P < 0 || width <= 0 || col_lo < 0 || col_hi <= col_lo) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "wedge_select: bad sizes%s");
-    if (P == 0) return 0;
-    if (!means3D || !viewmatrix || !scratch) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "wedge_select: NULL pointer%s");
-    return select_count(P, scratch, scratch_bytes, "wedge_select: scratch too small%s", stream, [&](uint32_t* flags) {
-        lg::launch_wedge_flags(P, means3D, scales, rotations, scale_modifier, viewmatrix, width, col_lo, col_hi, flags, stream);
-    });
-}
-
-int lidargs_shell_select_gather(int P, const float* means3D, const float* colors, const float* opacities, const float* scales,
-                                const float* rotations, int* idx_out, float* out_means3D, float* out_colors, float* out_opacities,
-                                float* out_scales, float* out_rotations, char* scratch, size_t scratch_bytes, int chunk_rows, int world,
-                                float* chunk_counts, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (P < 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "shell_select: P < 0%s");
-    if (chunk_counts && (chunk_rows <= 0 || world <= 0 || world > 256)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "shell_select: chunk counts need chunk_rows > 0 and 1 <= world <= 256%s");
-    if (P == 0) {
-        if (chunk_counts) LG_HIP(hipMemsetAsync(chunk_counts, 0, sizeof(float) * (size_t)world, stream));
-        return 0;
-    }
-    if (!means3D || !colors || !opacities || !scales || !rotations || !idx_out || !out_means3D || !out_colors || !out_opacities ||
-        !out_scales || !out_rotations || !scratch)
-        return fail(LIDARGS_ERR_INVALID_ARGUMENT, "shell_select: NULL pointer%s");
-    if (scratch_bytes < lidargs_shell_select_scratch_bytes(P)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "shell_select: scratch too small%s");
-    lg::Carver c(scratch);
-    uint32_t* flags = c.take<uint32_t>((size_t)P);
-    uint32_t* offs = c.take<uint32_t>((size_t)P);
-    uint32_t* total = c.take<uint32_t>(64);                            // (left there by the count step)
-    lg::launch_shell_gather(P, flags, offs, means3D, colors, opacities, scales, rotations, idx_out, out_means3D, out_colors, out_opacities,
-                            out_scales, out_rotations, stream, 0xFFFFFFFFu, total, nullptr, chunk_rows, world, chunk_counts);
-    return check_launch(stream, 0, "shell select gather");
-}
-
-int lidargs_shell_select_enqueue(int P, const float* means3D, const float* colors, const float* opacities, const float* scales,
-                                 const float* rotations, const float* viewmatrix, float shell_lo, float shell_hi, int capacity, int* idx_out,
-                                 float* out_means3D, float* out_colors, float* out_opacities, float* out_scales, float* out_rotations,
-                                 unsigned* n_valid_dev, unsigned* status_host, char* scratch, size_t scratch_bytes, int chunk_rows, int world,
-                                 float* chunk_counts, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (P <= 0 || capacity <= 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "shell_select_enqueue: P and capacity must be positive%s");
-    if (!means3D || !colors || !opacities || !scales || !rotations || !viewmatrix || !idx_out || !out_means3D || !out_colors || !out_opacities ||
-        !out_scales || !out_rotations || !n_valid_dev || !scratch)
-        return fail(LIDARGS_ERR_INVALID_ARGUMENT, "shell_select_enqueue: NULL pointer%s");
-    return select_enqueue(P, means3D, colors, opacities, scales, rotations, capacity, idx_out, out_means3D, out_colors, out_opacities, out_scales,
-                          out_rotations, n_valid_dev, status_host, scratch, scratch_bytes, "shell_select_enqueue: scratch too small%s", chunk_rows,
-                          world, chunk_counts, stream, [&](uint32_t* flags) {
-                              lg::launch_shell_flags(P, means3D, viewmatrix, shell_lo, shell_hi, flags, stream);
-                          });
-}
-
-int lidargs_wedge_select_enqueue(int P, const float* means3D, const float* colors, const float* opacities, const float* scales,
-                                 const float* rotations, float scale_modifier, const float* viewmatrix, int width, int col_lo, int col_hi,
-                                 int capacity, int* idx_out, float* out_means3D, float* out_colors, float* out_opacities, float* out_scales,
-                                 float* out_rotations, unsigned* n_valid_dev, unsigned* status_host, char* scratch, size_t scratch_bytes,
-                                 int chunk_rows, int world, float* chunk_counts, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (P <= 0 || capacity <= 0 || width <= 0 || col_lo < 0 || col_hi <= col_lo) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "wedge_select_enqueue: bad sizes%s");
-    if (!means3D || !colors || !opacities || !scales || !rotations || !viewmatrix || !idx_out || !out_means3D || !out_colors || !out_opacities ||
-        !out_scales || !out_rotations || !n_valid_dev || !scratch)
-        return fail(LIDARGS_ERR_INVALID_ARGUMENT, "wedge_select_enqueue: NULL pointer%s");
-    return select_enqueue(P, means3D, colors, opacities, scales, rotations, capacity, idx_out, out_means3D, out_colors, out_opacities, out_scales,
-                          out_rotations, n_valid_dev, status_host, scratch, scratch_bytes, "wedge_select_enqueue: scratch too small%s", chunk_rows,
-                          world, chunk_counts, stream, [&](uint32_t* flags) {
-                              lg::launch_wedge_flags(P, means3D, scales, rotations, scale_modifier, viewmatrix, width, col_lo, col_hi, flags, stream);
-                          });
-}
-
-namespace {
-// the one-launch selection (preprocess.hip k_select_fused) into `capacity` rows; fill_tail: idx_out's tail = 0x7F7F7F7F (enqueue-only frames:
-// the array stays ascending and every consumer skips indices >= P); wait: read the two counts back and return the rows gathered
-int select_fused(bool wedge, lg::SelArgs a, int capacity, unsigned* n_valid_dev, unsigned* status_host, char* scratch, size_t scratch_bytes,
-                 bool fill_tail, bool wait, hipStream_t stream) {
-    if (a.chunk_counts && (a.chunk_rows <= 0 || a.world <= 0 || a.world > 256)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "select: chunk counts need chunk_rows > 0 and 1 <= world <= 256%s");
-    if (scratch_bytes < lidargs_shell_select_scratch_bytes(a.P)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "select: scratch too small%s");
-    lg::Carver c(scratch);
-    const size_t words = lg::select_fused_words((size_t)a.P);
-    uint32_t* z = c.take<uint32_t>(words + 2);
-    a.ticket = z; a.status = reinterpret_cast<unsigned long long*>(z + 2);       // (128-byte aligned base: the 64-bit words are 8-byte aligned)
-    a.cap = (uint32_t)capacity; a.n_valid_out = n_valid_dev;
-    LG_HIP(hipMemsetAsync(z, 0, sizeof(uint32_t) * (words + 2), stream));
-    if (fill_tail) LG_HIP(hipMemsetAsync(a.idx_out, 0x7F, sizeof(int) * (size_t)capacity, stream));
-    if (a.chunk_counts) LG_HIP(hipMemsetAsync(a.chunk_counts, 0, sizeof(float) * (size_t)a.world, stream));
-    lg::launch_select_fused(a, wedge, stream);
-    if (status_host) LG_HIP(hipMemcpyAsync(status_host, n_valid_dev, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, stream));
-    const int rc = check_launch(stream, 0, "select (one launch)");
-    if (rc || !wait) return rc;
-    uint32_t h[2] = {0, 0};
-    LG_HIP((hipError_t)lg::api_read_words_zero_behind(n_valid_dev, 2, h, nullptr, 0, stream));
-    return (int)h[0];
-}
-lg::SelArgs sel_args(int P, const float* means3D, const float* colors, const float* opacities, const float* scales, const float* rotations, const float* viewmatrix,
-                     int* idx_out, float* out_means3D, float* out_colors, float* out_opacities, float* out_scales, float* out_rotations, int chunk_rows, int world,
-                     float* chunk_counts) {
-    lg::SelArgs a = lg::SelArgs();
-    a.P = P; a.means = means3D; a.colors = colors; a.opac = opacities; a.scales = scales; a.rot = rotations; a.vm = viewmatrix;
-    a.idx_out = idx_out; a.o_means = out_means3D; a.o_colors = out_colors; a.o_opac = out_opacities; a.o_scales = out_scales; a.o_rot = out_rotations;
-    a.chunk_rows = chunk_rows; a.world = world; a.chunk_counts = chunk_counts;
-    return a;
-}
-void sel_wedge(lg::SelArgs& a, float scale_modifier, int width, int col_lo, int col_hi) {
-    const float pi_f = 3.14159265358979323846f, step = 2 * pi_f / (float)width;       // as launch_wedge_flags
-    a.mod = scale_modifier; a.inv_col_step = 1.f / step; a.inv_tan_step = 1.f / tanf(step); a.col_lo = (float)col_lo; a.col_hi = (float)col_hi;
-}
-}  // namespace
-
-// Round 6 experiment (round-5 verdict item 4a), NOT the default: the selection of an ordinary frame in ONE launch (k_select_fused: test, scan in
-// index order by decoupled look-back over the blocks, gather) into `capacity` rows (the caller passes P-row arrays), then the one host read the
-// two-step form makes as well; returns the rows gathered M.  Bit-identical to the two-step form (tests/test_dist_gpu.py) and no faster:
-// 215-247 us against 88 + 38 + 78 us at 8 M Gaussians (EXPERIMENTS.md).
-int lidargs_shell_select_sync(int P, const float* means3D, const float* colors, const float* opacities, const float* scales, const float* rotations,
-                              const float* viewmatrix, float shell_lo, float shell_hi, int capacity, int* idx_out, float* out_means3D, float* out_colors,
-                              float* out_opacities, float* out_scales, float* out_rotations, unsigned* n_valid_dev, char* scratch, size_t scratch_bytes,
-                              int chunk_rows, int world, float* chunk_counts, void* stream_) {
-    if (P < 0 || capacity < 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "shell_select_sync: bad sizes%s");
-    if (P == 0 || capacity == 0) {
-        if (chunk_counts && world > 0) LG_HIP(hipMemsetAsync(chunk_counts, 0, sizeof(float) * (size_t)world, (hipStream_t)stream_));
-        return 0;
-    }
-    if (!means3D || !colors || !opacities || !scales || !rotations || !viewmatrix || !idx_out || !out_means3D || !out_colors || !out_opacities ||
-        !out_scales || !out_rotations || !n_valid_dev || !scratch)
-        return fail(LIDARGS_ERR_INVALID_ARGUMENT, "shell_select_sync: NULL pointer%s");
-    lg::SelArgs a = sel_args(P, means3D, colors, opacities, scales, rotations, viewmatrix, idx_out, out_means3D, out_colors, out_opacities, out_scales, out_rotations,
-                             chunk_rows, world, chunk_counts);
-    a.lo = shell_lo; a.hi = shell_hi;
-    return select_fused(false, a, capacity, n_valid_dev, nullptr, scratch, scratch_bytes, false, true, (hipStream_t)stream_);
-}
-int lidargs_wedge_select_sync(int P, const float* means3D, const float* colors, const float* opacities, const float* scales, const float* rotations,
-                              float scale_modifier, const float* viewmatrix, int width, int col_lo, int col_hi, int capacity, int* idx_out, float* out_means3D,
-                              float* out_colors, float* out_opacities, float* out_scales, float* out_rotations, unsigned* n_valid_dev, char* scratch,
-                              size_t scratch_bytes, int chunk_rows, int world, float* chunk_counts, void* stream_) {
-    if (P < 0 || capacity < 0 || width <= 0 || col_lo < 0 || col_hi <= col_lo) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "wedge_select_sync: bad sizes%s");
-    if (P == 0 || capacity == 0) {
-        if (chunk_counts && world > 0) LG_HIP(hipMemsetAsync(chunk_counts, 0, sizeof(float) * (size_t)world, (hipStream_t)stream_));
-        return 0;
-    }
-    if (!means3D || !colors || !opacities || !scales || !rotations || !viewmatrix || !idx_out || !out_means3D || !out_colors || !out_opacities ||
-        !out_scales || !out_rotations || !n_valid_dev || !scratch)
-        return fail(LIDARGS_ERR_INVALID_ARGUMENT, "wedge_select_sync: NULL pointer%s");
-    lg::SelArgs a = sel_args(P, means3D, colors, opacities, scales, rotations, viewmatrix, idx_out, out_means3D, out_colors, out_opacities, out_scales, out_rotations,
-                             chunk_rows, world, chunk_counts);
-    sel_wedge(a, scale_modifier, width, col_lo, col_hi);
-    return select_fused(true, a, capacity, n_valid_dev, nullptr, scratch, scratch_bytes, false, true, (hipStream_t)stream_);
-}
-
-// both steps in one call, into P-row arrays
-int lidargs_shell_select(int P, const float* means3D, const float* colors, const float* opacities, const float* scales, const float* rotations,
-                         const float* viewmatrix, float shell_lo, float shell_hi, int* idx_out, float* out_means3D, float* out_colors,
-                         float* out_opacities, float* out_scales, float* out_rotations, char* scratch, size_t scratch_bytes, void* stream_) {
-    const int M = lidargs_shell_select_count(P, means3D, viewmatrix, shell_lo, shell_hi, scratch, scratch_bytes, stream_);
-    if (M <= 0) return M;
-    const int rc = lidargs_shell_select_gather(P, means3D, colors, opacities, scales, rotations, idx_out, out_means3D, out_colors, out_opacities,
-                                               out_scales, out_rotations, scratch, scratch_bytes, 0, 0, nullptr, stream_);
-    return rc < 0 ? rc : M;
-}
-
-int lidargs_shell_pack_grad_rows(int M, const float* dL_dmeans3D, const float* dL_dmeans2D, const float* dL_dcolors, const float* dL_dopacity,
-                                 const float* dL_dscales, const float* dL_drotations, const int* idx, float* rows, void* stream) {
-    if (M < 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "shell_pack_grad_rows: M < 0%s");
-    if (M == 0) return 0;
-    if (!dL_dmeans3D || !dL_dmeans2D || !dL_dcolors || !dL_dopacity || !dL_dscales || !dL_drotations || !idx || !rows)
-        return fail(LIDARGS_ERR_INVALID_ARGUMENT, "shell_pack_grad_rows: NULL pointer%s");
-    lg::launch_shell_pack_rows(M, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, idx, rows, (hipStream_t)stream);
-    return check_launch((hipStream_t)stream, 0, "shell pack rows");
-}
-int lidargs_shell_unpack_grad_rows(int n, const float* rows, int P, float* dense, int blocked, void* stream) {
-    if (n < 0 || P < 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "shell_unpack_grad_rows: bad sizes%s");
-    if (P == 0) return 0;
-    if (!dense || (n > 0 && !rows)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "shell_unpack_grad_rows: NULL pointer%s");
-    LG_HIP(hipMemsetAsync(dense, 0, sizeof(float) * 17 * (size_t)P, (hipStream_t)stream));
-    if (n) lg::launch_shell_unpack_rows(n, rows, P, dense, blocked, (hipStream_t)stream);
-    return check_launch((hipStream_t)stream, 0, "shell unpack rows");
-}
-// Round 6: the gradient exchange ships only the rows that carry a gradient (preprocess.hip k_shell_pack_rows_live).  Step 1 counts them per
-// destination chunk into counts_dev u32[world] (zeroed here) and copies the counts to counts_host (waits: the all-to-all's split sizes are
-// host numbers); step 2 writes exactly sum(counts) rows of 18 floats, grouped by destination in ascending chunk order (cursor u32[world] is
-// scratch, zeroed here).  Returns the number of live rows (step 1) / 0 (step 2).
-int lidargs_shell_pack_grad_rows_live_count(int M, const float* dL_dmeans3D, const float* dL_dmeans2D, const float* dL_dcolors, const float* dL_dopacity,
-                                            const float* dL_dscales, const float* dL_drotations, const int* idx, int P, int chunk_rows, int world,
-                                            unsigned* counts_dev, unsigned* counts_host, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (M < 0 || P < 0 || chunk_rows <= 0 || world <= 0 || world > 256 || !counts_dev) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "shell_pack_grad_rows_live_count: bad arguments%s");
-    LG_HIP(hipMemsetAsync(counts_dev, 0, sizeof(unsigned) * (size_t)world, stream));
-    if (M > 0) {
-        if (!dL_dmeans3D || !dL_dmeans2D || !dL_dcolors || !dL_dopacity || !dL_dscales || !dL_drotations || !idx)
-            return fail(LIDARGS_ERR_INVALID_ARGUMENT, "shell_pack_grad_rows_live_count: NULL pointer%s");
-        lg::launch_shell_pack_rows_live(false, M, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, idx, P, chunk_rows, world, counts_dev, nullptr,
-                                        nullptr, stream);
-    }
-    if (!counts_host) return check_launch(stream, 0, "shell pack rows (live count)");      // the counts stay on the device (the caller gathers every rank's and reads them once)
-    LG_HIP((hipError_t)lg::api_read_words_zero_behind(counts_dev, world, counts_host, nullptr, 0, stream));
-    long long tot = 0;
-    for (int d = 0; d < world; d++) tot += counts_host[d];
-    return (int)tot;
-}
-int lidargs_shell_pack_grad_rows_live(int M, const float* dL_dmeans3D, const float* dL_dmeans2D, const float* dL_dcolors, const float* dL_dopacity,
-                                      const float* dL_dscales, const float* dL_drotations, const int* idx, int P, int chunk_rows, int world,
-                                      unsigned* counts_dev, unsigned* cursor_dev, float* rows, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (M < 0 || P < 0 || chunk_rows <= 0 || world <= 0 || world > 256 || !counts_dev || !cursor_dev) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "shell_pack_grad_rows_live: bad arguments%s");
-    if (M == 0) return 0;
-    if (!dL_dmeans3D || !dL_dmeans2D || !dL_dcolors || !dL_dopacity || !dL_dscales || !dL_drotations || !idx || !rows)
-        return fail(LIDARGS_ERR_INVALID_ARGUMENT, "shell_pack_grad_rows_live: NULL pointer%s");
-    LG_HIP(hipMemsetAsync(cursor_dev, 0, sizeof(unsigned) * (size_t)world, stream));
-    lg::launch_shell_pack_rows_live(true, M, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, idx, P, chunk_rows, world, counts_dev, cursor_dev,
-                                    rows, stream);
-    return check_launch(stream, 0, "shell pack rows (live)");
-}
-
-// Round 6, gradient mode "shard": the rows a rank received for its OWN index chunk [base, base + chunk_rows), unpacked into a
-// [17][chunk_rows] block (six contiguous gradient blocks of chunk_rows rows each) -- no dense [P, 17] block is zero-filled or scattered into
-// (544 MB + 20 M scattered words per frame at 8 M Gaussians).  add != 0: rows of equal index are added (column wedges).
-int lidargs_shell_unpack_grad_rows_chunk(int n, const float* rows, int base, int chunk_rows, float* dense, int add, void* stream) {
-    if (n < 0 || base < 0 || chunk_rows < 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "shell_unpack_grad_rows_chunk: bad sizes%s");
-    if (chunk_rows == 0) return 0;
-    if (!dense || (n > 0 && !rows)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "shell_unpack_grad_rows_chunk: NULL pointer%s");
-    LG_HIP(hipMemsetAsync(dense, 0, sizeof(float) * 17 * (size_t)chunk_rows, (hipStream_t)stream));
-    if (n) {
-        if (add) lg::launch_shell_unpack_rows_add(n, rows, chunk_rows, dense, (hipStream_t)stream, base);
-        else lg::launch_shell_unpack_rows(n, rows, chunk_rows, dense, 1, (hipStream_t)stream, base);
-    }
-    return check_launch((hipStream_t)stream, 0, "shell unpack rows (chunk)");
-}
-int lidargs_shell_chunk_counts(int M, const int* idx, int chunk_rows, int world, float* counts, void* stream) {
-    if (M < 0 || chunk_rows <= 0 || world <= 0 || !counts || (M > 0 && !idx)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "shell_chunk_counts: bad arguments%s");
-    lg::launch_shell_chunk_counts(M, idx, chunk_rows, world, counts, (hipStream_t)stream);
-    return check_launch((hipStream_t)stream, 0, "shell chunk counts");
-}
-int lidargs_shell_scatter_radii(int M, const int* idx, const int* radii_shell, int P, int* radii, void* stream) {
-    if (M < 0 || P < 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "shell_scatter_radii: bad sizes%s");
-    if (P == 0) return 0;
-    if (!radii || (M > 0 && (!idx || !radii_shell))) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "shell_scatter_radii: NULL pointer%s");
-    LG_HIP(hipMemsetAsync(radii, 0, sizeof(int) * (size_t)P, (hipStream_t)stream));
-    if (M) lg::launch_shell_scatter_i32(M, idx, radii_shell, P, radii, (hipStream_t)stream);
-    return check_launch((hipStream_t)stream, 0, "shell scatter radii");
-}
-
-int lidargs_shell_transmittance(int G, int rank, int N, size_t row_stride, const float* all_T, float* T_in, void* stream_) {
-    if (G < 1 || rank < 0 || rank >= G || N < 0 || row_stride < (size_t)N || !all_T || !T_in) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "shell_transmittance: bad argument%s");
-    if (N) lg::launch_shell_transmittance(G, rank, N, row_stride, all_T, T_in, (hipStream_t)stream_);
-    return 0;
-}
-
-int lidargs_shell_compose(int G, int rank, int N, const float* planes, const float* background, float* out_color, float* out_depth,
-                          float* out_occ, float* T_final, float* behind, void* stream_) {
-    if (G < 1 || rank < 0 || rank >= G || N < 0 || !planes || !out_color || !out_depth || !out_occ || !T_final || !behind)
-        return fail(LIDARGS_ERR_INVALID_ARGUMENT, "shell_compose: bad argument%s");
-    if (N) lg::launch_shell_compose(G, rank, N, planes, background, out_color, out_depth, out_occ, T_final, behind, (hipStream_t)stream_);
-    return 0;
 }
 
 }  // extern "C"

@@ -4,6 +4,7 @@
 //   k_preprocess        K1 (R3/cr/forward.cu:256-384) and, with FILTER, K2 (:388-497)
 //   k_mark_visible      K11 (R3/cr/rasterizer_impl.cu:54-66)
 //   k_gaussian_backward K9 + K10 fused (R3/cr/backward.cu:157-382, :453-532, :385-448)
+//   k_zero_touched / k_touch_visible   the touched-Gaussian lists the backward starts from
 //
 // All of them are one-thread-per-Gaussian HBM streams: 44 B in, <= 100 B out per Gaussian for
 // preprocess.  The arithmetic is a re-derivation (vector form), not a transcription: the
@@ -11,6 +12,7 @@
 // t_i^T Sigma t_j with t_i = Rv^T u_i the world-space tangent directions (two symmetric
 // mat-vecs and three dots), and the backward is written as vector-Jacobian products.
 #include "lidargs_common.h"
+#include "selection.h"
 #include <algorithm>
 
 namespace lg {
@@ -154,12 +156,10 @@ __global__ void __launch_bounds__(256) k_preprocess(const PreKernelArgs a) {
         if (!row_exists) break;
         const float3 pw = f3(a.means3D[3 * idx], a.means3D[3 * idx + 1], a.means3D[3 * idx + 2]);
         const float* vm = pp.view;
-        const float3 p = f3(vm[0] * pw.x + vm[4] * pw.y + vm[8] * pw.z + vm[12],
-                            vm[1] * pw.x + vm[5] * pw.y + vm[9] * pw.z + vm[13],
-                            vm[2] * pw.x + vm[6] * pw.y + vm[10] * pw.z + vm[14]);
-        const float dist = sqrtf(p.x * p.x + p.y * p.y + p.z * p.z);
+        const float3 p = view_point(vm, pw);
+        const float dist = range_of(p);
         if (dist >= pp.far_f || dist <= pp.near_f) break;            // R3/cr/forward.cu:304
-        if (!(dist >= pp.shell_lo && dist < pp.shell_hi)) break;     // range shell (multi-GPU only)
+        if (!in_shell(dist, pp.shell_lo, pp.shell_hi)) break;        // range shell (multi-GPU only): the selection's own test (selection.h)
         // every other input of a surviving Gaussian is requested here, together: the opacity and the colours are needed a thousand
         // instructions further down, where a load issued on the spot would be waited for
         const float op_in = FILTER ? 0.f : a.opacities[idx], col0_in = FILTER ? 0.f : a.colors[2 * idx], col1_in = FILTER ? 0.f : a.colors[2 * idx + 1];   // (K2 has neither)
@@ -694,431 +694,6 @@ void launch_touch_all(uint8_t* touched, const int* radii, size_t P, hipStream_t 
 void launch_gaussian_backward(const GaussBwdArgs& a, hipStream_t s) {
     const unsigned regions = (unsigned)((a.P + LG_REGION - 1) / LG_REGION);
     hipLaunchKernelGGL(k_gaussian_backward, dim3((regions + 3) / 4), dim3(256), 0, s, a);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Range-shell selection (multi-GPU): flag the Gaussians whose range lies in [lo, hi) with exactly the arithmetic
-// k_preprocess uses for its own shell test (same expression, same -ffp-contract=off file), then gather their
-// attributes into dense arrays in ascending index order.  The rank's whole frame then runs on P/N rows.
-__global__ void __launch_bounds__(256) k_shell_flags(int P, const float* __restrict__ means3D, const float* __restrict__ vm, float lo, float hi,
-                                                     uint32_t* __restrict__ flags) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= P) return;
-    const float3 pw = f3(means3D[3 * idx], means3D[3 * idx + 1], means3D[3 * idx + 2]);
-    const float3 p = f3(vm[0] * pw.x + vm[4] * pw.y + vm[8] * pw.z + vm[12],
-                        vm[1] * pw.x + vm[5] * pw.y + vm[9] * pw.z + vm[13],
-                        vm[2] * pw.x + vm[6] * pw.y + vm[10] * pw.z + vm[14]);
-    const float dist = sqrtf(p.x * p.x + p.y * p.y + p.z * p.z);
-    flags[idx] = (dist >= lo && dist < hi) ? 1u : 0u;
-}
-
-__global__ void __launch_bounds__(256) k_shell_gather(int P, const uint32_t* __restrict__ flags, const uint32_t* __restrict__ offs,
-                                                      const float* __restrict__ means3D, const float* __restrict__ colors,
-                                                      const float* __restrict__ opacities, const float* __restrict__ scales,
-                                                      const float* __restrict__ rotations, int* __restrict__ idx_out,
-                                                      float* __restrict__ o_means, float* __restrict__ o_colors, float* __restrict__ o_opac,
-                                                      float* __restrict__ o_scales, float* __restrict__ o_rot, uint32_t cap,
-                                                      const uint32_t* __restrict__ total, uint32_t* __restrict__ n_valid_out,
-                                                      int chunk_rows, int world, float* __restrict__ chunk_counts) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    // the gradient all-to-all's split sizes: selected rows whose index lies in chunk d = [d * chunk_rows, (d + 1) * chunk_rows), straight
-    // from the scan (offs[i] = selected rows in front of index i); exact as floats (< 2^24 rows per chunk)
-    if (chunk_counts && blockIdx.x == 0 && (int)threadIdx.x < world) {
-        const uint32_t t = *total, lim = t < cap ? t : cap;
-        auto before = [&](long long i) { const uint32_t v = i >= (long long)P ? t : offs[i]; return v < lim ? v : lim; };
-        const long long d = threadIdx.x;
-        chunk_counts[d] = (float)(before((d + 1) * chunk_rows) - before(d * chunk_rows));
-    }
-    // capacity-sized selection (enqueue-only rank frames): rows past `cap` are dropped, and the two status words say so --
-    // [0] rows gathered = min(selected, cap) (what k_preprocess takes as its n_valid), [1] rows selected
-    if (n_valid_out && idx == 0) { const uint32_t t = *total; n_valid_out[0] = t < cap ? t : cap; n_valid_out[1] = t; }
-    if (idx >= P || flags[idx] == 0u) return;
-    const size_t c = offs[idx];
-    if (c >= (size_t)cap) return;
-    idx_out[c] = idx;
-    for (int k = 0; k < 3; k++) { o_means[3 * c + k] = means3D[3 * (size_t)idx + k]; o_scales[3 * c + k] = scales[3 * (size_t)idx + k]; }
-    o_colors[2 * c] = colors[2 * (size_t)idx]; o_colors[2 * c + 1] = colors[2 * (size_t)idx + 1];
-    o_opac[c] = opacities[idx];
-    reinterpret_cast<float4*>(o_rot)[c] = reinterpret_cast<const float4*>(rotations)[idx];
-}
-
-// Column-wedge selection (multi-GPU): flag every Gaussian whose reference rect CAN reach pixel columns [col_lo, col_hi).  The exact
-// rect needs K1; this is a bound from above on its half-width, from the largest scale alone:
-//   every entry of the 2x2 footprint is <= A = (s_max^2 |q|^4 + 0.01) / range^2   (quaternion NOT normalised, R3/cr/forward.cu:228),
-//   lambda_max <= 2 A + sqrt(1e-9) (the floor of :328-330 included), radius = sqrt(lambda), rx = ceil(3 radius / tan(2 pi / W)) (:362),
-//   rect columns = [p_c - rx - 16, p_c + rx + 16) (R3/cr/auxiliary.h:80-92), + 2 pixels for atan2f rounding against K1's.
-// A Gaussian flagged here and found out of reach by K1 costs a preprocess row; one NOT flagged can reach no pixel of the wedge.
-__global__ void __launch_bounds__(256) k_wedge_flags(int P, const float* __restrict__ means3D, const float* __restrict__ scales,
-                                                     const float* __restrict__ rotations, float mod, const float* __restrict__ vm, float inv_col_step,
-                                                     float inv_tan_step, float col_lo, float col_hi, uint32_t* __restrict__ flags) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= P) return;
-    const float3 pw = f3(means3D[3 * idx], means3D[3 * idx + 1], means3D[3 * idx + 2]);
-    const float3 p = f3(vm[0] * pw.x + vm[4] * pw.y + vm[8] * pw.z + vm[12],
-                        vm[1] * pw.x + vm[5] * pw.y + vm[9] * pw.z + vm[13],
-                        vm[2] * pw.x + vm[6] * pw.y + vm[10] * pw.z + vm[14]);
-    const float d2 = p.x * p.x + p.y * p.y + p.z * p.z;
-    float smax = 0.f, nq = 1.f;
-    if (scales) smax = mod * fmaxf(fabsf(scales[3 * idx]), fmaxf(fabsf(scales[3 * idx + 1]), fabsf(scales[3 * idx + 2])));
-    if (rotations) {
-        const float4 q = reinterpret_cast<const float4*>(rotations)[idx];
-        nq = fmaxf(1.f, q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w);
-    }
-    const float A = (smax * smax * nq * nq * 1.0001f + 0.01f) / fmaxf(d2, 1e-12f);
-    const float rx = 3.f * sqrtf(2.f * A + 3.2e-5f) * inv_tan_step * 1.001f + 1.f;
-    const float pi_f = 3.14159265358979323846f;
-    const float p_c = (pi_f - atan2f(p.y, p.x)) * inv_col_step;
-    const float reach = rx + 18.f;
-    flags[idx] = (p_c + reach >= col_lo && p_c - reach < col_hi && d2 > 0.f) ? 1u : 0u;
-}
-void launch_wedge_flags(int P, const float* means3D, const float* scales, const float* rotations, float scale_modifier, const float* view,
-                        int W, int col_lo, int col_hi, uint32_t* flags, hipStream_t s) {
-    const float pi_f = 3.14159265358979323846f;
-    const float step = 2 * pi_f / (float)W;
-    hipLaunchKernelGGL(k_wedge_flags, dim3((P + 255) / 256), dim3(256), 0, s, P, means3D, scales, rotations, scale_modifier, view, 1.f / step,
-                       1.f / tanf(step), (float)col_lo, (float)col_hi, flags);
-}
-
-void launch_shell_flags(int P, const float* means3D, const float* view, float lo, float hi, uint32_t* flags, hipStream_t s) {
-    hipLaunchKernelGGL(k_shell_flags, dim3((P + 255) / 256), dim3(256), 0, s, P, means3D, view, lo, hi, flags);
-}
-void launch_shell_gather(int P, const uint32_t* flags, const uint32_t* offs, const float* means3D, const float* colors, const float* opacities,
-                         const float* scales, const float* rotations, int* idx_out, float* o_means, float* o_colors, float* o_opac,
-                         float* o_scales, float* o_rot, hipStream_t s, uint32_t cap, const uint32_t* total, uint32_t* n_valid_out,
-                         int chunk_rows, int world, float* chunk_counts) {
-    hipLaunchKernelGGL(k_shell_gather, dim3((P + 255) / 256), dim3(256), 0, s, P, flags, offs, means3D, colors, opacities, scales, rotations,
-                       idx_out, o_means, o_colors, o_opac, o_scales, o_rot, cap, total, n_valid_out, chunk_rows, world, chunk_counts);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Round 6: the selection in ONE launch (round-5 verdict item 4a).  flags -> scan (three launches over P) -> gather read every replicated
-// Gaussian's position twice and wrote / read 8 bytes of flags and offsets per Gaussian in between: 238 us of an 8 M-Gaussian wedge rank's
-// 0.90-ms frame.  Here a block tests 1024 consecutive Gaussians, scans its flags in index order (the selection stays ascending: equal
-// ranges break ties by index), learns the rows in front of it by decoupled look-back over the blocks before it (each block publishes its
-// count, then its inclusive prefix, in one 64-bit word; blocks take their number from a ticket so that a block only ever waits for blocks
-// that are already running), and writes the selected rows itself.  The block that finishes last writes the row counts and the gradient
-// all-to-all's split sizes (lower bounds on the ascending index array it can now read).
-template <bool WEDGE>
-__global__ void __launch_bounds__(256) k_select_fused(const SelArgs a) {
-    __shared__ uint32_t s_bid, s_cnt[SEL_ITEMS][4], s_base, s_total;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    if (tid == 0) s_bid = atomicAdd(a.ticket, 1u);
-    __syncthreads();
-    const unsigned b = s_bid;
-    const size_t base = (size_t)b * SEL_BLOCK;
-    const float* __restrict__ vm = a.vm;
-    bool f[SEL_ITEMS];
-    float3 pw[SEL_ITEMS];
-#pragma unroll
-    for (int j = 0; j < SEL_ITEMS; j++) {
-        const size_t idx = base + (size_t)j * 256 + tid;
-        f[j] = false; pw[j] = f3(0.f, 0.f, 0.f);
-        if (idx < (size_t)a.P) {
-            pw[j] = f3(a.means[3 * idx], a.means[3 * idx + 1], a.means[3 * idx + 2]);
-            const float3 p = f3(vm[0] * pw[j].x + vm[4] * pw[j].y + vm[8] * pw[j].z + vm[12],
-                                vm[1] * pw[j].x + vm[5] * pw[j].y + vm[9] * pw[j].z + vm[13],
-                                vm[2] * pw[j].x + vm[6] * pw[j].y + vm[10] * pw[j].z + vm[14]);
-            if (!WEDGE) {
-                const float dist = sqrtf(p.x * p.x + p.y * p.y + p.z * p.z);      // k_shell_flags' expression (and k_preprocess's)
-                f[j] = dist >= a.lo && dist < a.hi;
-            } else {                                                                // k_wedge_flags' bound
-                const float d2 = p.x * p.x + p.y * p.y + p.z * p.z;
-                const float smax = a.mod * fmaxf(fabsf(a.scales[3 * idx]), fmaxf(fabsf(a.scales[3 * idx + 1]), fabsf(a.scales[3 * idx + 2])));
-                const float4 q = reinterpret_cast<const float4*>(a.rot)[idx];
-                const float nq = fmaxf(1.f, q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w);
-                const float A = (smax * smax * nq * nq * 1.0001f + 0.01f) / fmaxf(d2, 1e-12f);
-                const float rx = 3.f * sqrtf(2.f * A + 3.2e-5f) * a.inv_tan_step * 1.001f + 1.f;
-                const float pi_f = 3.14159265358979323846f;
-                const float p_c = (pi_f - atan2f(p.y, p.x)) * a.inv_col_step;
-                const float reach = rx + 18.f;
-                f[j] = p_c + reach >= a.col_lo && p_c - reach < a.col_hi && d2 > 0.f;
-            }
-        }
-    }
-    // flags in index order inside the block: item-major (item j covers indices base + 256 j ..), then wave, then lane
-    uint32_t within[SEL_ITEMS];
-#pragma unroll
-    for (int j = 0; j < SEL_ITEMS; j++) {
-        const unsigned long long m = __ballot(f[j]);
-        within[j] = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-        if (lane == 0) s_cnt[j][w] = (uint32_t)__popcll(m);
-    }
-    __syncthreads();
-    // exclusive offsets of the 4 x SEL_ITEMS (item, wave) cells, in index order, by the first wave (one cell per lane: SEL_ITEMS * 4 <= 64)
-    static_assert(SEL_ITEMS * 4 <= 64, "one cell per lane");
-    if (w == 0) {
-        const uint32_t c = lane < SEL_ITEMS * 4 ? (&s_cnt[0][0])[lane] : 0u;
-        uint32_t incl = c;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const uint32_t v = __shfl_up(incl, o); if (lane >= o) incl += v; }
-        if (lane < SEL_ITEMS * 4) (&s_cnt[0][0])[lane] = incl - c;
-        if (lane == 63) s_total = incl;
-    }
-    __syncthreads();
-    const uint32_t total = s_total;
-    uint32_t off[SEL_ITEMS];
-#pragma unroll
-    for (int j = 0; j < SEL_ITEMS; j++) off[j] = s_cnt[j][w];
-    if (w == 0) {
-        // decoupled look-back by one WAVE: lane l reads the word of block p - l; the nearest block that already knows its inclusive prefix ends
-        // the walk, the aggregates of the blocks in front of it are added.  (One thread walking word by word waited a full memory round trip
-        // per predecessor: 8 k blocks looked back one after the other -- 5 ms for a 0.2-ms job.)
-        uint32_t excl = 0;
-        if (b > 0) {
-            if (lane == 0) __hip_atomic_store(a.status + b, (1ull << 32) | total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            long long p = (long long)b - 1;                            // the nearest block not yet accounted for
-            for (;;) {
-                const long long mine = p - lane;
-                unsigned long long v = 2ull << 32;                    // in front of block 0: an inclusive prefix of 0
-                if (mine >= 0) v = __hip_atomic_load(a.status + mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const unsigned long long empty = __ballot((v >> 32) == 0ull);
-                const unsigned long long pref = __ballot((v >> 32) == 2ull);
-                // usable lanes: those nearer than the first empty one; among them the nearest prefix ends the walk
-                const int first_empty = empty ? __builtin_ctzll(empty) : 64;
-                const int first_pref = pref ? __builtin_ctzll(pref) : 64;
-                const int upto = first_pref < first_empty ? first_pref + 1 : first_empty;      // lanes [0, upto) are added
-                uint32_t add = lane < upto ? (uint32_t)v : 0u;
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) add += __shfl_xor(add, o);
-                excl += add;
-                if (first_pref < first_empty) break;
-                p -= upto;
-                if (upto == 0) __builtin_amdgcn_s_sleep(2);
-            }
-        }
-        if (lane == 0) {
-            __hip_atomic_store(a.status + b, (2ull << 32) | (unsigned long long)(excl + total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            s_base = excl;
-        }
-    }
-    __syncthreads();
-    const uint32_t blk = s_base;
-#pragma unroll
-    for (int j = 0; j < SEL_ITEMS; j++) {
-        if (!f[j]) continue;
-        const size_t idx = base + (size_t)j * 256 + tid;
-        const size_t c = (size_t)blk + off[j] + within[j];
-        if (c >= (size_t)a.cap) continue;
-        a.idx_out[c] = (int)idx;
-        a.o_means[3 * c] = pw[j].x; a.o_means[3 * c + 1] = pw[j].y; a.o_means[3 * c + 2] = pw[j].z;
-        for (int k = 0; k < 3; k++) a.o_scales[3 * c + k] = a.scales[3 * idx + k];
-        reinterpret_cast<float2*>(a.o_colors)[c] = reinterpret_cast<const float2*>(a.colors)[idx];
-        a.o_opac[c] = a.opac[idx];
-        reinterpret_cast<float4*>(a.o_rot)[c] = reinterpret_cast<const float4*>(a.rot)[idx];
-    }
-    // Row counts and the gradient all-to-all's split sizes, without reading another block's rows (no fence anywhere in this launch: a
-    // word of the look-back carries its own data, relaxed 64-bit atomics suffice -- with release / acquire every block wrote the L2 back
-    // and the 8 k blocks of an 8 M-Gaussian frame went through one after the other, 2.2 ms).  counts[d] = before((d + 1) chunk) - before(d chunk)
-    // with before(i) = selected rows with index < i, clamped at the capacity: the block that holds index i adds +before(i) to counts[d - 1]
-    // and -before(i) to counts[d] (float atomics on integers < 2^24: exact, any order; zeroed by the caller); the block that holds the last
-    // index adds the total.
-    const bool last_block = base + SEL_BLOCK >= (size_t)a.P;
-    if (a.chunk_counts) {
-        for (int d = 1; d < a.world; d++) {
-            const long long i_d = (long long)d * a.chunk_rows;
-            if (i_d < (long long)base || i_d >= (long long)base + SEL_BLOCK || i_d >= (long long)a.P) continue;     // (block-uniform)
-            uint32_t c = 0;
-#pragma unroll
-            for (int j = 0; j < SEL_ITEMS; j++) c += (f[j] && (long long)(base + (size_t)j * 256 + tid) < i_d) ? 1u : 0u;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
-            __syncthreads();
-            if (lane == 0) s_cnt[0][w] = c;
-            __syncthreads();
-            if (tid == 0) {
-                uint32_t v = blk + s_cnt[0][0] + s_cnt[0][1] + s_cnt[0][2] + s_cnt[0][3];
-                v = v < a.cap ? v : a.cap;
-                atomicAdd(a.chunk_counts + d - 1, (float)v); atomicAdd(a.chunk_counts + d, -(float)v);
-            }
-        }
-    }
-    if (last_block && tid == 0) {
-        const uint32_t t = blk + total, n = t < a.cap ? t : a.cap;
-        if (a.n_valid_out) { a.n_valid_out[0] = n; a.n_valid_out[1] = t; }
-        if (a.chunk_counts) {
-            // boundaries at or behind P see every selected row in front of them
-            for (int d = 1; d <= a.world; d++) {
-                const long long i_d = (long long)d * a.chunk_rows;
-                if (d < a.world && i_d < (long long)a.P) continue;
-                atomicAdd(a.chunk_counts + d - 1, (float)n);
-                if (d < a.world) atomicAdd(a.chunk_counts + d, -(float)n);
-            }
-        }
-    }
-}
-void launch_select_fused(SelArgs a, bool wedge, hipStream_t s) {
-    a.blocks = (unsigned)(((size_t)a.P + SEL_BLOCK - 1) / SEL_BLOCK);
-    if (wedge) hipLaunchKernelGGL(k_select_fused<true>, dim3(a.blocks), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(k_select_fused<false>, dim3(a.blocks), dim3(256), 0, s, a);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Gradient rows of a range shell (lidargs_dist step 6): the six returned gradients of the shell's M Gaussians + their global
-// index as one [M, 18] row block (what the all-to-all ships), and back: rows scattered by index into a dense [P, 17] block.
-// One launch each instead of a concatenate, casts, an index_copy and their temporaries.
-__global__ void __launch_bounds__(256) k_shell_pack_rows(int M, const float* __restrict__ g_m3, const float* __restrict__ g_m2,
-                                                         const float* __restrict__ g_col, const float* __restrict__ g_op,
-                                                         const float* __restrict__ g_sc, const float* __restrict__ g_rot,
-                                                         const int* __restrict__ idx, float* __restrict__ rows) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= M) return;
-    float* r = rows + 18 * (size_t)i;
-    r[0] = g_m3[3 * (size_t)i]; r[1] = g_m3[3 * (size_t)i + 1]; r[2] = g_m3[3 * (size_t)i + 2];
-    const float4 m2 = reinterpret_cast<const float4*>(g_m2)[i];
-    r[3] = m2.x; r[4] = m2.y; r[5] = m2.z; r[6] = m2.w;
-    const float2 c = reinterpret_cast<const float2*>(g_col)[i];
-    r[7] = c.x; r[8] = c.y;
-    r[9] = g_op[i];
-    r[10] = g_sc[3 * (size_t)i]; r[11] = g_sc[3 * (size_t)i + 1]; r[12] = g_sc[3 * (size_t)i + 2];
-    const float4 q = reinterpret_cast<const float4*>(g_rot)[i];
-    r[13] = q.x; r[14] = q.y; r[15] = q.z; r[16] = q.w;
-    r[17] = __int_as_float(idx[i]);                                    // the index travels as a bit pattern
-}
-// Round 6: only the rows that carry a gradient travel.  A frame blends a fraction of the Gaussians a rank preprocesses (cfg4: 10 k of 8 M;
-// cfg3: a fifth) and every other row of the exchange is 72 bytes of zeros -- packed, shipped over xGMI, read and skipped.  Two launches
-// around one host read (the all-to-all's split sizes are host numbers anyway): count the rows with any non-zero gradient per destination
-// chunk, then write exactly those, grouped by destination (any order inside a group: the receiver scatters by index).
-__device__ __forceinline__ bool shell_row_live(const float* __restrict__ g_m3, const float* __restrict__ g_m2, const float* __restrict__ g_col, const float* __restrict__ g_op,
-                                               const float* __restrict__ g_sc, const float* __restrict__ g_rot, size_t i, float* r) {
-    r[0] = g_m3[3 * i]; r[1] = g_m3[3 * i + 1]; r[2] = g_m3[3 * i + 2];
-    const float4 m2 = reinterpret_cast<const float4*>(g_m2)[i];
-    r[3] = m2.x; r[4] = m2.y; r[5] = m2.z; r[6] = m2.w;
-    const float2 c = reinterpret_cast<const float2*>(g_col)[i];
-    r[7] = c.x; r[8] = c.y;
-    r[9] = g_op[i];
-    r[10] = g_sc[3 * i]; r[11] = g_sc[3 * i + 1]; r[12] = g_sc[3 * i + 2];
-    const float4 q = reinterpret_cast<const float4*>(g_rot)[i];
-    r[13] = q.x; r[14] = q.y; r[15] = q.z; r[16] = q.w;
-    bool live = false;
-#pragma unroll
-    for (int k = 0; k < 17; k++) live = live || (r[k] != 0.f);          // (a NaN is != 0: it travels)
-    return live;
-}
-// WRITE = false: counts[d] += live rows bound for chunk d.  WRITE = true: rows_out[prefix(counts)[d] + cursor[d]++] = the row.
-template <bool WRITE>
-__global__ void __launch_bounds__(256) k_shell_pack_rows_live(int M, const float* __restrict__ g_m3, const float* __restrict__ g_m2, const float* __restrict__ g_col,
-                                                              const float* __restrict__ g_op, const float* __restrict__ g_sc, const float* __restrict__ g_rot,
-                                                              const int* __restrict__ idx, int P, int chunk_rows, int world, uint32_t* __restrict__ counts,
-                                                              uint32_t* __restrict__ cursor, float* __restrict__ rows_out) {
-    __shared__ uint32_t s_base[256];
-    if (WRITE) {
-        // exclusive prefix of the counts (world <= 256): where each destination's group starts
-        const int t = threadIdx.x;
-        uint32_t v = t < world ? counts[t] : 0u, incl = v;
-        const int lane = t & 63;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const uint32_t u = __shfl_up(incl, o); if (lane >= o) incl += u; }
-        __shared__ uint32_t s_w[4];
-        if (lane == 63) s_w[t >> 6] = incl;
-        __syncthreads();
-        uint32_t off = 0;
-        for (int q = 0; q < (t >> 6); q++) off += s_w[q];
-        s_base[t] = off + incl - v;
-        __syncthreads();
-    }
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    float r[17];
-    int g = -1;
-    bool live = false;
-    if (i < M) {
-        g = idx[i];
-        if (g >= 0 && g < P) live = shell_row_live(g_m3, g_m2, g_col, g_op, g_sc, g_rot, (size_t)i, r);
-    }
-    const int d = live ? min(g / chunk_rows, world - 1) : -1;
-    // wave-aggregated per destination: the rows of a wave are index-ascending, so it sees one destination, rarely two
-    unsigned long long todo = __ballot(live);
-    const int lane = threadIdx.x & 63;
-    while (todo) {
-        const int leader = __builtin_ctzll(todo);
-        const int dl = __shfl(d, leader);
-        const unsigned long long same = __ballot(live && d == dl);
-        uint32_t pos = 0;
-        if (lane == leader) pos = atomicAdd((WRITE ? cursor : counts) + dl, (uint32_t)__builtin_popcountll(same));
-        pos = __shfl(pos, leader);
-        if (WRITE && live && d == dl) {
-            float* o = rows_out + 18 * ((size_t)s_base[dl] + pos + (uint32_t)__builtin_popcountll(same & ((1ull << lane) - 1ull)));
-#pragma unroll
-            for (int k = 0; k < 17; k++) o[k] = r[k];
-            o[17] = __int_as_float(g);
-        }
-        todo &= ~same;
-    }
-}
-void launch_shell_pack_rows_live(bool write, int M, const float* g_m3, const float* g_m2, const float* g_col, const float* g_op, const float* g_sc, const float* g_rot,
-                                 const int* idx, int P, int chunk_rows, int world, uint32_t* counts, uint32_t* cursor, float* rows_out, hipStream_t s) {
-    const dim3 grid((M + 255) / 256), block(256);
-    if (write) hipLaunchKernelGGL(k_shell_pack_rows_live<true>, grid, block, 0, s, M, g_m3, g_m2, g_col, g_op, g_sc, g_rot, idx, P, chunk_rows, world, counts, cursor, rows_out);
-    else hipLaunchKernelGGL(k_shell_pack_rows_live<false>, grid, block, 0, s, M, g_m3, g_m2, g_col, g_op, g_sc, g_rot, idx, P, chunk_rows, world, counts, cursor, rows_out);
-}
-// blocked != 0: dense is six contiguous blocks [P,3][P,4][P,2][P,1][P,3][P,4] (what autograd takes without a strided copy each)
-// base (round 6, the "shard" gradient mode): `dense` holds the rows [base, base + P) of the index space only -- a rank's own chunk
-__global__ void __launch_bounds__(256) k_shell_unpack_rows(int n, const float* __restrict__ rows, int P, float* __restrict__ dense, int blocked, int base) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float* r = rows + 18 * (size_t)i;
-    const int g = __float_as_int(r[17]) - base;
-    if (g < 0 || g >= P) return;
-    if (!blocked) {
-        float* d = dense + 17 * (size_t)g;
-#pragma unroll
-        for (int k = 0; k < 17; k++) d[k] = r[k];
-        return;
-    }
-    const size_t Ps = (size_t)P, gs = (size_t)g;
-    float* d = dense + 3 * gs;            d[0] = r[0]; d[1] = r[1]; d[2] = r[2];
-    d = dense + 3 * Ps + 4 * gs;          d[0] = r[3]; d[1] = r[4]; d[2] = r[5]; d[3] = r[6];
-    d = dense + 7 * Ps + 2 * gs;          d[0] = r[7]; d[1] = r[8];
-    dense[9 * Ps + gs] = r[9];
-    d = dense + 10 * Ps + 3 * gs;         d[0] = r[10]; d[1] = r[11]; d[2] = r[12];
-    d = dense + 13 * Ps + 4 * gs;         d[0] = r[13]; d[1] = r[14]; d[2] = r[15]; d[3] = r[16];
-}
-// Column wedges: a Gaussian whose rect straddles a wedge boundary has gradient rows on two (or more) ranks; the owner ADDS them.
-// dense = six contiguous blocks (blocked layout), zeroed by the caller.
-__global__ void __launch_bounds__(256) k_shell_unpack_rows_add(int n, const float* __restrict__ rows, int P, float* __restrict__ dense, int base) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float* r = rows + 18 * (size_t)i;
-    const int g = __float_as_int(r[17]) - base;
-    if (g < 0 || g >= P) return;
-    const size_t Ps = (size_t)P, gs = (size_t)g;
-    const int off[6] = {0, 3, 7, 9, 10, 13}, wid[6] = {3, 4, 2, 1, 3, 4};
-#pragma unroll
-    for (int b = 0; b < 6; b++)
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-            if (k < wid[b]) {
-                const float v = r[off[b] + k];
-                if (v != 0.f) atomicAdd(dense + off[b] * Ps + wid[b] * gs + k, v);
-            }
-}
-void launch_shell_unpack_rows_add(int n, const float* rows, int P, float* dense, hipStream_t s, int base) {
-    hipLaunchKernelGGL(k_shell_unpack_rows_add, dim3((n + 255) / 256), dim3(256), 0, s, n, rows, P, dense, base);
-}
-// counts[d] = #(idx in [d * chunk, (d + 1) * chunk)), idx ascending: the split sizes of the gradient all-to-all
-__global__ void __launch_bounds__(64) k_shell_chunk_counts(int M, const int* __restrict__ idx, int chunk, int world, float* __restrict__ counts) {
-    const int d = blockIdx.x * blockDim.x + threadIdx.x;
-    if (d >= world) return;
-    auto lower = [&](long long v) { int lo = 0, hi = M; while (lo < hi) { const int md = (lo + hi) >> 1; if ((long long)idx[md] < v) lo = md + 1; else hi = md; } return lo; };
-    counts[d] = (float)(lower((long long)(d + 1) * chunk) - lower((long long)d * chunk));
-}
-__global__ void __launch_bounds__(256) k_shell_scatter_i32(int M, const int* __restrict__ idx, const int* __restrict__ src, int P, int* __restrict__ dst) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= M) return;
-    const int g = idx[i];
-    if (g >= 0 && g < P) dst[g] = src[i];
-}
-void launch_shell_pack_rows(int M, const float* g_m3, const float* g_m2, const float* g_col, const float* g_op, const float* g_sc,
-                            const float* g_rot, const int* idx, float* rows, hipStream_t s) {
-    hipLaunchKernelGGL(k_shell_pack_rows, dim3((M + 255) / 256), dim3(256), 0, s, M, g_m3, g_m2, g_col, g_op, g_sc, g_rot, idx, rows);
-}
-void launch_shell_unpack_rows(int n, const float* rows, int P, float* dense, int blocked, hipStream_t s, int base) {
-    hipLaunchKernelGGL(k_shell_unpack_rows, dim3((n + 255) / 256), dim3(256), 0, s, n, rows, P, dense, blocked, base);
-}
-void launch_shell_chunk_counts(int M, const int* idx, int chunk, int world, float* counts, hipStream_t s) {
-    hipLaunchKernelGGL(k_shell_chunk_counts, dim3((world + 63) / 64), dim3(64), 0, s, M, idx, chunk, world, counts);
-}
-void launch_shell_scatter_i32(int M, const int* idx, const int* src, int P, int* dst, hipStream_t s) {
-    hipLaunchKernelGGL(k_shell_scatter_i32, dim3((M + 255) / 256), dim3(256), 0, s, M, idx, src, P, dst);
 }
 
 }  // namespace lg

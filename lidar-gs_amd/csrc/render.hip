@@ -22,7 +22,8 @@
 //                     partial sums of the segments (and, multi-GPU, range shells) behind it.
 // If a segment's walk trips T < 1e-4, Tpass holds the value that tripped it (< 1e-4), so every later
 // segment is shut off; otherwise Tpass is the exact product of its (1 - alpha).  This is the same
-// two-phase scheme lidargs_dist.py uses across GPUs, applied across the CUs of one GPU.
+// two-phase scheme lidargs_dist.py uses across GPUs (its per-pixel folds over the shells are in shard.hip), applied across the
+// CUs of one GPU.
 //
 // Per chunk of 64 list entries: lane l gathers entry l's 64-byte splat record (one aligned segment)
 // + row span into registers while the previous chunk is being composited, then parks it in LDS
@@ -1287,90 +1288,6 @@ void launch_render_backward(const RenderBwdArgs& a, hipStream_t s) {
     const unsigned blocks = a.walk.cnt ? (unsigned)LG_WORK_REGIONS * a.walk.cap : segment_grid(a.grid.window_patches(), a.S);
     if (walk2() & 4) hipLaunchKernelGGL(k_render_backward<true>, dim3(blocks), dim3(64), 0, s, a);
     else hipLaunchKernelGGL(k_render_backward<false>, dim3(blocks), dim3(64), 0, s, a);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Multi-GPU glue (lidargs_dist): per-pixel folds over the G range shells, one launch each instead of a dozen
-// elementwise framework ops on a 0.2 ms critical path.
-__global__ void __launch_bounds__(256) k_shell_transmittance(int G, int rank, int N, size_t row_stride, const float* __restrict__ all_T, float* __restrict__ T_in) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N) return;
-    float T = 1.f;
-    for (int g = 0; g < rank && g < G; g++) T *= all_T[(size_t)g * row_stride + i];
-    T_in[i] = T;
-}
-
-// planes[g] = (C0, C1, D, T_end, T_hand) of shell g.  The walk stopped in the first shell whose hand-over value fell
-// below the reference's 1e-4 threshold; T_final is that shell's T_end (the last shell's if none stopped).
-__global__ void __launch_bounds__(256) k_shell_compose(int G, int rank, int N, const float* __restrict__ planes, const float* __restrict__ bg,
-                                                       float* __restrict__ out_color, float* __restrict__ out_depth, float* __restrict__ out_occ,
-                                                       float* __restrict__ T_final, float* __restrict__ behind) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N) return;
-    float c0 = 0.f, c1 = 0.f, d = 0.f, b0 = 0.f, b1 = 0.f, bd = 0.f, Tf = 1.f;
-    bool stopped = false;
-    for (int g = 0; g < G; g++) {
-        const float* p = planes + (size_t)g * 5 * N + i;
-        const float pc0 = p[0], pc1 = p[(size_t)N], pd = p[2 * (size_t)N];
-        c0 += pc0; c1 += pc1; d += pd;
-        if (g > rank) { b0 += pc0; b1 += pc1; bd += pd; }
-        if (!stopped) { Tf = p[3 * (size_t)N]; stopped = p[4 * (size_t)N] < 0.0001f; }
-    }
-    const float g0 = bg ? bg[0] : 0.f, g1 = bg ? bg[1] : 0.f;
-    out_color[i] = c0 + Tf * g0; out_color[(size_t)N + i] = c1 + Tf * g1;
-    out_depth[i] = d; out_occ[i] = 1.f - Tf; T_final[i] = Tf;
-    behind[i] = b0; behind[(size_t)N + i] = b1; behind[2 * (size_t)N + i] = bd;
-}
-
-// Column wedges: a rank's own pixel columns [c0, c1) of the four image planes (colour 0/1, depth, occupancy) as one dense
-// [4][H][wmax] block (what the image all-gather ships; columns >= c1 - c0 are padding), and back: G such blocks -> full planes.
-__global__ void __launch_bounds__(256) k_wedge_pack_columns(int H, int W, int c0, int c1, int wmax, const float* __restrict__ color,
-                                                            const float* __restrict__ depth, const float* __restrict__ occ, float* __restrict__ out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int n = 4 * H * wmax;
-    if (i >= n) return;
-    const int x = i % wmax, y = (i / wmax) % H, pl = i / (wmax * H);
-    const int col = c0 + x;
-    float v = 0.f;
-    if (col < c1) {
-        const size_t pix = (size_t)y * W + col;
-        v = pl < 2 ? color[(size_t)pl * H * W + pix] : (pl == 2 ? depth[pix] : occ[pix]);
-    }
-    out[i] = v;
-}
-struct WedgeEdges { int e[65]; };
-__global__ void __launch_bounds__(256) k_wedge_unpack_columns(int G, int H, int W, int wmax, size_t stride, WedgeEdges ed, const float* __restrict__ blocks,
-                                                              float* __restrict__ color, float* __restrict__ depth, float* __restrict__ occ) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t n = (size_t)4 * H * W;
-    if (i >= n) return;
-    const int col = (int)(i % W), y = (int)((i / W) % H), pl = (int)(i / ((size_t)W * H));
-    int g = 0;
-    while (g + 1 < G && col >= ed.e[g + 1]) g++;
-    const float v = blocks[(size_t)g * stride + ((size_t)pl * H + y) * wmax + (col - ed.e[g])];
-    const size_t pix = (size_t)y * W + col;
-    if (pl < 2) color[(size_t)pl * H * W + pix] = v;
-    else if (pl == 2) depth[pix] = v;
-    else occ[pix] = v;
-}
-void launch_wedge_pack_columns(int H, int W, int c0, int c1, int wmax, const float* color, const float* depth, const float* occ, float* out, hipStream_t s) {
-    const int n = 4 * H * wmax;
-    hipLaunchKernelGGL(k_wedge_pack_columns, dim3((n + 255) / 256), dim3(256), 0, s, H, W, c0, c1, wmax, color, depth, occ, out);
-}
-void launch_wedge_unpack_columns(int G, int H, int W, int wmax, size_t stride, const int* edges, const float* blocks, float* color, float* depth,
-                                 float* occ, hipStream_t s) {
-    WedgeEdges ed;
-    for (int g = 0; g <= G && g < 65; g++) ed.e[g] = edges[g];
-    const size_t n = (size_t)4 * H * W;
-    hipLaunchKernelGGL(k_wedge_unpack_columns, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, G, H, W, wmax, stride, ed, blocks, color, depth, occ);
-}
-
-void launch_shell_transmittance(int G, int rank, int N, size_t row_stride, const float* all_T, float* T_in, hipStream_t s) {
-    hipLaunchKernelGGL(k_shell_transmittance, dim3((N + 255) / 256), dim3(256), 0, s, G, rank, N, row_stride, all_T, T_in);
-}
-void launch_shell_compose(int G, int rank, int N, const float* planes, const float* bg, float* out_color, float* out_depth, float* out_occ,
-                          float* T_final, float* behind, hipStream_t s) {
-    hipLaunchKernelGGL(k_shell_compose, dim3((N + 255) / 256), dim3(256), 0, s, G, rank, N, planes, bg, out_color, out_depth, out_occ, T_final, behind);
 }
 
 }  // namespace lg

@@ -132,7 +132,7 @@ class OracleShellBackend:
 
 
 class OracleWedgeBackend(OracleShellBackend):
-    """CPU stand-in for the column-wedge half of HipShellBackend: the selection restates k_wedge_flags' bound (so a bound that is
+    """CPU stand-in for the column-wedge half of HipShellBackend: the selection restates k_wedge_flags' bound (csrc/selection.h wedge_reaches; so a bound that is
     too tight shows up as a wrong image here), the render is the oracle on the selected rows with everything outside the rank's
     pixel columns ignored: cropped in the forward, upstream gradients zeroed in the backward."""
 
