@@ -20,8 +20,6 @@ import torch
 from diff_lidargs_rasterization import _C as _base
 
 _lib = _base._lib
-_lib.lidargs_anchor_growing_level.restype = C.c_int
-_lib.lidargs_ag_scratch_bytes.restype = C.c_size_t
 EXACT_DIVISION = 1     # LIDARGS_AG_EXACT_DIVISION
 
 
@@ -52,15 +50,15 @@ def grow_level(anchor, offset, scaling, anchor_feat, grads, offset_mask, rand, g
     empty = (torch.empty((0, 3), dtype=torch.float32, device=dev), torch.empty((0, F), dtype=torch.float32, device=dev))
     if N0 == 0:
         return empty + ((0, 0, 0),)
-    nb = int(_lib.lidargs_ag_scratch_bytes(C.c_int(N0), C.c_int(k)))
+    nb = _lib.lidargs_ag_scratch_bytes(N0, k)
     scratch = torch.empty(nb, dtype=torch.uint8, device=dev)
     work, out_a, out_f = _base._Scratch(dev), _base._Scratch(dev), _base._Scratch(dev)
     counts = (C.c_int * 3)()
     p = _base._ptr
     with torch.cuda.device(dev):
-        rc = _lib.lidargs_anchor_growing_level(C.c_int(N), C.c_int(N0), C.c_int(k), C.c_int(F), p(anchor), p(offset), p(scaling), p(anchor_feat), p(grads), p(om),
-                                               p(rnd), C.c_float(grad_threshold), C.c_float(rand_threshold), C.c_double(cur_size), C.c_int(flags), p(scratch),
-                                               C.c_size_t(nb), work.cb, work.user, out_a.cb, out_a.user, out_f.cb, out_f.user, counts, _base._stream(dev))
+        rc = _lib.lidargs_anchor_growing_level(N, N0, k, F, p(anchor), p(offset), p(scaling), p(anchor_feat), p(grads), p(om), p(rnd),
+                                               grad_threshold, rand_threshold, cur_size, flags, p(scratch), nb, work.cb, work.user,
+                                               out_a.cb, out_a.user, out_f.cb, out_f.user, counts, _base._stream(dev))
     work.take()
     ta, tf = out_a.take(), out_f.take()
     if rc < 0:

@@ -19,8 +19,6 @@ import torch
 from diff_lidargs_rasterization import _C as _base
 
 _lib = _base._lib
-_lib.lidargs_voxelize_sample.restype = C.c_int
-_lib.lidargs_voxelize_scratch_bytes.restype = C.c_size_t
 
 
 def voxelize_device(points, voxel_size):
@@ -38,12 +36,12 @@ def voxelize_device(points, voxel_size):
     P, dev, dt = int(pts.shape[0]), pts.device, pts.dtype
     if P == 0:
         return torch.empty((0, 3), dtype=dt, device=dev)
-    nb = int(_lib.lidargs_voxelize_scratch_bytes(C.c_int(P)))
+    nb = _lib.lidargs_voxelize_scratch_bytes(P)
     scratch = torch.empty(nb, dtype=torch.uint8, device=dev)
     out = _base._Scratch(dev)
     with torch.cuda.device(dev):
-        rc = _lib.lidargs_voxelize_sample(C.c_int(P), C.c_void_p(pts.data_ptr()), C.c_int(1 if dt == torch.float64 else 0), C.c_double(v),
-                                          _base._ptr(scratch), C.c_size_t(nb), out.cb, out.user, _base._stream(dev))
+        rc = _lib.lidargs_voxelize_sample(P, C.c_void_p(pts.data_ptr()), 1 if dt == torch.float64 else 0, v,
+                                          _base._ptr(scratch), nb, out.cb, out.user, _base._stream(dev))
     t = out.take()
     if rc < 0:
         _base._raise(rc, "voxelize_sample")

@@ -3,16 +3,11 @@
 extern/chamfer3D/dist_chamfer_3D.py looks for a module of this name first (`importlib.find_loader("chamfer_3D")`, :14) and only
 JIT-compiles its CUDA sources when it is missing; with lidar-gs_amd/ on PYTHONPATH the reference's own `chamfer_3DDist` wrapper
 therefore runs on the HIP kernels of include/lidargs_chamfer.h unchanged.  Same two functions, same in-place contract."""
-import ctypes as C
-
 import torch
 
 from diff_lidargs_rasterization import _C as _base
 
 _lib = _base._lib
-_lib.lidargs_chamfer_forward.restype = C.c_int
-_lib.lidargs_chamfer_backward.restype = C.c_int
-_lib.lidargs_chamfer_scratch_bytes.restype = C.c_size_t
 
 
 def _chk(t, name, dtype):
@@ -28,11 +23,11 @@ def forward(xyz1, xyz2, dist1, dist2, idx1, idx2):
     _chk(idx1, "idx1", torch.int32); _chk(idx2, "idx2", torch.int32)
     B, n, m = int(xyz1.shape[0]), int(xyz1.shape[1]), int(xyz2.shape[1])
     p = _base._ptr
-    nb = int(_lib.lidargs_chamfer_scratch_bytes(C.c_int(B), C.c_int(n), C.c_int(m)))
+    nb = _lib.lidargs_chamfer_scratch_bytes(B, n, m)
     scratch = torch.empty(nb, dtype=torch.uint8, device=xyz1.device)
     with torch.cuda.device(xyz1.device):
-        rc = _lib.lidargs_chamfer_forward(C.c_int(B), C.c_int(n), C.c_int(m), p(xyz1), p(xyz2), p(dist1), p(dist2), p(idx1), p(idx2),
-                                          p(scratch), C.c_size_t(nb), _base._stream(xyz1.device))
+        rc = _lib.lidargs_chamfer_forward(B, n, m, p(xyz1), p(xyz2), p(dist1), p(dist2), p(idx1), p(idx2), p(scratch), nb,
+                                          _base._stream(xyz1.device))
     if rc < 0:
         _base._raise(rc, "chamfer_3D.forward")
     return 1
@@ -46,7 +41,7 @@ def backward(xyz1, xyz2, gradxyz1, gradxyz2, graddist1, graddist2, idx1, idx2):
     B, n, m = int(xyz1.shape[0]), int(xyz1.shape[1]), int(xyz2.shape[1])
     p = _base._ptr
     with torch.cuda.device(xyz1.device):
-        rc = _lib.lidargs_chamfer_backward(C.c_int(B), C.c_int(n), C.c_int(m), p(xyz1), p(xyz2), p(graddist1), p(graddist2), p(idx1), p(idx2),
+        rc = _lib.lidargs_chamfer_backward(B, n, m, p(xyz1), p(xyz2), p(graddist1), p(graddist2), p(idx1), p(idx2),
                                            p(gradxyz1), p(gradxyz2), _base._stream(xyz1.device))
     if rc < 0:
         _base._raise(rc, "chamfer_3D.backward")

@@ -17,27 +17,12 @@ import os
 
 import torch
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SO_PATH = os.path.join(_HERE, "liblidargs_hip.so")
+import lidargs_abi
+
 NUM_CHANNELS = 2  # R3/cr/config.h:15
-
-if not os.path.exists(_SO_PATH):
-    raise ImportError(
-        f"diff_lidargs_rasterization: native library {_SO_PATH} is missing. Build it with "
-        "`python lidar-gs_amd/build_hip.py` (hipcc --offload-arch=gfx950). There is no CPU fallback.")
-
-_lib = C.CDLL(_SO_PATH)
+# The one CDLL of the process, every lidargs_* function typed from the headers (restype and argtypes: lidargs_abi).
+_lib = lidargs_abi.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "liblidargs_hip.so"))
 _ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_size_t)
-_lib.lidargs_last_error.restype = C.c_char_p
-for _name in ("lidargs_forward", "lidargs_forward_enqueue", "lidargs_backward", "lidargs_visible_filter", "lidargs_mark_visible",
-              "lidargs_forward_shell", "lidargs_render_shell", "lidargs_backward_shell", "lidargs_abi_version",
-              "lidargs_profile_read", "lidargs_profile_summary", "lidargs_last_counters"):
-    getattr(_lib, _name).restype = C.c_int
-_lib.lidargs_profile_stage_name.restype = C.c_char_p
-_lib.lidargs_profile_enable.restype = None
-_lib.lidargs_counters_enable.restype = None
-if _lib.lidargs_abi_version() != 2:
-    raise ImportError("diff_lidargs_rasterization: liblidargs_hip.so ABI version mismatch; rebuild it")
 
 
 def _err():
@@ -160,13 +145,12 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
         for t, n in ((bg, "bg"), (col, "colors_precomp"), (opa, "opacities"), (vm, "viewmatrix"), (beams, "beam_inclinations")):
             if t.numel():
                 _require_device(t, n)
-        common = (_alloc_cb, geom.user, _alloc_cb, binning.user, _alloc_cb, img.user,
-                  C.c_int(P), C.c_int(int(degree)), C.c_int(M), _ptr(bg), C.c_int(W), C.c_int(H),
+        common = (_alloc_cb, geom.user, _alloc_cb, binning.user, _alloc_cb, img.user, P, int(degree), M, _ptr(bg), W, H,
                   _ptr(m3), _ptr(shc if shc.is_cuda else None), _ptr(col), _ptr(opa), _ptr(sc if sc.is_cuda else None),
-                  C.c_float(float(scale_modifier)), _ptr(rot if rot.is_cuda else None), _ptr(cov if cov.is_cuda else None),
+                  float(scale_modifier), _ptr(rot if rot.is_cuda else None), _ptr(cov if cov.is_cuda else None),
                   _ptr(vm), _ptr(pm if pm.is_cuda else None), _ptr(cp if cp.is_cuda else None), _ptr(beams),
-                  C.c_int(int(bool(prefiltered))), C.c_int(int(far)), C.c_int(int(near)),
-                  _ptr(out_color), _ptr(out_depth), _ptr(out_occ), _ptr(radii), _ptr(radii_xy), C.c_int(int(bool(debug))))
+                  int(bool(prefiltered)), int(far), int(near),
+                  _ptr(out_color), _ptr(out_depth), _ptr(out_occ), _ptr(radii), _ptr(radii_xy), int(bool(debug)))
         with torch.cuda.device(dev):
             if enqueue is None:
                 rendered = _lib.lidargs_forward(*common, _stream(dev))
@@ -174,8 +158,8 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
                 cap, tile_rows, status = enqueue
                 if status is not None and not (status.dtype == torch.int32 and status.numel() >= 16 and status.is_pinned()):
                     raise RuntimeError("enqueue status must be a pinned int32 host tensor of at least 16 elements")
-                rendered = _lib.lidargs_forward_enqueue(*common, C.c_int(int(cap)), C.c_int(int(tile_rows)),
-                                                        C.c_void_p(status.data_ptr()) if status is not None else None, _stream(dev))
+                status = C.c_void_p(status.data_ptr()) if status is not None else None       # (pinned HOST memory: not _ptr's business)
+                rendered = _lib.lidargs_forward_enqueue(*common, int(cap), int(tile_rows), status, _stream(dev))
         if rendered < 0:
             geom.take(); binning.take(); img.take()
             _raise(rendered, "rasterize_gaussians")
@@ -220,14 +204,13 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
         sc, rot = _f32(scales, "scales"), _f32(rotations, "rotations")
         with torch.cuda.device(dev):
             rc = _lib.lidargs_backward(
-                C.c_int(P), C.c_int(int(degree)), C.c_int(M), C.c_int(int(R)), _ptr(bg), C.c_int(W), C.c_int(H),
-                _ptr(m3), None, _ptr(col), _ptr(sc if sc.is_cuda else None), C.c_float(float(scale_modifier)),
-                _ptr(rot if rot.is_cuda else None), _ptr(cov if cov.is_cuda else None), _ptr(vm), None, None, _ptr(beams),
-                C.c_float(float(tan_fovx)), C.c_float(float(tan_fovy)), _ptr(rad),
+                P, int(degree), M, int(R), _ptr(bg), W, H, _ptr(m3), None, _ptr(col), _ptr(sc if sc.is_cuda else None),
+                float(scale_modifier), _ptr(rot if rot.is_cuda else None), _ptr(cov if cov.is_cuda else None), _ptr(vm), None, None,
+                _ptr(beams), float(tan_fovx), float(tan_fovy), _ptr(rad),
                 _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(g0), _ptr(g1), _ptr(g2),
                 _ptr(dL_dmeans2D), _ptr(dL_dconic), _ptr(dL_dopacity), _ptr(dL_dcolors), _ptr(dL_ddepths), _ptr(dL_dmeans3D),
                 _ptr(dL_dsphere), _ptr(dL_du1), _ptr(dL_du2), _ptr(dL_dcov3D), None, _ptr(dL_dscales), _ptr(dL_drotations),
-                C.c_int(int(bool(debug))), _stream(dev))
+                int(bool(debug)), _stream(dev))
         if rc < 0:
             _raise(rc, "rasterize_gaussians_backward")
     return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
@@ -249,11 +232,10 @@ def rasterize_aussians_filter(means3D, scales, rotations, scale_modifier, cov3D_
         cov, vm, beams = _f32(cov3D_precomp, "cov3D_precomp"), _f32(viewmatrix, "viewmatrix"), _f32(beam_inclinations, "beam_inclinations")
         with torch.cuda.device(dev):
             rc = _lib.lidargs_visible_filter(
-                None, None, None, None, None, None, C.c_int(P), C.c_int(0), C.c_int(int(image_width)), C.c_int(int(image_height)),
-                _ptr(m3), _ptr(sc if sc.is_cuda else None), C.c_float(float(scale_modifier)), _ptr(rot if rot.is_cuda else None),
-                _ptr(cov if cov.is_cuda else None), _ptr(vm), None, None, _ptr(beams), C.c_float(float(tan_fovx)),
-                C.c_float(float(tan_fovy)), C.c_int(int(bool(prefiltered))), C.c_int(int(far)), C.c_int(int(near)),
-                _ptr(radii), _ptr(radii_xy), C.c_int(int(bool(debug))), _stream(dev))
+                None, None, None, None, None, None, P, 0, int(image_width), int(image_height),
+                _ptr(m3), _ptr(sc if sc.is_cuda else None), float(scale_modifier), _ptr(rot if rot.is_cuda else None),
+                _ptr(cov if cov.is_cuda else None), _ptr(vm), None, None, _ptr(beams), float(tan_fovx), float(tan_fovy),
+                int(bool(prefiltered)), int(far), int(near), _ptr(radii), _ptr(radii_xy), int(bool(debug)), _stream(dev))
         if rc < 0:
             _raise(rc, "rasterize_aussians_filter")
     return radii
@@ -268,7 +250,7 @@ def mark_visible(means3D, viewmatrix, projmatrix):
     if P != 0:
         m3, vm = _f32(means3D, "means3D"), _f32(viewmatrix, "viewmatrix")
         with torch.cuda.device(dev):
-            rc = _lib.lidargs_mark_visible(C.c_int(P), _ptr(m3), _ptr(vm), None, _ptr(present), _stream(dev))
+            rc = _lib.lidargs_mark_visible(P, _ptr(m3), _ptr(vm), None, _ptr(present), _stream(dev))
         if rc < 0:
             _raise(rc, "mark_visible")
     return present
@@ -278,14 +260,14 @@ def mark_visible(means3D, viewmatrix, projmatrix):
 def profile_enable(on=True):
     """False/0: off; True/1: stage events on every call; N > 1: on every N-th forward and every N-th backward (an event costs
     ~4.5 us of device time, a dozen per call 6 % of a 1 ms frame)."""
-    _lib.lidargs_profile_enable(C.c_int(int(on)))
+    _lib.lidargs_profile_enable(int(on))
 
 
 def profile_read():
     """[(stage name, milliseconds)] of the last forward or backward call on this thread."""
     buf = (C.c_float * 24)()
-    n = _lib.lidargs_profile_read(buf, C.c_int(24))
-    return [(_lib.lidargs_profile_stage_name(C.c_int(i)).decode(), float(buf[i])) for i in range(n)]
+    n = _lib.lidargs_profile_read(buf, 24)
+    return [(_lib.lidargs_profile_stage_name(i).decode(), float(buf[i])) for i in range(n)]
 
 
 def profile_summary():
@@ -293,20 +275,20 @@ def profile_summary():
     names = (C.c_char_p * 48)()
     tot = (C.c_float * 48)()
     cnt = (C.c_int * 48)()
-    n = _lib.lidargs_profile_summary(names, tot, cnt, C.c_int(48))
+    n = _lib.lidargs_profile_summary(names, tot, cnt, 48)
     return {names[i].decode(): (float(tot[i]) / max(1, cnt[i]), int(cnt[i])) for i in range(n)}
 
 
 def counters_enable(on):
     """While on, every forward of this thread ends with the small counting launches behind V, R_ref, taken_instances, touched and
     backward_entries of last_counters() (diagnostics: keep it off inside timed regions)."""
-    _lib.lidargs_counters_enable(C.c_int(1 if on else 0))
+    _lib.lidargs_counters_enable(1 if on else 0)
 
 
 def last_counters():
     """dict(P, V, instances, R_ref, tile_rows, tiles, ..., touched) of the last forward on this thread; the device-side ones (V, R_ref,
     taken_instances, touched, backward_entries) are -1 unless counters_enable(True) was in force during that forward."""
     buf = (C.c_longlong * 10)()
-    _lib.lidargs_last_counters(buf, C.c_int(10))
+    _lib.lidargs_last_counters(buf, 10)
     return dict(P=buf[0], V=buf[1], instances=buf[2], R_ref=buf[3], tile_rows=buf[4], tiles=buf[5], taken_instances=buf[6],
                 segments=buf[7], touched=buf[8], backward_entries=buf[9])

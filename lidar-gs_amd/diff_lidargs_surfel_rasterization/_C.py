@@ -7,8 +7,6 @@ diff_lidargs_surfel_rasterization) with the same names, positional signatures an
 include/lidargs_rasterizer.h.  The shared library, allocator callback and helpers are those of
 diff_lidargs_rasterization._C; there is no CPU path.
 """
-import ctypes as C
-
 import torch
 
 from diff_lidargs_rasterization import _C as _base
@@ -17,8 +15,6 @@ _lib = _base._lib
 _alloc_cb, _Scratch, _f32, _ptr, _stream, _require_device, _raise = (
     _base._alloc_cb, _base._Scratch, _base._f32, _base._ptr, _base._stream, _base._require_device, _base._raise)
 NUM_CHANNELS = 2   # R2/cr/config.h
-for _name in ("lidargs_surfel_forward", "lidargs_surfel_backward", "lidargs_surfel_visible_filter"):
-    getattr(_lib, _name).restype = C.c_int
 
 
 def _dev_or_none(t):
@@ -55,13 +51,10 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
                 _require_device(t, n)
         with torch.cuda.device(dev):
             rendered = _lib.lidargs_surfel_forward(
-                _alloc_cb, geom.user, _alloc_cb, binning.user, _alloc_cb, img.user,
-                C.c_int(P), C.c_int(int(degree)), C.c_int(M), _ptr(bg), C.c_int(W), C.c_int(H),
-                _ptr(m3), None, _ptr(col), _ptr(opa), _dev_or_none(sc), C.c_float(float(scale_modifier)), _dev_or_none(rot),
-                _dev_or_none(tm), _ptr(vm), None, None, _ptr(beams),
-                C.c_int(int(bool(prefiltered))), C.c_int(int(lidar_far)), C.c_int(int(lidar_near)),
-                _ptr(out_color), _ptr(out_others), _ptr(pixels), _ptr(radii), _ptr(radii_xy),
-                C.c_int(int(bool(debug))), _stream(dev))
+                _alloc_cb, geom.user, _alloc_cb, binning.user, _alloc_cb, img.user, P, int(degree), M, _ptr(bg), W, H,
+                _ptr(m3), None, _ptr(col), _ptr(opa), _dev_or_none(sc), float(scale_modifier), _dev_or_none(rot),
+                _dev_or_none(tm), _ptr(vm), None, None, _ptr(beams), int(bool(prefiltered)), int(lidar_far), int(lidar_near),
+                _ptr(out_color), _ptr(out_others), _ptr(pixels), _ptr(radii), _ptr(radii_xy), int(bool(debug)), _stream(dev))
         if rendered < 0:
             geom.take(); binning.take(); img.take()
             _raise(rendered, "rasterize_gaussians (surfel)")
@@ -96,12 +89,12 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
         sc, rot, rad = _f32(scales, "scales"), _f32(rotations, "rotations"), radii.contiguous()
         with torch.cuda.device(dev):
             rc = _lib.lidargs_surfel_backward(
-                C.c_int(P), C.c_int(int(degree)), C.c_int(M), C.c_int(int(R)), _ptr(bg), C.c_int(W), C.c_int(H),
-                _ptr(m3), None, None, _dev_or_none(sc), C.c_float(float(scale_modifier)), _dev_or_none(rot), _dev_or_none(tm),
-                _ptr(vm), None, None, _ptr(beams), _ptr(rad), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer),
+                P, int(degree), M, int(R), _ptr(bg), W, H, _ptr(m3), None, None, _dev_or_none(sc), float(scale_modifier),
+                _dev_or_none(rot), _dev_or_none(tm), _ptr(vm), None, None, _ptr(beams),
+                _ptr(rad), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer),
                 _ptr(g0), _ptr(g1), _ptr(dL_dmeans2D), _ptr(dL_dnormal), _ptr(dL_dopacity), _ptr(dL_dcolors), _ptr(dL_dmeans3D),
                 _ptr(dL_dtransMat), _ptr(dL_dtm2d), None, _ptr(dL_dscales), _ptr(dL_drotations), _ptr(depth),
-                C.c_int(int(bool(debug))), _stream(dev))
+                int(bool(debug)), _stream(dev))
         if rc < 0:
             _raise(rc, "rasterize_gaussians_backward (surfel)")
     return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, (None if skip else dL_dtransMat), dL_dsh, dL_dscales, dL_drotations, depth
@@ -122,10 +115,9 @@ def rasterize_aussians_filter(means3D, scales, rotations, scale_modifier, transM
         vm, beams = _f32(viewmatrix, "viewmatrix"), _f32(beam_inclinations, "beam_inclinations")
         with torch.cuda.device(dev):
             rc = _lib.lidargs_surfel_visible_filter(
-                None, None, None, None, None, None, C.c_int(P), C.c_int(0), C.c_int(int(image_width)), C.c_int(int(image_height)),
-                _ptr(m3), _dev_or_none(sc), C.c_float(float(scale_modifier)), _dev_or_none(rot), None, _ptr(vm), None, _ptr(beams),
-                C.c_int(int(bool(prefiltered))), C.c_int(int(lidar_far)), C.c_int(int(lidar_near)),
-                _ptr(radii), _ptr(radii_xy), C.c_int(int(bool(debug))), _stream(dev))
+                None, None, None, None, None, None, P, 0, int(image_width), int(image_height),
+                _ptr(m3), _dev_or_none(sc), float(scale_modifier), _dev_or_none(rot), None, _ptr(vm), None, _ptr(beams),
+                int(bool(prefiltered)), int(lidar_far), int(lidar_near), _ptr(radii), _ptr(radii_xy), int(bool(debug)), _stream(dev))
         if rc < 0:
             _raise(rc, "rasterize_aussians_filter (surfel)")
     return radii

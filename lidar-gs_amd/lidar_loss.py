@@ -9,17 +9,11 @@ without it `loss` is the image part alone.  `terms` also carries Ll1, depth_loss
 (detached scalars, as train.py logs them).  The loss value and its gradients w.r.t. image, depth and scaling come out of the forward
 calls (this is the root of the graph); autograd only scales the stored gradients by the incoming one.  HIP tensors only; no framework
 fallback."""
-import ctypes as C
-
 import torch
 
 from diff_lidargs_rasterization import _C as _base
 
 _lib = _base._lib
-_lib.lidargs_image_loss.restype = C.c_int
-_lib.lidargs_loss_scratch_bytes.restype = C.c_size_t
-_lib.lidargs_scaling_reg.restype = C.c_int
-_lib.lidargs_scaling_reg_scratch_bytes.restype = C.c_size_t
 
 
 class _ImageLoss(torch.autograd.Function):
@@ -35,28 +29,28 @@ class _ImageLoss(torch.autograd.Function):
         losses = torch.empty(7, dtype=torch.float32, device=dev)        # loss, Ll1, depth, ssim, raydrop, grad, scaling_reg
         g_image = torch.empty_like(img)
         g_depth = torch.empty_like(dep)
-        nb = int(_lib.lidargs_loss_scratch_bytes(C.c_int(H), C.c_int(W)))
+        nb = _lib.lidargs_loss_scratch_bytes(H, W)
         M, nr = 0, 0
         if scaling is not None:
             _base._require_device(scaling, "scaling")
             if scaling.dim() != 2 or scaling.shape[1] != 3:
                 raise RuntimeError("image_loss: expected scaling [M,3]")
             M = int(scaling.shape[0])
-            nr = int(_lib.lidargs_scaling_reg_scratch_bytes(C.c_int(M)))
+            nr = _lib.lidargs_scaling_reg_scratch_bytes(M)
         scratch = torch.empty(max(nb, nr), dtype=torch.uint8, device=dev)
         p = _base._ptr
         g_scaling = None
         with torch.cuda.device(dev):
-            rc = _lib.lidargs_image_loss(C.c_int(H), C.c_int(W), p(img), p(dep), p(g), C.c_float(float(lambda_dssim)), p(losses), p(g_image),
-                                         p(g_depth), p(scratch), C.c_size_t(nb), _base._stream(dev))
+            rc = _lib.lidargs_image_loss(H, W, p(img), p(dep), p(g), float(lambda_dssim), p(losses), p(g_image),
+                                         p(g_depth), p(scratch), nb, _base._stream(dev))
             if rc < 0:
                 _base._raise(rc, "lidargs_image_loss")
             if scaling is not None:
                 sc = f32(scaling)
                 g_scaling = torch.empty_like(sc)
                 # (the same scratch: the stream runs the loss's launches first)
-                rc = _lib.lidargs_scaling_reg(C.c_int(M), p(sc), C.c_float(float(scaling_weight)), p(losses[6:]), p(losses), p(g_scaling), p(scratch),
-                                              C.c_size_t(max(nb, nr)), _base._stream(dev))
+                rc = _lib.lidargs_scaling_reg(M, p(sc), float(scaling_weight), p(losses[6:]), p(losses), p(g_scaling), p(scratch),
+                                              max(nb, nr), _base._stream(dev))
                 if rc < 0:
                     _base._raise(rc, "lidargs_scaling_reg")
             else:

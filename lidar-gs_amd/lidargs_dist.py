@@ -195,14 +195,6 @@ class HipShellBackend:
         from diff_lidargs_rasterization import _C
         self._C = _C
         self.lib = _C._lib
-        for name in ("lidargs_wedge_select_count", "lidargs_forward_wedge", "lidargs_backward_wedge", "lidargs_wedge_pack_columns", "lidargs_wedge_unpack_columns",
-                     "lidargs_wedge_unpack_grad_rows_add", "lidargs_shell_select", "lidargs_shell_select_count", "lidargs_shell_select_gather", "lidargs_shell_transmittance", "lidargs_shell_compose", "lidargs_shell_pack_grad_rows",
-                     "lidargs_shell_unpack_grad_rows", "lidargs_shell_chunk_counts", "lidargs_shell_scatter_radii", "lidargs_shell_select_enqueue",
-                     "lidargs_wedge_select_enqueue", "lidargs_forward_shell_enqueue", "lidargs_forward_wedge_enqueue", "lidargs_shell_select_sync",
-                     "lidargs_wedge_select_sync", "lidargs_shell_unpack_grad_rows_chunk", "lidargs_shell_pack_grad_rows_live_count",
-                     "lidargs_shell_pack_grad_rows_live"):
-            getattr(self.lib, name).restype = C.c_int
-        self.lib.lidargs_shell_select_scratch_bytes.restype = C.c_size_t
         self._scratch = {}          # persistent scratch of the selection (flags + offsets) per (device, P); never saved for a backward
         self._tls = threading.local()
 
@@ -233,18 +225,18 @@ class HipShellBackend:
     @staticmethod
     def _chunk_args(chunks):
         if chunks is None:
-            return C.c_int(0), C.c_int(0), None
+            return 0, 0, None
         rows, world, out = chunks
-        return C.c_int(int(rows)), C.c_int(int(world)), C.c_void_p(out.data_ptr())
+        return rows, world, C.c_void_p(out.data_ptr())
 
     def select(self, inp, lo, hi, plan=None, chunks=None):
         """Step 0: dense copies of the Gaussians with range in [lo, hi) + their indices (ascending); see _select."""
-        test = (self._C._ptr(inp["viewmatrix"]), C.c_float(lo), C.c_float(hi))
+        test = (self._C._ptr(inp["viewmatrix"]), lo, hi)
         return self._select("shell", ("means3D",), test, inp, plan, chunks)
 
     def select_wedge(self, inp, c0, c1, plan=None, chunks=None):
         """Dense copies of the Gaussians whose rect can reach pixel columns [c0, c1) + their indices (ascending); see _select."""
-        test = (C.c_float(inp["scale_modifier"]), self._C._ptr(inp["viewmatrix"]), C.c_int(inp["W"]), C.c_int(c0), C.c_int(c1))
+        test = (inp["scale_modifier"], self._C._ptr(inp["viewmatrix"]), inp["W"], c0, c1)
         return self._select("wedge", ("means3D", "scales", "rotations"), test, inp, plan, chunks)
 
     def _select(self, cut, count_keys, test, inp, plan, chunks):
@@ -257,29 +249,26 @@ class HipShellBackend:
           plan (enqueue-only frames): plan.rows capacity rows, no host read -- the row count stays on the device (sel["n_valid"]);
           _SELECT_FUSED (round 6): one launch into P-row arrays (only the first M rows are written and kept as views), one host read for M;
           otherwise count (one host read for M), then the gather into M rows."""
-        _C, lib, p = self._C, self.lib, self._C._ptr
+        _C, p = self._C, self._C._ptr
         m3 = inp["means3D"]
         _C._require_device(m3, "means3D")
         dev, P = m3.device, int(m3.shape[0])
         key = (dev, P)
         scr = self._scratch.get(key)
         if scr is None:
-            nb = int(lib.lidargs_shell_select_scratch_bytes(C.c_int(P)))
+            nb = self.lib.lidargs_shell_select_scratch_bytes(P)
             scr = (torch.empty(nb, dtype=torch.uint8, device=dev), nb)
             self._scratch = {key: scr}
         f = lambda n: dict((k, torch.empty((n, w), dtype=torch.float32, device=dev)) for k, w in zip(ROW_KEYS, (3, 2, 1, 3, 4)))   # n rows of each input
         if P and (plan is not None or _SELECT_FUSED):
-            cap = int(plan.rows) if plan is not None else P
+            cap = plan.rows if plan is not None else P
             name = f"lidargs_{cut}_select_enqueue" if plan is not None else f"lidargs_{cut}_select_sync"
             status = (C.c_void_p(plan.status.data_ptr() + 64),) if plan is not None else ()
             idx = torch.empty(cap, dtype=torch.int32, device=dev)
             rows = f(cap)
             n_valid = torch.empty(2, dtype=torch.int32, device=dev)
-            with self._on(dev):
-                M = getattr(lib, name)(C.c_int(P), *(p(inp[k]) for k in ROW_KEYS), *test, C.c_int(cap), p(idx), *(p(rows[k]) for k in ROW_KEYS),
-                                       p(n_valid), *status, p(scr[0]), C.c_size_t(scr[1]), *self._chunk_args(chunks), self._st(dev))
-            if M < 0:
-                _C._raise(M, name)
+            M = self._call(name, dev, P, *(p(inp[k]) for k in ROW_KEYS), *test, cap, p(idx), *(p(rows[k]) for k in ROW_KEYS), p(n_valid),
+                           *status, p(scr[0]), scr[1], *self._chunk_args(chunks))
             sel = dict(inp)
             if plan is not None:
                 sel.update(rows, n_valid=n_valid)
@@ -288,20 +277,13 @@ class HipShellBackend:
             return idx[:M], sel
         M = 0
         if P:
-            name = f"lidargs_{cut}_select_count"
-            with self._on(dev):
-                M = getattr(lib, name)(C.c_int(P), *(p(inp[k]) for k in count_keys), *test, p(scr[0]), C.c_size_t(scr[1]), self._st(dev))
-            if M < 0:
-                _C._raise(M, name)
+            M = self._call(f"lidargs_{cut}_select_count", dev, P, *(p(inp[k]) for k in count_keys), *test, p(scr[0]), scr[1])
         idx = torch.empty(M, dtype=torch.int32, device=dev)
         sel = dict(inp)
         sel.update(f(M))
         if M:
-            with self._on(dev):
-                rc = lib.lidargs_shell_select_gather(C.c_int(P), *(p(inp[k]) for k in ROW_KEYS), p(idx), *(p(sel[k]) for k in ROW_KEYS),
-                                                     p(scr[0]), C.c_size_t(scr[1]), *self._chunk_args(chunks), self._st(dev))
-            if rc < 0:
-                _C._raise(rc, "lidargs_shell_select_gather")
+            self._call("lidargs_shell_select_gather", dev, P, *(p(inp[k]) for k in ROW_KEYS), p(idx), *(p(sel[k]) for k in ROW_KEYS),
+                       p(scr[0]), scr[1], *self._chunk_args(chunks))
         elif chunks is not None:
             chunks[2].zero_()
         return idx, sel
@@ -316,7 +298,7 @@ class HipShellBackend:
             T_pass.fill_(1.0)                                              # (with rows, the library writes every pixel)
         dummy = torch.empty(4 * N, dtype=torch.float32, device=dev)
         p = self._C._ptr
-        self._forward(st, "lidargs_forward_shell", None, plan, C.c_float(lo), C.c_float(hi), None, C.c_int(1), p(dummy), p(dummy[2 * N:]),
+        self._forward(st, "lidargs_forward_shell", None, plan, lo, hi, None, 1, p(dummy), p(dummy[2 * N:]),
                       p(dummy[3 * N:]), p(T_pass))
         return st, T_pass
 
@@ -336,18 +318,14 @@ class HipShellBackend:
         _C, inp, n = self._C, st["inp"], 0
         if st["P"]:
             dev, p = inp["means3D"].device, _C._ptr
-            args = (_C._alloc_cb, st["geom"].user, _C._alloc_cb, st["binning"].user, _C._alloc_cb, st["img"].user, C.c_int(st["P"]), bg,
-                    C.c_int(inp["W"]), C.c_int(inp["H"]), p(inp["means3D"]), p(inp["colors"]), p(inp["opacities"]), p(inp["scales"]),
-                    C.c_float(inp["scale_modifier"]), p(inp["rotations"]), None, p(inp["viewmatrix"]), p(inp["beams"]), C.c_int(inp["far"]),
-                    C.c_int(inp["near"]), *cut_args, p(st["radii"]), p(st["radii_xy"]), C.c_int(0))
-            with self._on(dev):
-                if plan is None:
-                    n = getattr(self.lib, name)(*args, self._st(dev))
-                else:
-                    n = getattr(self.lib, name + "_enqueue")(*args, p(inp.get("n_valid")), C.c_int(plan.instances), C.c_int(plan.tile_rows),
-                                                             C.c_void_p(plan.status.data_ptr()), self._st(dev))
-            if n < 0:
-                _C._raise(n, name)
+            args = (_C._alloc_cb, st["geom"].user, _C._alloc_cb, st["binning"].user, _C._alloc_cb, st["img"].user, st["P"], bg,
+                    inp["W"], inp["H"], p(inp["means3D"]), p(inp["colors"]), p(inp["opacities"]), p(inp["scales"]), inp["scale_modifier"],
+                    p(inp["rotations"]), None, p(inp["viewmatrix"]), p(inp["beams"]), inp["far"], inp["near"], *cut_args,
+                    p(st["radii"]), p(st["radii_xy"]), 0)
+            if plan is None:
+                n = self._call(name, dev, *args)
+            else:
+                n = self._call(name + "_enqueue", dev, *args, p(inp.get("n_valid")), plan.instances, plan.tile_rows, C.c_void_p(plan.status.data_ptr()))
         for k in ("geom", "binning", "img"):       # keep only the tensors: nothing holds the registry entries alive
             st[k] = st[k].take()
         st["R"] = n
@@ -360,8 +338,8 @@ class HipShellBackend:
         g, o = {}, 0
         for k, w in GRAD_WIDTHS + (("cov3D", 6),):
             g[k] = slab[o:o + P * w].view(P, w); o += P * w
-        args = (C.c_int(P), C.c_int(st["R"]), p(inp["bg"]), C.c_int(inp["W"]), C.c_int(inp["H"]), p(inp["means3D"]), p(inp["colors"]),
-                p(inp["scales"]), C.c_float(inp["scale_modifier"]), p(inp["rotations"]), None, p(inp["viewmatrix"]), p(inp["beams"]),
+        args = (P, st["R"], p(inp["bg"]), inp["W"], inp["H"], p(inp["means3D"]), p(inp["colors"]),
+                p(inp["scales"]), inp["scale_modifier"], p(inp["rotations"]), None, p(inp["viewmatrix"]), p(inp["beams"]),
                 p(st["radii"]), p(st["geom"]), p(st["binning"]), p(st["img"]))
         return g, g.pop("cov3D"), args
 
@@ -372,29 +350,19 @@ class HipShellBackend:
         if allT.stride(1) != 1 or (G > 1 and allT.stride(0) < N):
             allT = allT.contiguous()
         stride = int(allT.stride(0)) if G > 1 else N                       # (the gathered rows may carry the split sizes behind their N values)
-        with self._on(allT.device):
-            rc = self.lib.lidargs_shell_transmittance(C.c_int(G), C.c_int(rank), C.c_int(N), C.c_size_t(stride), C.c_void_p(allT.data_ptr()),
-                                                      self._C._ptr(T_in), self._st(allT.device))
-        if rc < 0:
-            self._C._raise(rc, "lidargs_shell_transmittance")
+        self._call("lidargs_shell_transmittance", allT.device, G, rank, N, stride, C.c_void_p(allT.data_ptr()), self._C._ptr(T_in))
         return T_in
 
     def render(self, st, T_in):
         """Step 3 -> planes [5, N]: colour0, colour1, depth partial sums, T_end, T_hand."""
-        _C, lib = self._C, self.lib
         inp = st["inp"]
         dev, H, W = T_in.device, inp["H"], inp["W"]
         N = H * W
         planes = torch.empty(6 * N, dtype=torch.float32, device=dev)     # [C0, C1, D, T_end, T_hand, occ scratch]
         if st["P"]:
-            p = _C._ptr
-            with self._on(dev):
-                rc = lib.lidargs_render_shell(C.c_int(st["P"]), C.c_int(st["R"]), None, C.c_int(W), C.c_int(H), p(st["geom"]),
-                                              p(st["binning"]), p(st["img"]), p(T_in.contiguous()), C.c_int(0), p(planes),
-                                              p(planes[2 * N:]), p(planes[5 * N:]), p(planes[4 * N:]), p(planes[3 * N:]), C.c_int(0),
-                                              self._st(dev))
-            if rc < 0:
-                _C._raise(rc, "lidargs_render_shell")
+            p = self._C._ptr
+            self._call("lidargs_render_shell", dev, st["P"], st["R"], None, W, H, p(st["geom"]), p(st["binning"]), p(st["img"]),
+                       p(T_in.contiguous()), 0, p(planes), p(planes[2 * N:]), p(planes[5 * N:]), p(planes[4 * N:]), p(planes[3 * N:]), 0)
         else:
             planes[:3 * N] = 0
             planes[3 * N:4 * N] = T_in
@@ -403,16 +371,10 @@ class HipShellBackend:
 
     def compose(self, planes, rank, bg, H, W):
         """Step 4: planes [G, 5, N] -> (color [2,H,W], depth [1,H,W], occ [1,H,W], T_final [N], behind [3,N])."""
-        _C = self._C
-        G, N, dev = int(planes.shape[0]), H * W, planes.device
+        G, N, dev, p = int(planes.shape[0]), H * W, planes.device, self._C._ptr
         out = torch.empty(8 * N, dtype=torch.float32, device=dev)
         color, depth, occ, T_final, behind = out[:2 * N], out[2 * N:3 * N], out[3 * N:4 * N], out[4 * N:5 * N], out[5 * N:]
-        p = _C._ptr
-        with self._on(dev):
-            rc = self.lib.lidargs_shell_compose(C.c_int(G), C.c_int(rank), C.c_int(N), p(planes.contiguous()), p(bg), p(color), p(depth), p(occ),
-                                                p(T_final), p(behind), self._st(dev))
-        if rc < 0:
-            _C._raise(rc, "lidargs_shell_compose")
+        self._call("lidargs_shell_compose", dev, G, rank, N, p(planes.contiguous()), p(bg), p(color), p(depth), p(occ), p(T_final), p(behind))
         return color.view(2, H, W), depth.view(1, H, W), occ.view(1, H, W), T_final, behind.view(3, N)
 
     def backward(self, st, behind, T_final, grads):
@@ -423,7 +385,7 @@ class HipShellBackend:
             gc, gd, go = (t.contiguous() for t in grads)
             self._call("lidargs_backward_shell", dev, *args, p(behind.contiguous()), p(T_final.contiguous()), p(gc), p(gd), p(go), p(g["means2D"]),
                        None, p(g["opacities"]), p(g["colors"]), None, p(g["means3D"]), None, None, None, p(g_cov), p(g["scales"]),
-                       p(g["rotations"]), C.c_int(0))           # (the Nones: the reference's scratch gradients, not materialised)
+                       p(g["rotations"]), 0)    # (the Nones: the reference's scratch gradients, not materialised)
         return g
 
 
@@ -435,7 +397,7 @@ class HipShellBackend:
         dev, N = st["radii"].device, inp["H"] * inp["W"]
         planes = torch.empty(4 * N, dtype=torch.float32, device=dev)
         p = self._C._ptr
-        self._forward(st, "lidargs_forward_wedge", p(inp["bg"]), plan, C.c_int(c0), C.c_int(c1), p(planes), p(planes[2 * N:]), p(planes[3 * N:]))
+        self._forward(st, "lidargs_forward_wedge", p(inp["bg"]), plan, c0, c1, p(planes), p(planes[2 * N:]), p(planes[3 * N:]))
         if not st["P"]:       # no Gaussian can reach the wedge: background only
             pl = planes.view(4, N)
             pl[0] = inp["bg"][0]; pl[1] = inp["bg"][1]; pl[2] = 0; pl[3] = 0
@@ -448,15 +410,15 @@ class HipShellBackend:
         g, g_cov, args = self._backward_setup(st, dev)
         if st["P"]:
             gc, gd, go = (t.contiguous() for t in grads)
-            self._call("lidargs_backward_wedge", dev, *args, C.c_int(st["cols"][0]), C.c_int(st["cols"][1]), p(gc), p(gd), p(go), p(g["means2D"]),
-                       p(g["opacities"]), p(g["colors"]), p(g["means3D"]), p(g_cov), p(g["scales"]), p(g["rotations"]), C.c_int(0))
+            self._call("lidargs_backward_wedge", dev, *args, st["cols"][0], st["cols"][1], p(gc), p(gd), p(go), p(g["means2D"]),
+                       p(g["opacities"]), p(g["colors"]), p(g["means3D"]), p(g_cov), p(g["scales"]), p(g["rotations"]), 0)
         return g
 
     def pack_columns(self, planes, H, W, c0, c1, wmax, out):
         """out f32[4*H*wmax (+ tail)]: this rank's columns of the four planes, zero padded to wmax columns."""
         p = self._C._ptr
         N = H * W
-        self._call("lidargs_wedge_pack_columns", planes.device, C.c_int(H), C.c_int(W), C.c_int(c0), C.c_int(c1), C.c_int(wmax), p(planes),
+        self._call("lidargs_wedge_pack_columns", planes.device, H, W, c0, c1, wmax, p(planes),
                    p(planes[2 * N:]), p(planes[3 * N:]), p(out))
 
     def unpack_columns(self, blocks, edges, H, W, wmax):
@@ -466,7 +428,7 @@ class HipShellBackend:
         out = torch.empty(4 * H * W, dtype=torch.float32, device=dev)
         N = H * W
         e = (C.c_int * (G + 1))(*[int(x) for x in edges])
-        self._call("lidargs_wedge_unpack_columns", dev, C.c_int(G), C.c_int(H), C.c_int(W), C.c_int(wmax), C.c_size_t(stride), e,
+        self._call("lidargs_wedge_unpack_columns", dev, G, H, W, wmax, stride, e,
                    p(blocks.contiguous()), p(out), p(out[2 * N:]), p(out[3 * N:]))
         return out[:2 * N].view(2, H, W), out[2 * N:3 * N].view(1, H, W), out[3 * N:].view(1, H, W)
 
@@ -475,7 +437,7 @@ class HipShellBackend:
         dev, p = rows.device, self._C._ptr
         rows = rows.contiguous()
         dense = torch.empty(P * GRAD_COLS, dtype=torch.float32, device=dev)
-        self._call("lidargs_wedge_unpack_grad_rows_add", dev, C.c_int(int(rows.shape[0])), p(rows), C.c_int(P), p(dense))
+        self._call("lidargs_wedge_unpack_grad_rows_add", dev, int(rows.shape[0]), p(rows), P, p(dense))
         return dense
 
     # ---- step 6 helpers: one launch each instead of concatenates, casts and index copies -------------------------------
@@ -483,50 +445,48 @@ class HipShellBackend:
         """Gradient mode "shard": [n, 18] rows -> this rank's own [17 * chunk_rows] block (six contiguous gradient blocks)."""
         dev = rows.device
         dense = torch.empty(GRAD_COLS * int(chunk_rows), dtype=torch.float32, device=dev)
-        self._call("lidargs_shell_unpack_grad_rows_chunk", dev, C.c_int(int(rows.shape[0])), self._C._ptr(rows), C.c_int(int(base)), C.c_int(int(chunk_rows)),
-                   self._C._ptr(dense) if chunk_rows else None, C.c_int(1 if add else 0))
+        self._call("lidargs_shell_unpack_grad_rows_chunk", dev, int(rows.shape[0]), self._C._ptr(rows), int(base), int(chunk_rows),
+                   self._C._ptr(dense) if chunk_rows else None, 1 if add else 0)
         return dense
 
     def _call(self, name, dev, *args):
+        """lib.<name>(*args, stream) on `dev`: its return value, or RuntimeError for a negative one."""
         with self._on(dev):
             rc = getattr(self.lib, name)(*args, self._st(dev))
         if rc < 0:
             self._C._raise(rc, name)
+        return rc
 
     def scatter_radii(self, idx, radii_shell, P):
         """radii i32[P]: the shell's radii at their global rows, zero elsewhere."""
         dev, p = idx.device, self._C._ptr
         out = torch.empty(P, dtype=torch.int32, device=dev)
-        self._call("lidargs_shell_scatter_radii", dev, C.c_int(int(idx.shape[0])), p(idx), p(radii_shell), C.c_int(P), p(out))
+        self._call("lidargs_shell_scatter_radii", dev, int(idx.shape[0]), p(idx), p(radii_shell), P, p(out))
         return out
 
     def chunk_counts(self, idx, chunk_rows, world, out):
         """out f32[world] (a view into the buffer the T_pass all-gather ships): rows of this shell bound for each index chunk."""
-        self._call("lidargs_shell_chunk_counts", idx.device, C.c_int(int(idx.shape[0])), self._C._ptr(idx), C.c_int(chunk_rows), C.c_int(world),
-                   self._C._ptr(out))
+        self._call("lidargs_shell_chunk_counts", idx.device, int(idx.shape[0]), self._C._ptr(idx), chunk_rows, world, self._C._ptr(out))
 
     def pack_rows(self, g, idx):
         """[M, 18]: the six gradients of the shell's rows + the bit pattern of their global index."""
         dev, p, M = idx.device, self._C._ptr, int(idx.shape[0])
         rows = torch.empty((M, GRAD_COLS + 1), dtype=torch.float32, device=dev)
-        self._call("lidargs_shell_pack_grad_rows", dev, C.c_int(M), p(g["means3D"]), p(g["means2D"]), p(g["colors"]), p(g["opacities"]),
+        self._call("lidargs_shell_pack_grad_rows", dev, M, p(g["means3D"]), p(g["means2D"]), p(g["colors"]), p(g["opacities"]),
                    p(g["scales"]), p(g["rotations"]), p(idx), p(rows))
         return rows
 
     def _live_args(self, g, idx, P, chunk_rows, world):
         p = self._C._ptr
-        return (C.c_int(int(idx.shape[0])), p(g["means3D"]), p(g["means2D"]), p(g["colors"]), p(g["opacities"]), p(g["scales"]), p(g["rotations"]), p(idx),
-                C.c_int(int(P)), C.c_int(int(chunk_rows)), C.c_int(int(world)))
+        return (int(idx.shape[0]), p(g["means3D"]), p(g["means2D"]), p(g["colors"]), p(g["opacities"]), p(g["scales"]), p(g["rotations"]), p(idx),
+                int(P), int(chunk_rows), int(world))
 
     def count_rows_live(self, g, idx, P, chunk_rows, world):
         """Rows that carry a gradient, per destination chunk (round 6): int32 [2 * world] ON THE DEVICE, no host read -- the first world
         words are the counts, the other world are pack_rows_live's cursor."""
         dev = idx.device
         cnt = torch.empty(2 * world, dtype=torch.int32, device=dev)
-        with self._on(dev):
-            rc = self.lib.lidargs_shell_pack_grad_rows_live_count(*self._live_args(g, idx, P, chunk_rows, world), C.c_void_p(cnt.data_ptr()), None, self._st(dev))
-        if rc < 0:
-            self._C._raise(rc, "lidargs_shell_pack_grad_rows_live_count")
+        self._call("lidargs_shell_pack_grad_rows_live_count", dev, *self._live_args(g, idx, P, chunk_rows, world), C.c_void_p(cnt.data_ptr()), None)
         return cnt
 
     def pack_rows_live(self, g, idx, P, chunk_rows, world, cnt, n):
@@ -534,11 +494,8 @@ class HipShellBackend:
         dev = idx.device
         rows = torch.empty((int(n), GRAD_COLS + 1), dtype=torch.float32, device=dev)
         if n:
-            with self._on(dev):
-                rc = self.lib.lidargs_shell_pack_grad_rows_live(*self._live_args(g, idx, P, chunk_rows, world), C.c_void_p(cnt.data_ptr()),
-                                                                C.c_void_p(cnt.data_ptr() + 4 * world), self._C._ptr(rows), self._st(dev))
-            if rc < 0:
-                self._C._raise(rc, "lidargs_shell_pack_grad_rows_live")
+            self._call("lidargs_shell_pack_grad_rows_live", dev, *self._live_args(g, idx, P, chunk_rows, world), C.c_void_p(cnt.data_ptr()),
+                       C.c_void_p(cnt.data_ptr() + 4 * world), self._C._ptr(rows))
         return rows
 
     def unpack_rows(self, rows, P, blocked=False):
@@ -547,7 +504,7 @@ class HipShellBackend:
         dev, p = rows.device, self._C._ptr
         rows = rows.contiguous()
         dense = torch.empty(P * GRAD_COLS if blocked else (P, GRAD_COLS), dtype=torch.float32, device=dev)
-        self._call("lidargs_shell_unpack_grad_rows", dev, C.c_int(int(rows.shape[0])), p(rows), C.c_int(P), p(dense), C.c_int(1 if blocked else 0))
+        self._call("lidargs_shell_unpack_grad_rows", dev, int(rows.shape[0]), p(rows), P, p(dense), 1 if blocked else 0)
         return dense
 
 

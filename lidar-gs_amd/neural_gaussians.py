@@ -24,18 +24,12 @@ class _Model(C.Structure):
                 ("W1", C.c_void_p * 4), ("b1", C.c_void_p * 4), ("W2", C.c_void_p * 4), ("b2", C.c_void_p * 4), ("W2T", C.c_void_p * 4)]
 
 
-for _n in ("lidargs_ng_forward_select", "lidargs_ng_forward_select_enqueue", "lidargs_ng_forward_decode", "lidargs_ng_backward", "lidargs_ng_backward_mfma",
-           "lidargs_ng_backward_partials", "lidargs_ng_training_stats", "lidargs_ng_weight_grad_floats", "lidargs_ng_weight_grad_stage_floats", "lidargs_ng_reduce_weight_grads", "lidargs_ng_transpose_w2"):
-    getattr(_lib, _n).restype = C.c_int
-_lib.lidargs_ng_scratch_bytes.restype = C.c_size_t
-
-
 def _transposed_w2(params, k, dev):
     """Transposed second-layer weights, the B operand of Y = H W2^T on the matrix pipe (forward and backward): one launch for the four."""
     out = torch.empty(320 * k, dtype=torch.float32, device=dev)
     ptrs = (C.c_void_p * 4)(*[params[4 * i + 2].data_ptr() for i in range(4)])
     with torch.cuda.device(dev):
-        _check(_lib.lidargs_ng_transpose_w2(C.c_int(k), ptrs, _base._ptr(out), _base._stream(dev)), "lidargs_ng_transpose_w2")
+        _check(_lib.lidargs_ng_transpose_w2(k, ptrs, _base._ptr(out), _base._stream(dev)), "lidargs_ng_transpose_w2")
     o = (0, k, 8 * k, 9 * k)
     return tuple(out[32 * o[i]:32 * o[i] + 32 * (7 * k if i == 1 else k)].view(32, 7 * k if i == 1 else k) for i in range(4))
 
@@ -101,7 +95,7 @@ class _Decode(torch.autograd.Function):
         N, k = int(anchor.shape[0]), int(offset.shape[1])
         w2t = _transposed_w2(params, k, dev)
         model = _model_struct(k, flags, params, w2t)
-        nb = int(_lib.lidargs_ng_scratch_bytes(C.c_int(N), C.c_int(k)))
+        nb = _lib.lidargs_ng_scratch_bytes(N, k)
         scratch = torch.empty(nb, dtype=torch.uint8, device=dev)
         neural_opacity = torch.empty(max(N, 1) * k, dtype=torch.float32, device=dev)
         mask = torch.empty(max(N, 1) * k, dtype=torch.uint8, device=dev)
@@ -113,16 +107,16 @@ class _Decode(torch.autograd.Function):
             stream = _base._stream(dev)
             # everything the decode launch needs that does not depend on (n, M), before the select's host read: the device is idle from
             # that read to the launch, so nothing but the output allocation sits between them (the output views are made behind it)
-            dec_head = (C.c_int(N), C.byref(model), p(anchor_feat), p(anchor), p(offset), p(scaling), camv, p(neural_opacity))
-            dec_tail = (p(scratch), C.c_size_t(nb), stream)
+            dec_head = (N, C.byref(model), p(anchor_feat), p(anchor), p(offset), p(scaling), camv, p(neural_opacity))
+            dec_tail = (p(scratch), nb, stream)
             cap = N * k                                                # rows of each output array: M itself, or its upper bound
             if 0 < cap * 52 <= _CAPACITY_BYTES:
                 # No idle device between the two steps: the decode writes into arrays of N k rows (its rows come from the device-side
                 # scan), queued right behind the selection; the host waits for the two counts -- an event in front of the decode --
                 # while it runs, and the outputs are the first M rows.
                 pinned, ev = _pinned_counts(dev)
-                _check(_lib.lidargs_ng_forward_select_enqueue(C.c_int(N), C.byref(model), p(vis), p(anchor_feat), p(anchor), camv, p(neural_opacity),
-                                                              p(mask), C.c_void_p(pinned.data_ptr()), p(scratch), C.c_size_t(nb), stream),
+                _check(_lib.lidargs_ng_forward_select_enqueue(N, C.byref(model), p(vis), p(anchor_feat), p(anchor), camv, p(neural_opacity),
+                                                              p(mask), C.c_void_p(pinned.data_ptr()), p(scratch), nb, stream),
                        "lidargs_ng_forward_select_enqueue")
                 ev.record(torch.cuda.current_stream(dev))
                 out = torch.empty(cap * 13, dtype=torch.float32, device=dev)
@@ -132,8 +126,8 @@ class _Decode(torch.autograd.Function):
                 ev.synchronize()
                 n, M = int(pinned[0]), int(pinned[1])
             else:
-                _check(_lib.lidargs_ng_forward_select(C.c_int(N), C.byref(model), p(vis), p(anchor_feat), p(anchor), camv, p(neural_opacity), p(mask),
-                                                      counts, p(scratch), C.c_size_t(nb), stream), "lidargs_ng_forward_select")
+                _check(_lib.lidargs_ng_forward_select(N, C.byref(model), p(vis), p(anchor_feat), p(anchor), camv, p(neural_opacity), p(mask),
+                                                      counts, p(scratch), nb, stream), "lidargs_ng_forward_select")
                 n, M = int(counts[0]), int(counts[1])
                 cap = M
                 out = torch.empty(M * 13, dtype=torch.float32, device=dev)
@@ -181,10 +175,10 @@ class _Decode(torch.autograd.Function):
             delta2 = torch.empty((n, 10 * k), dtype=torch.float32, device=dev)
             if N:
                 with torch.cuda.device(dev):
-                    _check(_lib.lidargs_ng_backward(C.c_int(N), C.c_int(n), C.byref(model), p(anchor_feat), p(anchor), p(offset), p(scaling), camv,
+                    _check(_lib.lidargs_ng_backward(N, n, C.byref(model), p(anchor_feat), p(anchor), p(offset), p(scaling), camv,
                                                     p(g_xyz), p(g_color), p(g_opacity), p(g_scaling), p(g_rot), p(g_no), p(d_feat), p(d_anchor),
                                                     p(d_offset), p(d_scaling), p(act_x), p(act_h), p(delta1), p(delta2), p(scratch),
-                                                    C.c_size_t(scratch.numel()), _base._stream(dev)), "lidargs_ng_backward")
+                                                    scratch.numel(), _base._stream(dev)), "lidargs_ng_backward")
             # With n ~ 1e5..1e6 and a, b <= 132 a plain mm picks a one-tile kernel that walks all of n serially (0.5 ms each), so n is
             # split into chunks: a batched GEMM of partial products plus a small sum.
             def tn(a, b):
@@ -200,15 +194,15 @@ class _Decode(torch.autograd.Function):
             # everything matrix-shaped on the matrix pipe, weight gradients included: the persistent waves' partial sums come back,
             # one row per wave
             waves, per_wave = C.c_int(0), C.c_int(0)
-            _check(_lib.lidargs_ng_backward_partials(C.c_int(k), C.byref(waves), C.byref(per_wave)), "lidargs_ng_backward_partials")
+            _check(_lib.lidargs_ng_backward_partials(k, C.byref(waves), C.byref(per_wave)), "lidargs_ng_backward_partials")
             partials = torch.empty((waves.value, per_wave.value), dtype=torch.float32, device=dev)
             if N:
                 with torch.cuda.device(dev):
                     base = dense.data_ptr()
                     at = lambda floats: C.c_void_p(base + 4 * floats)       # the launch first, the views of `dense` behind it
-                    _check(_lib.lidargs_ng_backward_mfma(C.c_int(N), C.byref(model), p(anchor_feat), p(anchor), p(offset), p(scaling), camv,
+                    _check(_lib.lidargs_ng_backward_mfma(N, C.byref(model), p(anchor_feat), p(anchor), p(offset), p(scaling), camv,
                                                          p(g_xyz), p(g_color), p(g_opacity), p(g_scaling), p(g_rot), p(g_no), at(0), at(N * 32),
-                                                         at(N * 35), at(N * (35 + 3 * k)), p(partials), p(scratch), C.c_size_t(scratch.numel()),
+                                                         at(N * 35), at(N * (35 + 3 * k)), p(partials), p(scratch), scratch.numel(),
                                                          _base._stream(dev)), "lidargs_ng_backward_mfma")
             d_feat, d_anchor, d_offset, d_scaling = dense_views()
             # sum over the waves and unpack into the sixteen parameter gradients, two small launches (before: a framework reduction over
@@ -216,13 +210,13 @@ class _Decode(torch.autograd.Function):
             dins = (35 + int(flags[0]), 35 + int(flags[1]), 35 + int(flags[2]), 35 + int(flags[2]))
             douts = (k, 7 * k, k, k)
             din_c = (C.c_int * 4)(*dins)
-            nfl = int(_lib.lidargs_ng_weight_grad_floats(C.c_int(k), din_c))
+            nfl = _lib.lidargs_ng_weight_grad_floats(k, din_c)
             _check(nfl, "lidargs_ng_weight_grad_floats")
             if N:
-                nst = int(_lib.lidargs_ng_weight_grad_stage_floats(C.c_int(k), din_c))
+                nst = _lib.lidargs_ng_weight_grad_stage_floats(k, din_c)
                 flat = torch.empty(nfl + nst, dtype=torch.float32, device=dev)     # the gradients, then the first stage's row-group sums
                 with torch.cuda.device(dev):
-                    _check(_lib.lidargs_ng_reduce_weight_grads(C.c_int(k), din_c, C.c_int(waves.value), p(partials), p(flat), p(flat[nfl:]), _base._stream(dev)),
+                    _check(_lib.lidargs_ng_reduce_weight_grads(k, din_c, waves.value, p(partials), p(flat), p(flat[nfl:]), _base._stream(dev)),
                            "lidargs_ng_reduce_weight_grads")
             else:
                 flat = torch.zeros(nfl, dtype=torch.float32, device=dev)
@@ -317,10 +311,10 @@ def training_statis(pc, viewspace_point_tensor, opacity, update_filter, offset_s
             raise RuntimeError("training_statis: the accumulators must be contiguous float32 tensors")
     vis, sel, upd = u8(anchor_visible_mask), u8(offset_selection_mask), u8(update_filter)
     op, grad = f32(opacity), f32(viewspace_point_tensor.grad)
-    nb = int(_lib.lidargs_ng_scratch_bytes(C.c_int(N), C.c_int(k)))
+    nb = _lib.lidargs_ng_scratch_bytes(N, k)
     scratch = torch.empty(nb, dtype=torch.uint8, device=dev)
     p = _base._ptr
     with torch.no_grad(), torch.cuda.device(dev):
-        _check(_lib.lidargs_ng_training_stats(C.c_int(N), C.c_int(k), p(vis), p(sel), p(upd), p(op), p(grad), p(pc.opacity_accum), p(pc.anchor_demon),
-                                              p(pc.offset_gradient_accum), p(pc.offset_denom), p(scratch), C.c_size_t(nb), _base._stream(dev)),
+        _check(_lib.lidargs_ng_training_stats(N, k, p(vis), p(sel), p(upd), p(op), p(grad), p(pc.opacity_accum), p(pc.anchor_demon),
+                                              p(pc.offset_gradient_accum), p(pc.offset_denom), p(scratch), nb, _base._stream(dev)),
                "lidargs_ng_training_stats")

@@ -5,7 +5,6 @@ the whole metric -- back-projection of the non-empty pixels, nearest neighbours 
 on device-resident images (include/lidargs_chamfer.h lidargs_points_meter); the reference copies both images to the host, back-projects
 with numpy, uploads the clouds for its chamfer kernel and reads the results back (:256-279).  The per-frame values stay on the device
 until `measure()` asks for them."""
-import ctypes as C
 import os
 
 import numpy as np
@@ -14,8 +13,6 @@ import torch
 from diff_lidargs_rasterization import _C as _base
 
 _lib = _base._lib
-_lib.lidargs_points_meter.restype = C.c_int
-_lib.lidargs_points_meter_scratch_bytes.restype = C.c_size_t
 
 
 def points_metrics(pred, truth, scale=1.0, intrinsics=None, beam_inclinations=None, threshold=0.05):
@@ -41,12 +38,11 @@ def points_metrics(pred, truth, scale=1.0, intrinsics=None, beam_inclinations=No
     else:
         raise RuntimeError("points_metrics: need beam_inclinations or intrinsics = (fov_up, fov)")
     out = torch.empty(6, dtype=torch.float32, device=dev)
-    nb = int(_lib.lidargs_points_meter_scratch_bytes(C.c_int(H), C.c_int(W)))
+    nb = _lib.lidargs_points_meter_scratch_bytes(H, W)
     scratch = torch.empty(nb, dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        rc = _lib.lidargs_points_meter(C.c_int(H), C.c_int(W), _base._ptr(pred), _base._ptr(truth), C.c_float(float(scale)), _base._ptr(beams),
-                                       C.c_float(fov_up), C.c_float(fov), C.c_float(float(threshold)), _base._ptr(out), _base._ptr(scratch),
-                                       C.c_size_t(nb), _base._stream(dev))
+        rc = _lib.lidargs_points_meter(H, W, _base._ptr(pred), _base._ptr(truth), float(scale), _base._ptr(beams), fov_up, fov,
+                                       float(threshold), _base._ptr(out), _base._ptr(scratch), nb, _base._stream(dev))
     if rc < 0:
         _base._raise(rc, "points_meter")
     return out

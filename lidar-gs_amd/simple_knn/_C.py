@@ -14,8 +14,6 @@ import torch
 from diff_lidargs_rasterization import _C as _base
 
 _lib = _base._lib
-_lib.lidargs_knn_mean_dist.restype = C.c_int
-_lib.lidargs_knn_scratch_bytes.restype = C.c_size_t
 
 
 def distCUDA2(points):
@@ -33,11 +31,11 @@ def distCUDA2(points):
         return out
     if pts.stride(1) != 1 or pts.stride(0) < 3:
         pts = pts.contiguous()
-    nb = int(_lib.lidargs_knn_scratch_bytes(C.c_int(P)))
+    nb = _lib.lidargs_knn_scratch_bytes(P)
     scratch = torch.empty(nb, dtype=torch.uint8, device=pts.device)
     with torch.cuda.device(pts.device):
-        rc = _lib.lidargs_knn_mean_dist(C.c_int(P), C.c_void_p(pts.data_ptr()), C.c_int(int(pts.stride(0))), _base._ptr(out), _base._ptr(scratch),
-                                        C.c_size_t(nb), _base._stream(pts.device))
+        rc = _lib.lidargs_knn_mean_dist(P, C.c_void_p(pts.data_ptr()), pts.stride(0), _base._ptr(out), _base._ptr(scratch), nb,
+                                        _base._stream(pts.device))
     if rc < 0:
         _base._raise(rc, "distCUDA2")
     return out

@@ -7,16 +7,12 @@ scikit-image's structural_similarity, takes two torch medians and reads the poin
 read back.  The SSIM restates scikit-image's default algorithm from its publication; it is not pinned against scikit-image itself.
 
 `ViewMeter` collects one row per view and reads them back once, in `measure()`."""
-import ctypes as C
-
 import numpy as np
 import torch
 
 from diff_lidargs_rasterization import _C as _base
 
 _lib = _base._lib
-_lib.lidargs_view_metrics_ex.restype = C.c_int
-_lib.lidargs_view_metrics_scratch_bytes.restype = C.c_size_t
 
 NAMES = ("l1", "psnr", "ssim", "in_mae", "in_rmse", "in_medae", "cd", "fscore", "mae", "medae", "rmse")
 
@@ -64,13 +60,12 @@ def view_metrics(render, depth, gt_image, beam_inclinations=None, intrinsics=Non
         out = torch.empty(11, dtype=torch.float64, device=dev)
     elif not (out.is_cuda and out.device == dev and out.dtype == torch.float64 and out.numel() == 11 and out.is_contiguous()):
         raise RuntimeError("view_metrics: out must be a contiguous float64[11] tensor on the inputs' device")
-    nb = int(_lib.lidargs_view_metrics_scratch_bytes(C.c_int(H), C.c_int(W)))
+    nb = _lib.lidargs_view_metrics_scratch_bytes(H, W)
     scratch = torch.empty(nb, dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        rc = _lib.lidargs_view_metrics_ex(C.c_int(H), C.c_int(W), _base._ptr(render), _base._ptr(depth), _base._ptr(gt_image),
-                                          C.c_float(float(depth_min)), C.c_float(float(depth_max)), _base._ptr(beams), C.c_float(fov_up),
-                                          C.c_float(fov), C.c_int(1 if points_meter else 0), _base._ptr(out), _base._ptr(scratch),
-                                          C.c_size_t(nb), _base._stream(dev))
+        rc = _lib.lidargs_view_metrics_ex(H, W, _base._ptr(render), _base._ptr(depth), _base._ptr(gt_image), float(depth_min),
+                                          float(depth_max), _base._ptr(beams), fov_up, fov, 1 if points_meter else 0, _base._ptr(out),
+                                          _base._ptr(scratch), nb, _base._stream(dev))
     if rc < 0:
         _base._raise(rc, "view_metrics")
     return out

@@ -11,17 +11,15 @@ import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "lidargs_rasterizer.h")
-HEADERS = [HEADER, os.path.join(ROOT, "include", "lidargs_neural_gaussians.h"), os.path.join(ROOT, "include", "lidargs_loss.h"),
-           os.path.join(ROOT, "include", "lidargs_chamfer.h"), os.path.join(ROOT, "include", "lidargs_anchor_growing.h")]
+INCLUDE = os.path.join(ROOT, "include")
+HEADER = os.path.join(INCLUDE, "lidargs_rasterizer.h")
+HEADERS = sorted(os.path.join(INCLUDE, f) for f in os.listdir(INCLUDE))      # every public header
 
 
 def _declared_functions():
-    names = set()
-    for h in HEADERS:
-        src = re.sub(r"/\*.*?\*/", "", open(h).read(), flags=re.S)
-        names |= set(re.findall(r"\b(lidargs_[a-z_0-9]+)\s*\(", src))
-    return sorted(names - {"lidargs_alloc_fn"})
+    """The binding's own parser (lidargs_abi): what it types is what the library must export."""
+    import lidargs_abi
+    return sorted(lidargs_abi.signatures(INCLUDE))
 
 
 def test_header_is_plain_c():
@@ -46,6 +44,94 @@ def test_library_exports_every_declared_symbol(hip_lib_built):
     out = subprocess.run(["nm", "-D", "--defined-only", hip_lib_built], capture_output=True, text=True).stdout
     exported = set(re.findall(r" T (lidargs_\w+)", out))
     assert set(names) <= exported
+
+
+INSTRUMENTED_ONLY = {"lidargs_debug_lane_stats"}     # exported by -DLG_LANE_STATS builds of the tools alone: no header declares it
+
+
+def test_binding_types_exactly_the_exported_functions(hip_lib_built):
+    """Both directions: every exported lidargs_* function has a signature (nothing callable is left untyped) and every signature
+    has a symbol."""
+    import lidargs_abi
+    out = subprocess.run(["nm", "-D", "--defined-only", hip_lib_built], capture_output=True, text=True).stdout
+    exported = set(re.findall(r" T (lidargs_\w+)", out)) - INSTRUMENTED_ONLY
+    typed = set(lidargs_abi.signatures(INCLUDE))
+    assert exported - typed == set(), "exported but not declared in include/"
+    assert typed - exported == set(), "declared in include/ but not exported"
+    from diff_lidargs_rasterization import _C
+    for name, (restype, argtypes) in lidargs_abi.signatures(INCLUDE).items():
+        fn = getattr(_C._lib, name)
+        assert fn.restype is restype and tuple(fn.argtypes) == argtypes, name
+
+
+def test_parser_against_prototypes_read_by_eye():
+    """Expectations written from the headers by hand, not produced by the parser."""
+    import lidargs_abi
+    i, f, d, z, p = ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_size_t, ctypes.c_void_p
+    sigs = lidargs_abi.signatures(INCLUDE)
+    assert len(sigs) == 75
+    ret, args = sigs["lidargs_forward"]
+    assert ret is i and len(args) == 34
+    assert args[:6] == (p,) * 6                                           # three (allocator, user) pairs
+    assert args[6:9] == (i, i, i) and args[9] is p and args[10:12] == (i, i)     # P, D, M, background, width, height
+    assert [k for k, t in enumerate(args) if t is f] == [17]              # scale_modifier, the one float
+    assert args[24:27] == (i, i, i) and args[27:32] == (p,) * 5 and args[32] is i and args[33] is p   # ..., debug, stream
+    assert len(sigs["lidargs_forward_enqueue"][1]) == 37 and sigs["lidargs_forward_enqueue"][1][33:] == (i, i, p, p)
+    assert len(sigs["lidargs_backward"][1]) == 42 and len(sigs["lidargs_surfel_backward"][1]) == 37
+    assert sigs["lidargs_last_error"] == (ctypes.c_char_p, ())
+    assert sigs["lidargs_abi_version"] == (i, ())
+    assert sigs["lidargs_profile_stage_name"] == (ctypes.c_char_p, (i,))
+    assert sigs["lidargs_profile_enable"] == (None, (i,)) and sigs["lidargs_counters_enable"] == (None, (i,))
+    assert sigs["lidargs_last_counters"] == (i, (p, i))
+    assert sigs["lidargs_shell_select_scratch_bytes"] == (z, (i,))
+    assert sigs["lidargs_chamfer_scratch_bytes"] == (z, (i, i, i))
+    assert sigs["lidargs_shell_transmittance"] == (i, (i, i, i, z, p, p, p))
+    # three lidargs_alloc_fn + user pairs behind (scratch, scratch_bytes); cur_size the one double
+    assert sigs["lidargs_anchor_growing_level"] == (i, (i, i, i, i) + (p,) * 7 + (f, f, d, i, p, z) + (p,) * 6 + (p, p))
+    # `char* (*alloc_out)(void* user, size_t bytes)` declared inline: ONE parameter, not two
+    assert sigs["lidargs_voxelize_sample"] == (i, (i, p, i, d, p, z, p, p, p))
+    assert sigs["lidargs_ng_transpose_w2"] == (i, (i, p, p, p))           # const float* const* W2
+    assert sigs["lidargs_ng_backward_partials"] == (i, (i, p, p))
+    assert sigs["lidargs_view_metrics_ex"] == (i, (i, i, p, p, p, f, f, p, f, f, i, p, p, z, p))
+
+
+def test_parser_refuses_what_it_cannot_map():
+    """A prototype outside the headers' vocabulary is an ImportError naming the function: never a function left untyped."""
+    import lidargs_abi
+    assert lidargs_abi.parse_header("/* c */ int lidargs_ok(int a, const float* b); // d") == {"lidargs_ok": (ctypes.c_int, (ctypes.c_int, ctypes.c_void_p))}
+    for text, what in (("int lidargs_by_value(struct pair v);", "lidargs_by_value"), ("int lidargs_short(short n);", "lidargs_short"),
+                       ("long lidargs_ret(void);", "lidargs_ret"), ("float* lidargs_retp(void);", "lidargs_retp"),
+                       ("int other_name(int a);", "other_name"), ("int lidargs_var;", "lidargs_var")):
+        with pytest.raises(ImportError, match=what):
+            lidargs_abi.parse_header(text)
+
+
+def test_typed_calls_are_refused_before_the_library_is_entered(hip_lib_built):
+    """Through the package's own _lib.  lidargs_mark_visible validates first (P = -1 never reaches the device), and a call ctypes
+    refuses never reaches it: the thread's last error stays the one a different entry point left."""
+    from diff_lidargs_rasterization import _C
+    lib = _C._lib
+    forward = [None] * 6 + [-1, 0, 0, None, 512, 16] + [None] * 5 + [1.0] + [None] * 6 + [0, 80, 0] + [None] * 5 + [0, None]
+    assert lib.lidargs_forward(*forward) == -1 and lib.lidargs_last_error() == b"forward: bad sizes"
+    with pytest.raises(TypeError):
+        lib.lidargs_forward(*forward[:-1])                                 # one argument too few (the stream)
+    with pytest.raises(TypeError):
+        lib.lidargs_mark_visible(-1, None, None, None, None)
+    with pytest.raises(ctypes.ArgumentError):
+        lib.lidargs_mark_visible(-1.0, None, None, None, None, None)       # a float where an int is declared
+    with pytest.raises(ctypes.ArgumentError):
+        lib.lidargs_mark_visible(-1, 1.0, None, None, None, None)          # a float where a pointer is declared
+    with pytest.raises(ctypes.ArgumentError):
+        lib.lidargs_mark_visible(ctypes.c_void_p(64), None, None, None, None, None)   # what _ptr(t) returns where an int is declared
+    with pytest.raises(ctypes.ArgumentError):
+        lib.lidargs_mark_visible(-1, ctypes.c_int(64), None, None, None, None)        # a c_int where a pointer is declared
+    with pytest.raises(ctypes.ArgumentError):
+        lib.lidargs_shell_transmittance(1, 0, -1, ctypes.c_int(4), None, None, None)  # a c_int where size_t is declared
+    with pytest.raises(ctypes.ArgumentError):                              # a spliced list shifted by one: a pointer lands in `P`
+        lib.lidargs_forward(*forward[:5], *forward[4:])
+    assert lib.lidargs_last_error() == b"forward: bad sizes"               # none of them got in
+    assert lib.lidargs_mark_visible(-1, None, None, None, None, None) == -1 and b"mark_visible" in lib.lidargs_last_error()
+    assert isinstance(_C._ptr(torch.zeros(4)), ctypes.c_void_p) and _C._ptr(torch.zeros(0)) is None and _C._ptr(None) is None
 
 
 def test_argument_validation_happens_before_any_device_work(hip_lib_built):
@@ -136,9 +222,25 @@ def test_missing_library_is_a_loud_import_error(tmp_path, hip_lib_built):
     dst.mkdir()
     for fn in ("__init__.py", "_C.py"):
         shutil.copy(os.path.join(src, fn), dst / fn)
+    shutil.copy(os.path.join(ROOT, "lidar-gs_amd", "lidargs_abi.py"), tmp_path / "lidargs_abi.py")     # the loader _C.py imports
     code = f"import sys; sys.path.insert(0, {str(tmp_path)!r}); import diff_lidargs_rasterization"
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True)
     assert r.returncode != 0 and "liblidargs_hip.so is missing" in (r.stderr + r.stdout).replace("\n", " ") or "is missing" in r.stderr
+
+
+def test_missing_headers_are_a_loud_import_error(tmp_path, hip_lib_built):
+    """The signatures come from include/: the package with its library but without the headers must raise, not load untyped."""
+    import shutil
+    src = os.path.join(ROOT, "lidar-gs_amd", "diff_lidargs_rasterization")
+    dst = tmp_path / "tree" / "diff_lidargs_rasterization"
+    dst.mkdir(parents=True)
+    for fn in ("__init__.py", "_C.py"):
+        shutil.copy(os.path.join(src, fn), dst / fn)
+    os.symlink(hip_lib_built, dst / "liblidargs_hip.so")
+    shutil.copy(os.path.join(ROOT, "lidar-gs_amd", "lidargs_abi.py"), tmp_path / "tree" / "lidargs_abi.py")
+    code = f"import sys; sys.path.insert(0, {str(tmp_path / 'tree')!r}); import diff_lidargs_rasterization"
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True)
+    assert r.returncode != 0 and "ImportError" in r.stderr and "headers" in r.stderr and "are missing" in r.stderr
 
 
 def test_surfel_package_mirrors_the_reference_interface(hip_lib_built):
