@@ -3,6 +3,7 @@
     python lidar-gs_amd/build_hip.py [--force]
 
 Output: lidar-gs_amd/diff_lidargs_rasterization/liblidargs_hip.so  (git-ignored, travels with gpurun)
+        lidar-gs_amd/lidargs_optim/liblidargs_optim.so             (the optimizer step: csrc/adam.hip alone, include_optim/)
 
 Per-file flags: the per-Gaussian kernels (preprocess.hip) are HBM-bound, so they are built with
 -ffp-contract=off: every expression rounds as written, which keeps the unit vectors s = p/|p| that
@@ -35,15 +36,22 @@ SOURCES = {
     "knn.hip": ["-ffp-contract=off"],              # the 3-NN squared distances and the voxel quotients are compared bit for bit; the box bound prunes exactly only without contraction
     "metrics.hip": ["-ffp-contract=off"],          # the SSIM map and the float32 means round as scikit-image / torch write them
 }
+# The optimizer's library: a target of its own, so that liblidargs_hip.so exports exactly what include/ declares.
+OPTIM_OUT = os.path.join(HERE, "lidargs_optim", "liblidargs_optim.so")
+OPTIM_INCLUDE = os.path.join(HERE, "..", "include_optim")
+OPTIM_SOURCES = {
+    "adam.hip": ["-ffp-contract=off"],             # torch's op-by-op roundings; the steps its device kernels fuse are written as fmaf
+}
 
 
 def build_id():
-    """A content hash of everything the library is built from (csrc/, the public headers, this file): the same on every box that holds the
+    """A content hash of everything the libraries are built from (csrc/, the public headers of both, this file): the same on every box that holds the
     same sources -- what the profile tools stamp their summaries with and bench.py compares against (the GPU boxes have no .git)."""
     import hashlib
     h = hashlib.sha1()
     files = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC)) + sorted(
-        os.path.join(HERE, "..", "include", f) for f in os.listdir(os.path.join(HERE, "..", "include"))) + [os.path.abspath(__file__)]
+        os.path.join(HERE, "..", "include", f) for f in os.listdir(os.path.join(HERE, "..", "include"))) + sorted(
+        os.path.join(OPTIM_INCLUDE, f) for f in os.listdir(OPTIM_INCLUDE)) + [os.path.abspath(__file__)]
     for f in files:
         h.update(os.path.basename(f).encode()); h.update(open(f, "rb").read())
     return h.hexdigest()[:12]
@@ -62,33 +70,45 @@ def box_id():
     return None
 
 
-def needs_build():
-    if not os.path.exists(OUT):
+def _stale(out, deps):
+    if not os.path.exists(out):
         return True
-    t = os.path.getmtime(OUT)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", "lidargs_rasterizer.h"), __file__]
+    t = os.path.getmtime(out)
     return any(os.path.getmtime(d) > t for d in deps)
+
+
+def needs_build():
+    return _stale(OUT, [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f not in OPTIM_SOURCES]
+                  + [os.path.join(HERE, "..", "include", "lidargs_rasterizer.h"), __file__])
+
+
+def optim_needs_build():
+    return _stale(OPTIM_OUT, [os.path.join(CSRC, f) for f in OPTIM_SOURCES]
+                  + [os.path.join(OPTIM_INCLUDE, f) for f in os.listdir(OPTIM_INCLUDE)] + [__file__])
 
 
 def build(force=False, verbose=False):
     """Up-to-date check and build under an exclusive file lock: the ranks of `bench.py --gpus N` (one process per GPU) all call this
     at start-up, and only the first may compile -- the others wait and then find the library up to date.  The link goes to a
-    temporary name and is moved into place, so a process that loaded the library earlier never sees a half-written file."""
-    if not force and not needs_build():
+    temporary name and is moved into place, so a process that loaded the library earlier never sees a half-written file.
+    Builds both libraries, each when its own dependencies are newer; returns the main library's path."""
+    if not force and not needs_build() and not optim_needs_build():
         return OUT
     import fcntl
     os.makedirs(OBJ, exist_ok=True)
     with open(os.path.join(OBJ, ".lock"), "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
         try:
-            if not force and not needs_build():
-                return OUT
-            return _build_locked(verbose)
+            if force or needs_build():
+                _build_locked(SOURCES, OUT, verbose)
+            if force or optim_needs_build():
+                _build_locked(OPTIM_SOURCES, OPTIM_OUT, verbose)
+            return OUT
         finally:
             fcntl.flock(lock, fcntl.LOCK_UN)
 
 
-def _build_locked(verbose):
+def _build_locked(sources, out, verbose):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     extra_all = os.environ.get("LIDARGS_EXTRA_HIPCC_FLAGS", "").split()      # instrumented builds of the tools (e.g. -DLG_LANE_STATS), never the product's
 
@@ -102,14 +122,14 @@ def _build_locked(verbose):
         return obj
 
     with ThreadPoolExecutor(max_workers=4) as ex:
-        objs = list(ex.map(compile_one, SOURCES.items()))
-    tmp = OUT + ".tmp.%d" % os.getpid()
+        objs = list(ex.map(compile_one, sources.items()))
+    tmp = out + ".tmp.%d" % os.getpid()
     cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-fno-gpu-rdc"] + objs + ["-o", tmp]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
-    os.replace(tmp, OUT)
-    return OUT
+    os.replace(tmp, out)
+    return out
 
 
 if __name__ == "__main__":

@@ -1,7 +1,8 @@
 """lidargs_abi -- the Python side of the C ABI: one loader, every signature read from the public headers.
 
 `load(path)` opens liblidargs_hip.so and sets `restype` and `argtypes` of every function the headers under include/ declare; the
-result is the one `CDLL` every module calls through (`diff_lidargs_rasterization._C._lib`).  The headers are the only source: a new
+result is the one `CDLL` every module calls through (`diff_lidargs_rasterization._C._lib`).  A second library with a header directory
+and a version function of its own (liblidargs_optim.so, include_optim/) is loaded by the same function with those three named.  The headers are the only source: a new
 entry point is typed the moment it is declared, and a prototype this parser cannot map is an ImportError naming the function, never
 a function left untyped.
 
@@ -72,7 +73,7 @@ def parse_header(text):
 
 
 def signatures(include=INCLUDE):
-    """The signatures of every header of include/."""
+    """The signatures of every header of a header directory (include/ unless another is named)."""
     if not os.path.isdir(include):
         raise ImportError(f"lidargs_abi: the public headers ({include}) are missing; the binding reads its signatures from them")
     sigs = {}
@@ -82,19 +83,21 @@ def signatures(include=INCLUDE):
     return sigs
 
 
-def load(path):
-    """The typed CDLL of liblidargs_hip.so at `path`."""
+def load(path, include=INCLUDE, version_fn="lidargs_abi_version", version=ABI_VERSION, package="diff_lidargs_rasterization"):
+    """The typed CDLL of the library at `path` (liblidargs_hip.so unless the other arguments say otherwise): every function the headers
+    of `include` declare is typed, and `version_fn()` must return `version`.  `package` names the importer in the error messages."""
+    so = os.path.basename(path)
     if not os.path.exists(path):
         raise ImportError(
-            f"diff_lidargs_rasterization: native library {path} is missing. Build it with "
+            f"{package}: native library {path} is missing. Build it with "
             "`python lidar-gs_amd/build_hip.py` (hipcc --offload-arch=gfx950). There is no CPU fallback.")
     lib = C.CDLL(path)
-    for name, (restype, argtypes) in signatures().items():
+    for name, (restype, argtypes) in signatures(include).items():
         try:
             fn = getattr(lib, name)
         except AttributeError:
-            raise ImportError(f"diff_lidargs_rasterization: liblidargs_hip.so does not export {name}, which the headers declare; rebuild it") from None
+            raise ImportError(f"{package}: {so} does not export {name}, which the headers declare; rebuild it") from None
         fn.restype, fn.argtypes = restype, argtypes
-    if lib.lidargs_abi_version() != ABI_VERSION:
-        raise ImportError("diff_lidargs_rasterization: liblidargs_hip.so ABI version mismatch; rebuild it")
+    if getattr(lib, version_fn)() != version:
+        raise ImportError(f"{package}: {so} ABI version mismatch; rebuild it")
     return lib
