@@ -529,6 +529,36 @@ int lidargs_last_counters(long long* out, int n);
  * rounding boundary (which one random Gaussian in 1e8 hits) and require bit equality with the oracle's getRect. */
 int lidargs_debug_rects(int n, int surfel, const float* p_cr, const int* r_xy, int tiles_x, int tiles_y, int* rects, void* stream);
 
+/* Test hooks of the sorts (no reference counterpart as entry points; never called by the binding): the library's own sort launchers on
+ * caller-supplied pairs, so that tests/ can hold the ORDER they produce bit for bit against a stable argsort.  Device pointers unless
+ * said otherwise; nothing waits for the stream.
+ *
+ * lidargs_debug_sort_pairs: the stable LSD radix sort of n (key, u32 value) pairs on the digit field
+ *     ((bias_on ? (key == 0xFFFFFFFF ? cull : key - kmin) : key) >> begin_bit) & ((1 << (end_bit - begin_bit)) - 1),
+ * keys of key_bytes = 4 or 2 bytes in key_a, values in val_a (not read with vals_are_positions: the values are then 0..n-1), the b side
+ * as the other half of the ping-pong.  Digits of at most max_bits (0 = the default 8; at most 11).  scratch holds
+ * lidargs_debug_sort_scratch_words(n, scratch_bits) words, scratch_bits = 0 (the digit width) or up to 11: room beyond the digit width
+ * lets the sort use half-size blocks.  n_dev (nullable): the pair count is min(n, *n_dev) and the positions behind it are unspecified.
+ * tail_mode 1: the last pass also writes u32 tail_dst[i] = ((const u32*)tail_src)[value at i]; 2: u32x2 tail_dst[i] = (y, x) of the
+ * u32x4 record tail_src[value at i]; with a tail the sorted keys may not be written.  Returns the side the result lies on (0: a, 1: b)
+ * or a negative LIDARGS_ERR_*.  16-bit keys take no tail, bias, begin_bit, positions, scratch_bits or digit width of their own.
+ * lidargs_debug_sort_result_side: the side the sort leaves n pairs on, for default digits and no tail, as the frame's tile sort asks.
+ * lidargs_debug_range_sort_rest: how a frame cuts its range sort in two -- from the smallest and largest visible key, plan (HOST
+ * memory, 4 words) = (kmin, cull, end_bit, max_bits) of the second call, which sorts bits [8, end_bit) behind a first call on [0, 8).
+ * lidargs_debug_range_sort_buckets: the bucketed range sort of P (key, position) pairs: key_a = the range keys (0xFFFFFFFF: culled),
+ * key_span u32[64][2] = (~smallest, largest) visible key per slot as the preprocess leaves them (unused slots 0, 0), scratch of
+ * lidargs_debug_sort_scratch_words(P, 11) words; ids in range order -> id_a, the tail's records (tail_mode 1 or 2, as above; culled ids
+ * get "no instances": 0xFFFFFFFF / (0, 0)) -> tail_dst, which holds 2 P words in either mode.  Refused for a P at which no frame takes
+ * this form. */
+size_t lidargs_debug_sort_scratch_words(size_t n, int scratch_bits);
+int lidargs_debug_sort_result_side(size_t n, int end_bit);
+int lidargs_debug_sort_pairs(size_t n, int key_bytes, void* key_a, void* key_b, unsigned* val_a, unsigned* val_b, int begin_bit, int end_bit,
+                             int max_bits, int scratch_bits, unsigned* scratch, const unsigned* n_dev, int vals_are_positions, int bias_on,
+                             size_t kmin, size_t cull, int tail_mode, const void* tail_src, void* tail_dst, void* stream);
+int lidargs_debug_range_sort_rest(size_t key_min, size_t key_max, unsigned* plan);
+int lidargs_debug_range_sort_buckets(size_t P, unsigned* key_a, unsigned* key_b, unsigned* id_a, unsigned* id_b, unsigned* scratch,
+                                     const unsigned* key_span, int tail_mode, const void* tail_src, void* tail_dst, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -403,18 +403,15 @@ int bin_frame(const BinSpec& spec, const GeomView& geom, uint2* ranges, size_t P
             for (int slot = 0; slot < LG_INST_SLOTS; slot++) {
                 kinv = std::max(kinv, totals_h[LG_TOTALS_KEYSPAN_WORD + 2 * slot]); kmax = std::max(kmax, totals_h[LG_TOTALS_KEYSPAN_WORD + 2 * slot + 1]);
             }
-            KeyBias kb;
-            kb.kmin = (~kinv) & ~255u;                                      // a multiple of 256: (key - kmin) & 255 == key & 255
-            if (kmax < kb.kmin) { kb.kmin = 0u; kmax = 0u; }               // no visible Gaussian: every key is the culled one
-            kb.cull = ((kmax - kb.kmin) | 255u) + 1u;                       // above every valid key - kmin in the bits the later passes sort on
-            int bits = 32 - __builtin_clz(kb.cull | 1u);
-            if (bits < 9) bits = 9;
+            const RangeSortRest rest = range_sort_rest(kinv, kmax);
+            KeyBias kb = rest.bias;
+            int bits = rest.end_bit;
             static const int env_full = [] { const char* e = getenv("LIDARGS_RANGE_SORT_FULL"); return e ? atoi(e) : 0; }();   // 1: always 31 bits (A/B)
             if (env_full && !surfel) { bits = 32; kb.kmin = 0u; kb.cull = 0xFFFFFFFFu; }
             uint32_t* const k_in = first_side ? geom.key_b : geom.key_a; uint32_t* const k_out = first_side ? geom.key_a : geom.key_b;
             uint32_t* const v_in = first_side ? geom.id_b : geom.id_a; uint32_t* const v_out = first_side ? geom.id_a : geom.id_b;
             const int side = launch_radix_sort_pairs(k_in, k_out, v_in, v_out, P, bits, geom.scratch, stream,
-                                                     bits > 26 ? 8 : 9, nullptr, SORT_MAX_RADIX_BITS, false, span_tail, 8, &kb);
+                                                     env_full && !surfel ? 8 : rest.max_bits, nullptr, SORT_MAX_RADIX_BITS, false, span_tail, 8, &kb);
             ids_sorted = side ? v_out : v_in;
             LG_STAGE_CHECK("range sort");
         }
@@ -808,6 +805,69 @@ int lidargs_debug_rects(int n, int surfel, const float* p_cr, const int* r_xy, i
     if (!p_cr || !r_xy || !rects) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_rects: NULL required pointer%s");
     lg::launch_debug_rects(n, surfel, p_cr, r_xy, tiles_x, tiles_y, rects, stream);
     LG_STAGE_CHECK("debug rects");
+    return 0;
+}
+
+// Test hooks of the sorts (binning.hip): the product's own launchers on caller-supplied pairs; no dispatch is decided here.
+size_t lidargs_debug_sort_scratch_words(size_t n, int scratch_bits) {
+    if (scratch_bits < 1 || scratch_bits > lg::SORT_MAX_RADIX_BITS) scratch_bits = lg::SORT_RADIX_BITS;
+    return lg::sort_scratch_words(n, scratch_bits);
+}
+
+int lidargs_debug_sort_result_side(size_t n, int end_bit) { return lg::radix_sort_result_side(n, end_bit); }
+
+int lidargs_debug_sort_pairs(size_t n, int key_bytes, void* key_a, void* key_b, unsigned* val_a, unsigned* val_b, int begin_bit, int end_bit,
+                             int max_bits, int scratch_bits, unsigned* scratch, const unsigned* n_dev, int vals_are_positions, int bias_on,
+                             size_t kmin, size_t cull, int tail_mode, const void* tail_src, void* tail_dst, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const int debug = 0;
+    if (key_bytes != 2 && key_bytes != 4) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_sort_pairs: key_bytes must be 2 or 4%s");
+    if (n > (size_t)std::numeric_limits<int>::max()) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_sort_pairs: bad size%s");
+    if (begin_bit < 0 || end_bit < begin_bit || end_bit > 8 * key_bytes) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_sort_pairs: bad bit range%s");
+    if (max_bits < 0 || max_bits > lg::SORT_MAX_RADIX_BITS) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_sort_pairs: bad digit width%s");
+    const int digit = max_bits ? max_bits : lg::SORT_RADIX_BITS;
+    if (scratch_bits != 0 && (scratch_bits < digit || scratch_bits > lg::SORT_MAX_RADIX_BITS))
+        return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_sort_pairs: scratch_bits must be 0 or in [digit width, 11]%s");
+    if (tail_mode < 0 || tail_mode > 2 || (tail_mode != 0 && (!tail_src || !tail_dst)))
+        return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_sort_pairs: bad tail%s");
+    if (kmin > 0xFFFFFFFFull || cull > 0xFFFFFFFFull) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_sort_pairs: the bias is 32 bits wide%s");
+    if (key_bytes == 2 && (tail_mode != 0 || bias_on || begin_bit != 0 || vals_are_positions || scratch_bits != 0 || digit != lg::SORT_RADIX_BITS))
+        return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_sort_pairs: 16-bit keys have no tail, bias, begin_bit, positions or other digit width%s");
+    if (n == 0) return 0;
+    if (!key_a || !key_b || !val_b || !scratch || (!val_a && !vals_are_positions))
+        return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_sort_pairs: NULL required pointer%s");
+    int side;
+    if (key_bytes == 2) {
+        side = lg::launch_radix_sort_pairs16(static_cast<uint16_t*>(key_a), static_cast<uint16_t*>(key_b), val_a, val_b, n, end_bit, scratch, stream, n_dev);
+    } else {
+        lg::RadixTail tail; tail.src = tail_src; tail.dst = tail_dst; tail.mode = tail_mode;
+        lg::KeyBias kb; kb.kmin = (uint32_t)kmin; kb.cull = (uint32_t)cull;
+        side = lg::launch_radix_sort_pairs(static_cast<uint32_t*>(key_a), static_cast<uint32_t*>(key_b), val_a, val_b, n, end_bit, scratch, stream, max_bits,
+                                           n_dev, scratch_bits, vals_are_positions != 0, tail, begin_bit, bias_on ? &kb : nullptr);
+    }
+    LG_STAGE_CHECK("debug sort pairs");
+    return side;
+}
+
+int lidargs_debug_range_sort_rest(size_t key_min, size_t key_max, unsigned* plan) {
+    if (!plan || key_min > 0xFFFFFFFFull || key_max > 0xFFFFFFFFull) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_range_sort_rest: bad argument%s");
+    const lg::RangeSortRest r = lg::range_sort_rest(~(uint32_t)key_min, (uint32_t)key_max);
+    plan[0] = r.bias.kmin; plan[1] = r.bias.cull; plan[2] = (unsigned)r.end_bit; plan[3] = (unsigned)r.max_bits;
+    return 0;
+}
+
+int lidargs_debug_range_sort_buckets(size_t P, unsigned* key_a, unsigned* key_b, unsigned* id_a, unsigned* id_b, unsigned* scratch,
+                                     const unsigned* key_span, int tail_mode, const void* tail_src, void* tail_dst, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const int debug = 0;
+    if (P > (size_t)std::numeric_limits<int>::max()) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_range_sort_buckets: bad size%s");
+    if (!lg::range_sort_buckets_ok(P)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_range_sort_buckets: no frame of this size takes the bucketed form%s");
+    if (tail_mode < 1 || tail_mode > 2) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_range_sort_buckets: tail_mode must be 1 or 2%s");
+    if (!key_a || !key_b || !id_a || !id_b || !scratch || !key_span || !tail_src || !tail_dst)
+        return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_range_sort_buckets: NULL required pointer%s");
+    lg::RadixTail tail; tail.src = tail_src; tail.dst = tail_dst; tail.mode = tail_mode;
+    lg::launch_range_sort_buckets(key_a, key_b, id_a, id_b, P, scratch, key_span, tail, stream);
+    LG_STAGE_CHECK("debug range sort buckets");
     return 0;
 }
 

@@ -662,6 +662,7 @@ __global__ void __launch_bounds__(64 * SMALL_SORT_WAVES) k_radix_sort_small(KT* 
     __shared__ uint32_t cnt[256][SMALL_SORT_WAVES + 1];                // [digit][wave] counts, then bases (+1: no bank conflicts down a column)
     __shared__ uint32_t wsum[SMALL_SORT_WAVES];
     if (n_dev) n = min(n, *n_dev);
+    if (n == 0) return;                                                // (uniform; a device-side count of 0: wg_radix_sort's clamped loads need one pair)
     wg_radix_sort<KT>(key_a, key_b, val_a, val_b, n, begin_bit, end_bit, max_bits, vals_are_positions, tail, km, cnt, wsum);
 }
 

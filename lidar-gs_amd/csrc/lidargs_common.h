@@ -389,6 +389,19 @@ struct RadixTail { const void* src = nullptr; void* dst = nullptr; int mode = 0;
 // has to cover the frame's key SPAN.  With kmin a multiple of 256 the low byte of key - kmin is the key's own low byte: a first pass
 // over bits [0, 8) needs no bias and can be queued before the host knows the span.
 struct KeyBias { uint32_t kmin, cull; const uint32_t* lin_span = nullptr; };   // lin_span (device, binning.hip KeyMap): linear range buckets instead
+// The second call of the range sort cut in two (api.hip bin_frame; the first sorted bits [0, 8) before the host knew the span): from the
+// frame's (~smallest, largest) visible key, the bias, the bits [8, end_bit) left to sort -- at least one pass, for the tail -- and the digit width.
+struct RangeSortRest { KeyBias bias; int end_bit, max_bits; };
+inline RangeSortRest range_sort_rest(uint32_t kinv, uint32_t kmax) {
+    RangeSortRest r;
+    r.bias.kmin = (~kinv) & ~255u;                                      // a multiple of 256: (key - kmin) & 255 == key & 255
+    if (kmax < r.bias.kmin) { r.bias.kmin = 0u; kmax = 0u; }           // no visible Gaussian: every key is the culled one
+    r.bias.cull = ((kmax - r.bias.kmin) | 255u) + 1u;                   // above every valid key - kmin in the bits the later passes sort on
+    r.end_bit = 32 - __builtin_clz(r.bias.cull | 1u);
+    if (r.end_bit < 9) r.end_bit = 9;
+    r.max_bits = r.end_bit > 26 ? 8 : 9;                               // passes of at most 9 bits
+    return r;
+}
 int launch_radix_sort_pairs(uint32_t* key_a, uint32_t* key_b, uint32_t* val_a, uint32_t* val_b, size_t n, int end_bit,
                             uint32_t* scratch, hipStream_t s, int max_bits = 0, const uint32_t* n_dev = nullptr, int scratch_bits = 0,
                             bool vals_are_positions = false,    // true: the values are 0..n-1 and val_a is never read
