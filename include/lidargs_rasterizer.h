@@ -559,6 +559,48 @@ int lidargs_debug_range_sort_rest(size_t key_min, size_t key_max, unsigned* plan
 int lidargs_debug_range_sort_buckets(size_t P, unsigned* key_a, unsigned* key_b, unsigned* id_a, unsigned* id_b, unsigned* scratch,
                                      const unsigned* key_span, int tail_mode, const void* tail_src, void* tail_dst, void* stream);
 
+/* Test hooks of the stage between and behind the sorts (no reference counterpart as entry points; never called by the binding): the
+ * library's own launchers of the exclusive scan, the instance emit and the tile ranges on caller-supplied arrays, so that tests/ can hold
+ * them word for word against a numpy restatement (tests/binning_ref.py).  Device pointers; nothing waits for the stream; no dispatch is
+ * decided here.  Each returns 0 or a negative LIDARGS_ERR_*.
+ *
+ * lidargs_debug_exclusive_scan: out[i] = in[0] + ... + in[i - 1] (mod 2^32) for i < n, *total_out (nullable) = the sum of all n.  out may
+ * equal in (it may not overlap it otherwise).  scratch holds lidargs_debug_scan_scratch_words(n) words.  n = 0: only *total_out is
+ * written.  Refused: n > INT_MAX.
+ *
+ * lidargs_debug_emit_instances: the instance lists of P Gaussians in range order, as a frame's binning queues them: the block sums
+ * (launch_instance_offsets, scanned there if scan_block_sums, otherwise added up by the emit itself) and then the emit.
+ *   ids_sorted u32[P]: the Gaussian of every position (read only where the record has instances).
+ *   span_sorted: compact = 0: u32x2[P] = (xspan, rowspan) = (x0 | x1 << 16, lo | hi << 16), as RadixTail mode 2 leaves them: tile
+ *     columns [x0, x1) of 16 pixels, pixel rows [lo, hi).  compact = 1: u32[P], x0 | (x1 - x0 - 1) << 8 | lo << 16 | (hi - 1) << 24, and
+ *     0xFFFFFFFF = no instances.  PRECONDITIONS on a record, not checked (the preprocess kernels keep them): xspan == 0 (no instances,
+ *     the row span is then not looked at) or x1 > x0; hi > lo; x1 <= 2 * tiles_x (a span across the seam of the panorama is unwrapped by
+ *     ONE subtraction of tiles_x); every tile id ((lo >> log2 tile_rows) + ry) * tiles_x + tx < tiles_x * tiles_y, and < 2^(8 key_bytes);
+ *     the instance total of all P records < 2^32.  The compact form cannot hold x0 = 255, x1 = 511, lo = 255, hi = 256 at once: that word
+ *     is the one that says "no instances" (no frame has such a span: one across the seam is narrower than the grid).
+ *   Gaussian i has (x1 - x0) * (((hi - 1) >> s) - (lo >> s) + 1) instances, s = log2 tile_rows, row-major (tile row outer, column inner);
+ *   instance j of the whole list gets tile id -> inst_tile[j] (u16 or u32, key_bytes) and ids_sorted[i] -> inst_val[j], for j < cap alone
+ *   (cap = 0xFFFFFFFF: no cut; nothing at or behind min(total, cap) is written).
+ *   block_off: (P + 1023) / 1024 words; left holding the exclusive instance offset of every block of 1024 records (scan_block_sums = 1)
+ *   or its instance count (0).  *total_out = the instance total, uncut -- written with scan_block_sums = 1 ALONE (a frame that takes the
+ *   other form has the total from its preprocess).  ranges (nullable): u32x2[tiles_x * tiles_y], cleared by the emit's launch.
+ *   Refused: tile_rows not 4, 8, 16 or 32; key_bytes not 2 or 4; key_bytes = 2 with more than 65536 tiles; compact with tiles_x > 256;
+ *   a grid of more than INT_MAX tiles; P or cap beyond 32 bits.  P = 0: returns 0, nothing is launched or written.
+ *
+ * lidargs_debug_tile_ranges: ranges[t] = (first, last + 1) position of tile t among the first Rn = min(R, *R_dev) (R_dev nullable) sorted
+ * keys, (0, 0) for a tile without keys; every one of the `tiles` entries is written if prezeroed = 0, only those of the tiles present if
+ * prezeroed = 1 (the caller -- in a frame the emit's launch -- has cleared the rest; with Rn = 0 all are cleared in either form).  The
+ * n_zero words at `zero` (nullable: then nothing) are cleared.  PRECONDITIONS: tile_sorted is 16-byte aligned and READABLE up to R rounded
+ * up to a multiple of 8 keys (whole 16-byte loads; what lies at or behind Rn is not looked at); the first Rn keys ascend and are < tiles;
+ * tiles <= 65536 with key_bytes = 2. */
+size_t lidargs_debug_scan_scratch_words(size_t n);
+int lidargs_debug_exclusive_scan(size_t n, const unsigned* in, unsigned* out, unsigned* total_out, unsigned* scratch, void* stream);
+int lidargs_debug_emit_instances(size_t P, int compact, int tile_rows, int tiles_x, int tiles_y, const unsigned* ids_sorted, const void* span_sorted,
+                                 unsigned* block_off, unsigned* total_out, int scan_block_sums, int key_bytes, void* inst_tile, unsigned* inst_val,
+                                 size_t cap, unsigned* ranges, void* stream);
+int lidargs_debug_tile_ranges(size_t R, int key_bytes, const void* tile_sorted, const unsigned* R_dev, unsigned* ranges, int tiles, unsigned* zero,
+                              int n_zero, int prezeroed, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

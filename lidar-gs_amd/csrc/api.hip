@@ -871,6 +871,61 @@ int lidargs_debug_range_sort_buckets(size_t P, unsigned* key_a, unsigned* key_b,
     return 0;
 }
 
+// Test hooks of the scan, the instance emit and the tile ranges (binning.hip): the product's own launchers on caller-supplied arrays.
+size_t lidargs_debug_scan_scratch_words(size_t n) { return lg::scan_scratch_words(n); }
+
+int lidargs_debug_exclusive_scan(size_t n, const unsigned* in, unsigned* out, unsigned* total_out, unsigned* scratch, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const int debug = 0;
+    if (n > (size_t)std::numeric_limits<int>::max()) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_exclusive_scan: bad size%s");
+    if (n != 0 && (!in || !out || !scratch)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_exclusive_scan: NULL required pointer%s");
+    lg::launch_exclusive_scan(in, out, n, total_out, scratch, stream);
+    LG_STAGE_CHECK("debug exclusive scan");
+    return 0;
+}
+
+int lidargs_debug_emit_instances(size_t P, int compact, int tile_rows, int tiles_x, int tiles_y, const unsigned* ids_sorted, const void* span_sorted,
+                                 unsigned* block_off, unsigned* total_out, int scan_block_sums, int key_bytes, void* inst_tile, unsigned* inst_val,
+                                 size_t cap, unsigned* ranges, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const int debug = 0;
+    if (!(tile_rows == 4 || tile_rows == 8 || tile_rows == 16 || tile_rows == 32))
+        return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_emit_instances: tile_rows must be 4, 8, 16 or 32%s");
+    if (key_bytes != 2 && key_bytes != 4) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_emit_instances: key_bytes must be 2 or 4%s");
+    if (tiles_x <= 0 || tiles_y <= 0 || (long long)tiles_x * tiles_y > (long long)std::numeric_limits<int>::max())
+        return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_emit_instances: bad grid%s");
+    if (key_bytes == 2 && (long long)tiles_x * tiles_y > 65536) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_emit_instances: 16-bit keys hold at most 65536 tiles%s");
+    if (compact && tiles_x > 256) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_emit_instances: compact records hold at most 256 tile columns%s");
+    if (P > (size_t)std::numeric_limits<int>::max() || cap > 0xFFFFFFFFull) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_emit_instances: bad size%s");
+    if (P == 0) return 0;                                              // (the launchers would ask for a grid of zero blocks)
+    if (!ids_sorted || !span_sorted || !block_off || !inst_tile || !inst_val || (scan_block_sums && !total_out))
+        return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_emit_instances: NULL required pointer%s");
+    lg::TileGrid grid{};
+    grid.TH = tile_rows; grid.tiles_x = grid.ref_tiles_x = grid.x_n = tiles_x; grid.tiles_y = tiles_y;
+    grid.W = 16 * tiles_x; grid.H = tile_rows * tiles_y; grid.waves_per_tile = 1;
+    lg::launch_instance_offsets(span_sorted, compact != 0, tile_rows, block_off, total_out, P, stream, scan_block_sums != 0);
+    LG_STAGE_CHECK("debug instance offsets");
+    lg::launch_emit_instances(ids_sorted, block_off, span_sorted, compact != 0, P, grid, static_cast<uint32_t*>(inst_tile), inst_val, stream, (uint32_t)cap,
+                              key_bytes == 2, reinterpret_cast<uint2*>(ranges), scan_block_sums == 0);
+    LG_STAGE_CHECK("debug emit instances");
+    return 0;
+}
+
+int lidargs_debug_tile_ranges(size_t R, int key_bytes, const void* tile_sorted, const unsigned* R_dev, unsigned* ranges, int tiles, unsigned* zero,
+                              int n_zero, int prezeroed, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const int debug = 0;
+    if (key_bytes != 2 && key_bytes != 4) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_tile_ranges: key_bytes must be 2 or 4%s");
+    if (R > (size_t)std::numeric_limits<int>::max() || tiles < 0 || n_zero < 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_tile_ranges: bad size%s");
+    if (key_bytes == 2 && tiles > 65536) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_tile_ranges: 16-bit keys hold at most 65536 tiles%s");
+    if ((tiles && !ranges) || (R && !tile_sorted)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_tile_ranges: NULL required pointer%s");
+    if (reinterpret_cast<uintptr_t>(tile_sorted) & 15u) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_tile_ranges: tile_sorted must be 16-byte aligned%s");
+    lg::launch_tile_ranges(static_cast<const uint32_t*>(tile_sorted), R, reinterpret_cast<uint2*>(ranges), tiles, stream, R_dev, key_bytes == 2, zero, n_zero,
+                           prezeroed != 0);
+    LG_STAGE_CHECK("debug tile ranges");
+    return 0;
+}
+
 int lidargs_forward_shell(lidargs_alloc_fn geometry_alloc, void* geometry_user, lidargs_alloc_fn binning_alloc, void* binning_user,
                           lidargs_alloc_fn image_alloc, void* image_user, int P, const float* background, int width, int height,
                           const float* means3D, const float* colors_precomp, const float* opacities, const float* scales,
