@@ -8,8 +8,11 @@
  * keeping only the offsets whose neural opacity is > 0, in (anchor, offset) order.
  *
  * Supported model configuration (the reference's defaults, arguments/__init__.py:51-79): feat_dim 32, hidden 32,
- * n_offsets in {4,5,6,8,10}, appearance_dim 0, use_feat_bank false, colour channels 2.  Anything else is the caller's job to
- * reject (the Python front-end does, loudly).
+ * n_offsets in {4,5,6,8,10}, colour channels 2.  Anything else is the caller's job to reject (the Python front-end does, loudly).
+ * The two model options run IN FRONT of these entry points, which do not change for them (include_decode/lidargs_decode_options.h,
+ * a library of its own): with use_feat_bank the caller passes lidargs_ng_bank_forward's feat_out as `anchor_feat` and hands
+ * dL_danchor_feat to lidargs_ng_bank_backward; with appearance_dim > 0 the colour and ray-drop heads' W1 / b1 of the model struct
+ * are lidargs_ng_appearance_fold's packed [32][din] weights and folded biases.
  *
  * All pointers are device pointers unless stated otherwise; plain float32 row-major arrays; no torch types.  Functions return 0
  * or a positive count on success, a negative LIDARGS_ERR_* code on failure (message: lidargs_last_error()).

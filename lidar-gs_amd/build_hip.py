@@ -4,6 +4,7 @@
 
 Output: lidar-gs_amd/diff_lidargs_rasterization/liblidargs_hip.so  (git-ignored, travels with gpurun)
         lidar-gs_amd/lidargs_optim/liblidargs_optim.so             (the optimizer step: csrc/adam.hip alone, include_optim/)
+        lidar-gs_amd/liblidargs_decode_options.so                  (feature bank + appearance in front of the decode: csrc/decode_options.hip alone, include_decode/)
 
 Per-file flags: the per-Gaussian kernels (preprocess.hip) are HBM-bound, so they are built with
 -ffp-contract=off: every expression rounds as written, which keeps the unit vectors s = p/|p| that
@@ -42,6 +43,14 @@ OPTIM_INCLUDE = os.path.join(HERE, "..", "include_optim")
 OPTIM_SOURCES = {
     "adam.hip": ["-ffp-contract=off"],             # torch's op-by-op roundings; the steps its device kernels fuse are written as fmaf
 }
+# The decode's two model options (use_feat_bank, appearance_dim > 0): new entry points beside the decode's, a target and a header
+# directory of their own like the optimizer's.
+DECODE_OUT = os.path.join(HERE, "liblidargs_decode_options.so")
+DECODE_INCLUDE = os.path.join(HERE, "..", "include_decode")
+DECODE_SOURCES = {
+    "decode_options.hip": [],
+}
+_OWN_TARGET = {**OPTIM_SOURCES, **DECODE_SOURCES}          # sources that are not part of liblidargs_hip.so
 
 
 def build_id():
@@ -51,7 +60,8 @@ def build_id():
     h = hashlib.sha1()
     files = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC)) + sorted(
         os.path.join(HERE, "..", "include", f) for f in os.listdir(os.path.join(HERE, "..", "include"))) + sorted(
-        os.path.join(OPTIM_INCLUDE, f) for f in os.listdir(OPTIM_INCLUDE)) + [os.path.abspath(__file__)]
+        os.path.join(OPTIM_INCLUDE, f) for f in os.listdir(OPTIM_INCLUDE)) + sorted(
+        os.path.join(DECODE_INCLUDE, f) for f in os.listdir(DECODE_INCLUDE)) + [os.path.abspath(__file__)]
     for f in files:
         h.update(os.path.basename(f).encode()); h.update(open(f, "rb").read())
     return h.hexdigest()[:12]
@@ -78,7 +88,7 @@ def _stale(out, deps):
 
 
 def needs_build():
-    return _stale(OUT, [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f not in OPTIM_SOURCES]
+    return _stale(OUT, [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f not in _OWN_TARGET]
                   + [os.path.join(HERE, "..", "include", "lidargs_rasterizer.h"), __file__])
 
 
@@ -87,12 +97,17 @@ def optim_needs_build():
                   + [os.path.join(OPTIM_INCLUDE, f) for f in os.listdir(OPTIM_INCLUDE)] + [__file__])
 
 
+def decode_needs_build():
+    return _stale(DECODE_OUT, [os.path.join(CSRC, f) for f in DECODE_SOURCES]
+                  + [os.path.join(DECODE_INCLUDE, f) for f in os.listdir(DECODE_INCLUDE)] + [__file__])
+
+
 def build(force=False, verbose=False):
     """Up-to-date check and build under an exclusive file lock: the ranks of `bench.py --gpus N` (one process per GPU) all call this
     at start-up, and only the first may compile -- the others wait and then find the library up to date.  The link goes to a
     temporary name and is moved into place, so a process that loaded the library earlier never sees a half-written file.
-    Builds both libraries, each when its own dependencies are newer; returns the main library's path."""
-    if not force and not needs_build() and not optim_needs_build():
+    Builds the three libraries, each when its own dependencies are newer; returns the main library's path."""
+    if not force and not needs_build() and not optim_needs_build() and not decode_needs_build():
         return OUT
     import fcntl
     os.makedirs(OBJ, exist_ok=True)
@@ -103,6 +118,8 @@ def build(force=False, verbose=False):
                 _build_locked(SOURCES, OUT, verbose)
             if force or optim_needs_build():
                 _build_locked(OPTIM_SOURCES, OPTIM_OUT, verbose)
+            if force or decode_needs_build():
+                _build_locked(DECODE_SOURCES, DECODE_OUT, verbose)
             return OUT
         finally:
             fcntl.flock(lock, fcntl.LOCK_UN)

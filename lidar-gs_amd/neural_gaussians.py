@@ -5,17 +5,38 @@ Same signature and return values as the reference function; a checkout switches 
 framework ops of the reference become three native calls (include/lidargs_neural_gaussians.h); the eight weight gradients
 are the plain GEMMs torch already does well (hipBLASLt), fed by the per-anchor deltas the backward kernel writes.
 
-Model configurations outside the native kernel's scope (feature bank, appearance embedding, colour channels != 2, feature /
-hidden width != 32, n_offsets not in {4,5,6,8,10}) raise NotImplementedError: there is no silent framework fallback.
+The two model options of GaussianModel's constructor run in front of the unchanged decode (include_decode/lidargs_decode_options.h,
+liblidargs_decode_options.so): `use_feat_bank=True` is one native call that writes the view-adapted features the decode then reads
+(`_FeatBank`), and `appearance_dim > 0` one that packs the colour and ray-drop heads' first layer to the decode's width and folds the
+frame's embedding vector into their bias (`_AppearanceFold`); each has one native backward.  With both options off the call sequence
+is the decode's alone.
+
+Model configurations outside the native kernels' scope (colour channels != 2, feature / hidden width != 32, n_offsets not in
+{4,5,6,8,10}, a feature-bank MLP of another layout, an appearance module that is not an nn.Embedding) raise NotImplementedError:
+there is no silent framework fallback.
 """
 import ctypes as C
 import os
 
 import torch
 
+import lidargs_abi
 from diff_lidargs_rasterization import _C as _base
 
 _lib = _base._lib
+_HERE = os.path.dirname(os.path.abspath(__file__))
+OPTIONS_INCLUDE = os.path.normpath(os.path.join(_HERE, "..", "include_decode"))
+OPTIONS_ABI_VERSION = 1     # LIDARGS_NG_OPTIONS_ABI_VERSION of include_decode/lidargs_decode_options.h
+_OPTIONS_LIB = None
+
+
+def _options_lib():
+    """liblidargs_decode_options.so, loaded and typed on the first use of an option: a model with both options off never needs it."""
+    global _OPTIONS_LIB
+    if _OPTIONS_LIB is None:
+        _OPTIONS_LIB = lidargs_abi.load(os.path.join(_HERE, "liblidargs_decode_options.so"), include=OPTIONS_INCLUDE,
+                                        version_fn="lidargs_ng_options_abi_version", version=OPTIONS_ABI_VERSION, package="neural_gaussians")
+    return _OPTIONS_LIB
 MLP_ORDER = ("opacity", "cov", "color", "raydrop")
 
 
@@ -235,6 +256,135 @@ class _Decode(torch.autograd.Function):
         return (d_feat, d_anchor, d_offset, d_scaling, *g_params, None, None, None)
 
 
+def _check_opt(rc, what):
+    if rc < 0:
+        raise RuntimeError(f"{what} failed with code {rc}: {_options_lib().lidargs_ng_options_last_error().decode(errors='replace')}")
+
+
+class _FeatBank(torch.autograd.Function):
+    """anchor_feat [N,32], anchor [N,3], W1 [32,4], b1 [32], W2 [3,32], b2 [3] of the bank MLP; cam (3 floats, host), visible_mask
+    (bool[N] or None) -> feat' [N,32], zero rows for invisible anchors (gaussian_renderer/__init__.py:37-47)."""
+
+    @staticmethod
+    def forward(ctx, anchor_feat, anchor, W1, b1, W2, b2, cam, visible_mask):
+        _base._require_device(anchor, "anchor")
+        for t, name in ((anchor_feat, "anchor_feat"), (W1, "mlp_feature_bank[0].weight"), (b1, "mlp_feature_bank[0].bias"),
+                        (W2, "mlp_feature_bank[2].weight"), (b2, "mlp_feature_bank[2].bias")):
+            _base._require_device(t, name)
+        dev = anchor.device
+        anchor_feat, anchor, W1, b1, W2, b2 = (_f32c(t) for t in (anchor_feat, anchor, W1, b1, W2, b2))
+        N = int(anchor.shape[0])
+        vis = None if visible_mask is None else visible_mask.to(torch.bool).contiguous().view(torch.uint8)
+        if tuple(anchor_feat.shape) != (N, 32) or tuple(anchor.shape) != (N, 3) or (vis is not None and (vis.numel() != N or vis.device != dev)):
+            raise RuntimeError("neural_gaussians: anchor_feat [N,32], anchor [N,3] and visible_mask [N] must agree in N and device")
+        camv = (C.c_float * 3)(*[float(c) for c in cam])
+        out = torch.empty((N, 32), dtype=torch.float32, device=dev)      # every row is written by the kernel
+        p = _base._ptr
+        with torch.cuda.device(dev):
+            _check_opt(_options_lib().lidargs_ng_bank_forward(N, p(vis), p(anchor_feat), p(anchor), camv, p(W1), p(b1), p(W2), p(b2), p(out),
+                                                    _base._stream(dev)), "lidargs_ng_bank_forward")
+        ctx.save_for_backward(anchor_feat, anchor, W1, b1, W2, b2, vis if vis is not None else torch.empty(0, dtype=torch.uint8, device=dev))
+        ctx.meta = (N, tuple(float(c) for c in cam), vis is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        anchor_feat, anchor, W1, b1, W2, b2, vis = ctx.saved_tensors
+        N, cam, masked = ctx.meta
+        dev = anchor.device
+        g_out = _f32c(g_out)
+        camv = (C.c_float * 3)(*cam)
+        dense = torch.empty(N * 35, dtype=torch.float32, device=dev)      # d_feat | d_anchor: every row is written by the kernel
+        nfl = _options_lib().lidargs_ng_bank_backward_partial_floats(N)
+        flat = torch.empty(259 + nfl, dtype=torch.float32, device=dev) if N else torch.zeros(259, dtype=torch.float32, device=dev)
+        p = _base._ptr
+        if N:
+            base = dense.data_ptr()
+            with torch.cuda.device(dev):
+                _check_opt(_options_lib().lidargs_ng_bank_backward(N, p(vis) if masked else None, p(anchor_feat), p(anchor), camv, p(W1), p(b1), p(W2),
+                                                         p(b2), p(g_out), C.c_void_p(base), C.c_void_p(base + 4 * N * 32), p(flat),
+                                                         p(flat[259:]), nfl, _base._stream(dev)), "lidargs_ng_bank_backward")
+        return (dense[:N * 32].view(N, 32), dense[N * 32:].view(N, 3), flat[:128].view(32, 4), flat[128:160], flat[160:256].view(3, 32),
+                flat[256:259], None, None)
+
+
+class _AppearanceFold(torch.autograd.Function):
+    """W1 [32, din+A] and b1 [32] of the colour head, the same of the ray-drop head, the two embedding weights [num, A]; uid, din ->
+    W1 [32, din] and b1_eff [32] of the colour head, then of the ray-drop head: what the decode takes (gaussian_renderer/__init__.py:52-56,
+    :73-79 with the frame's one embedding row folded into the bias)."""
+
+    @staticmethod
+    def forward(ctx, W1c, b1c, W1r, b1r, emb_c, emb_r, uid, din):
+        for t, name in ((W1c, "mlp_color[0].weight"), (b1c, "mlp_color[0].bias"), (W1r, "mlp_raydrop[0].weight"), (b1r, "mlp_raydrop[0].bias"),
+                        (emb_c, "embedding_appearance.weight"), (emb_r, "embedding_appearance_rd.weight")):
+            _base._require_device(t, name)
+        dev = W1c.device
+        W1c, b1c, W1r, b1r, emb_c, emb_r = (_f32c(t) for t in (W1c, b1c, W1r, b1r, emb_c, emb_r))
+        A = int(emb_c.shape[1])
+        out = torch.empty(64 * din + 64, dtype=torch.float32, device=dev)
+        p = _base._ptr
+        with torch.cuda.device(dev):
+            _check_opt(_options_lib().lidargs_ng_appearance_fold(din, A, p(W1c), p(b1c), p(emb_c[uid]), p(W1r), p(b1r), p(emb_r[uid]), p(out),
+                                                       p(out[64 * din:]), _base._stream(dev)), "lidargs_ng_appearance_fold")
+        ctx.save_for_backward(W1c, W1r, emb_c, emb_r)
+        ctx.meta = (uid, din, A)
+        return (out[:32 * din].view(32, din), out[64 * din:64 * din + 32], out[32 * din:64 * din].view(32, din), out[64 * din + 32:])
+
+    @staticmethod
+    def backward(ctx, g_W1c, g_b1c, g_W1r, g_b1r):
+        W1c, W1r, emb_c, emb_r = ctx.saved_tensors
+        uid, din, A = ctx.meta
+        dev = W1c.device
+        g_W1c, g_b1c, g_W1r, g_b1r = (_f32c(g) for g in (g_W1c, g_b1c, g_W1r, g_b1r))
+        full = torch.empty((2, 32, din + A), dtype=torch.float32, device=dev)
+        d_emb_c, d_emb_r = torch.zeros_like(emb_c), torch.zeros_like(emb_r)          # dense, as nn.Embedding's: the kernel writes row uid
+        p = _base._ptr
+        with torch.cuda.device(dev):
+            _check_opt(_options_lib().lidargs_ng_appearance_backward(din, A, p(W1c), p(emb_c[uid]), p(W1r), p(emb_r[uid]), p(g_W1c), p(g_b1c), p(g_W1r),
+                                                           p(g_b1r), p(full), p(d_emb_c[uid]), p(d_emb_r[uid]), _base._stream(dev)),
+                       "lidargs_ng_appearance_backward")
+        return full[0], g_b1c, full[1], g_b1r, d_emb_c, d_emb_r, None, None
+
+
+def _bank_mlp(pc):
+    """Weights of the feature-bank MLP after checking its WHOLE layout, Linear(4,32)-ReLU-Linear(32,3)-Softmax(dim=1)
+    (scene/gaussian_model.py:105-111), as `_linear_pair` checks the four heads."""
+    import torch.nn as nn
+    seq = getattr(pc, "get_featurebank_mlp", None)
+    if seq is None:
+        raise NotImplementedError("neural_gaussians: use_feat_bank=True on a model without a feature-bank MLP (pc.get_featurebank_mlp)")
+    try:
+        mods = list(seq)
+    except TypeError:
+        mods = [seq]
+    want = [nn.Linear, nn.ReLU, nn.Linear, nn.Softmax]
+    ok = len(mods) == 4 and all(type(m) is w for m, w in zip(mods, want))
+    if ok:
+        ok = (mods[0].in_features, mods[0].out_features, mods[2].in_features, mods[2].out_features) == (4, 32, 32, 3) \
+            and mods[0].bias is not None and mods[2].bias is not None and mods[3].dim in (1, -1)
+    if not ok:
+        layout = "-".join(type(m).__name__ for m in mods)
+        raise NotImplementedError(f"neural_gaussians: unsupported feature-bank MLP [{layout}]: the native bank handles exactly "
+                                  "Linear(4,32)-ReLU-Linear(32,3)-Softmax(dim=1)")
+    return mods[0].weight, mods[0].bias, mods[2].weight, mods[2].bias
+
+
+def _embedding_weight(module, what, A):
+    """The weight of pc.get_appearance / pc.get_appearance_rd: an nn.Embedding, or an object whose `.embedding` is one
+    (scene/embedding.py:69).  Anything else -- a torch.jit module loaded from a checkpoint, an embedding that renormalises or pads --
+    would compute something the fold does not, and is refused."""
+    import torch.nn as nn
+    emb = module if type(module) is nn.Embedding else getattr(module, "embedding", None)
+    if type(emb) is not nn.Embedding:
+        raise NotImplementedError(f"neural_gaussians: unsupported {what} module {type(module).__name__}: the native appearance path "
+                                  "handles an nn.Embedding (or an object whose .embedding is one)")
+    if emb.max_norm is not None or emb.padding_idx is not None:
+        raise NotImplementedError(f"neural_gaussians: {what}: an nn.Embedding with max_norm or padding_idx is not supported")
+    if emb.embedding_dim != A:
+        raise NotImplementedError(f"neural_gaussians: {what}: embedding_dim {emb.embedding_dim} != appearance_dim {A}")
+    return emb.weight
+
+
 def _linear_pair(seq, what, head):
     """Weights of one of the four MLPs after checking its WHOLE layout: the native decode hard-codes Linear(din, 32) - ReLU -
     Linear(32, dout) followed by `head` (scene/gaussian_model.py:113-142: Tanh for opacity, none for cov, Sigmoid for colour and
@@ -274,10 +424,7 @@ def _camera_center_host(viewpoint_camera):
 
 def generate_neural_gaussians(viewpoint_camera, pc, visible_mask=None, is_training=False):
     """Drop-in for gaussian_renderer.generate_neural_gaussians (:17-119): same arguments, same 5- or 7-tuple."""
-    if getattr(pc, "use_feat_bank", False):
-        raise NotImplementedError("neural_gaussians: use_feat_bank=True is not supported by the native decode")
-    if getattr(pc, "appearance_dim", 0) > 0:
-        raise NotImplementedError("neural_gaussians: appearance_dim > 0 is not supported by the native decode")
+    use_bank, A = bool(getattr(pc, "use_feat_bank", False)), int(getattr(pc, "appearance_dim", 0))
     if getattr(pc, "color_channel", 2) != 2:
         raise NotImplementedError("neural_gaussians: colour channels other than 2 (intensity + ray-drop) are not supported")
     anchor_feat, anchor, offset, scaling = pc._anchor_feat, pc.get_anchor, pc._offset, pc.get_scaling
@@ -290,7 +437,22 @@ def generate_neural_gaussians(viewpoint_camera, pc, visible_mask=None, is_traini
     params = (*_linear_pair(pc.get_opacity_mlp, "opacity", nn.Tanh), *_linear_pair(pc.get_cov_mlp, "cov", None),
               *_linear_pair(pc.get_color_mlp, "color", nn.Sigmoid), *_linear_pair(pc.get_raydrop_mlp, "raydrop", nn.Sigmoid))
     flags = (bool(pc.add_opacity_dist), bool(pc.add_cov_dist), bool(pc.add_color_dist))
+    bank = _bank_mlp(pc) if use_bank else None
+    if A > 0:
+        din = 35 + int(flags[2])
+        emb_c = _embedding_weight(getattr(pc, "get_appearance", None), "get_appearance", A)
+        emb_r = _embedding_weight(getattr(pc, "get_appearance_rd", None), "get_appearance_rd", A)
+        if params[8].shape[1] != din + A or params[12].shape[1] != din + A:
+            raise NotImplementedError(f"neural_gaussians: the colour and ray-drop MLPs' first layer must take {din} + appearance_dim = "
+                                      f"{din + A} inputs (found {params[8].shape[1]} and {params[12].shape[1]})")
+        uid = int(viewpoint_camera.uid)
+        if not (0 <= uid < emb_c.shape[0] and uid < emb_r.shape[0]):
+            raise IndexError(f"neural_gaussians: camera uid {uid} is out of range of the appearance embedding ({emb_c.shape[0]} rows)")
+        folded = _AppearanceFold.apply(params[8], params[9], params[12], params[13], emb_c, emb_r, uid, din)
+        params = (*params[:8], folded[0], folded[1], *params[10:12], folded[2], folded[3], *params[14:])
     cam = _camera_center_host(viewpoint_camera)
+    if bank is not None:
+        anchor_feat = _FeatBank.apply(anchor_feat, anchor, *bank, cam, visible_mask)
     xyz, color, opacity, scal, rot, neural_opacity, mask = _Decode.apply(anchor_feat, anchor, offset, scaling, *params, cam, visible_mask, flags)
     if is_training:
         return xyz, color, opacity, scal, rot, neural_opacity, mask
