@@ -35,16 +35,84 @@ static size_t ng_carve(char* base, size_t N, size_t k, NgScratch* v) {
     return (size_t)(c.p - base) + 256;
 }
 
+// ---- the layouts, stated once ---------------------------------------------------------------------------------------------------
+// delta2 / W2 / b2 of the four MLPs side by side: columns [k | 7k | k | k] = opacity, covariance, colour, ray-drop
+constexpr bool ng_valid_k(int k) { return k == 4 || k == 5 || k == 6 || k == 8 || k == 10; }
+constexpr int ng_dout(int m, int k) { return m == NG_COV ? 7 * k : k; }
+constexpr int ng_col0(int m, int k) { return m == NG_OPA ? 0 : (m == NG_COV ? k : (m == NG_COL ? 8 * k : 9 * k)); }   // a row is 10 k wide
+// a partial row of the matrix-pipe backward: 32 x 32 tiles of G1 (four MLPs and their narrow columns) and G2, then 128 bias sums
+#define NG_COV_TILES(K) ((7 * (K) + 31) / 32)
+#define NG_G2_TILES(K) (3 + NG_COV_TILES(K))       // opacity, covariance (1-3), colour, ray-drop
+constexpr int ng_partial_floats(int k) { return (5 + NG_G2_TILES(k)) * 1024 + 128; }
+
+// ---- the per-offset math, stated once: values in, values out, operation order as the reference's (the three generations of kernels
+//      below differ in how they multiply matrices and move data, not in this) --------------------------------------------------------
 __device__ __forceinline__ float ng_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
 
+// (view direction, distance) of an anchor seen from the camera  (:28-34)
+__device__ __forceinline__ float4 ng_view(float3 a, float3 cam) {
+    const float ox = a.x - cam.x, oy = a.y - cam.y, oz = a.z - cam.z;
+    const float dist = sqrtf(ox * ox + oy * oy + oz * oz);
+    return make_float4(ox / dist, oy / dist, oz / dist, dist);
+}
+// its VJP: view = ob / |ob|, dist = |ob| back to the anchor position (dx32..35: the gradient of inputs 32..35)
+__device__ __forceinline__ void ng_view_backward(float dx32, float dx33, float dx34, float dx35, float4 vd, float (&da)[3]) {
+    const float vx = vd.x, vy = vd.y, vz = vd.z, dist = vd.w;
+    const float dv = dx32 * vx + dx33 * vy + dx34 * vz;
+    da[0] += dx32 / dist - vx * (dv / dist) + dx35 * vx;
+    da[1] += dx33 / dist - vy * (dv / dist) + dx35 * vy;
+    da[2] += dx34 / dist - vz * (dv / dist) + dx35 * vz;
+}
+// nn.Tanh closes the opacity MLP (gaussian_model.py:118); an offset is kept where its opacity is positive (:67)
+struct NgOpacity { float o; bool keep; };
+__device__ __forceinline__ NgOpacity ng_opacity_out(float y) {
+    const float o = tanhf(y);
+    return {o, o > 0.0f};
+}
+// one selected (anchor, offset) pair: s = the anchor's six scalings, col / rd / sr[7] = its outputs of the colour, ray-drop and covariance MLPs
+struct NgRow { float3 xyz; float2 color; float3 scaling; float4 rot; };
+__device__ __forceinline__ NgRow ng_decode_row(float3 anchor, float3 of, const float (&s)[6], float col, float rd, const float* sr) {
+    NgRow r;
+    r.xyz = make_float3(anchor.x + of.x * s[0], anchor.y + of.y * s[1], anchor.z + of.z * s[2]);                        // :111-112
+    r.color = make_float2(ng_sigmoid(col), ng_sigmoid(rd));                                                            // :85-87
+    r.scaling = make_float3(s[3] * ng_sigmoid(sr[0]), s[4] * ng_sigmoid(sr[1]), s[5] * ng_sigmoid(sr[2]));             // :107
+    const float q0 = sr[3], q1 = sr[4], q2 = sr[5], q3 = sr[6];
+    const float qn = fmaxf(sqrtf(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3), 1e-12f);                                      // F.normalize, :108
+    r.rot = make_float4(q0 / qn, q1 / qn, q2 / qn, q3 / qn);
+    return r;
+}
+// the covariance head's backward for one pair: scaling = s[3:6] * sigmoid(sr[0:3]), rot = normalize(sr[3:7]), and the direct paths of
+// xyz / scaling.  gx / gs / gr: the pair's upstream gradients (zeros where it is not selected).  d[7]: delta2; returns d_offset; adds the
+// pair's share to the anchor's d_scaling (ds) and d_anchor (da)
+__device__ __forceinline__ float3 ng_cov_delta(const float* sr, const float (&s)[6], float3 of, float3 gx, float3 gs, float4 gr, float* d,
+                                               float (&ds)[6], float (&da)[3]) {
+    const float3 dof = make_float3(gx.x * s[0], gx.y * s[1], gx.z * s[2]);
+    ds[0] += gx.x * of.x; ds[1] += gx.y * of.y; ds[2] += gx.z * of.z;
+    da[0] += gx.x; da[1] += gx.y; da[2] += gx.z;
+    const float g0 = ng_sigmoid(sr[0]), g1 = ng_sigmoid(sr[1]), g2 = ng_sigmoid(sr[2]);
+    ds[3] += gs.x * g0; ds[4] += gs.y * g1; ds[5] += gs.z * g2;
+    d[0] = gs.x * s[3] * g0 * (1.f - g0); d[1] = gs.y * s[4] * g1 * (1.f - g1); d[2] = gs.z * s[5] * g2 * (1.f - g2);
+    const float q0 = sr[3], q1 = sr[4], q2 = sr[5], q3 = sr[6];
+    const float qn = fmaxf(sqrtf(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3), 1e-12f);
+    const float r0 = q0 / qn, r1 = q1 / qn, r2 = q2 / qn, r3 = q3 / qn;
+    const float dotp = gr.x * r0 + gr.y * r1 + gr.z * r2 + gr.w * r3;
+    d[3] = (gr.x - r0 * dotp) / qn; d[4] = (gr.y - r1 * dotp) / qn; d[5] = (gr.z - r2 * dotp) / qn; d[6] = (gr.w - r3 * dotp) / qn;
+    return dof;
+}
+// delta2 of one of the three k-output MLPs: WHICH 0 = opacity (tanh), 1 = colour, 2 = ray-drop (sigmoid)
+template <int WHICH>
+__device__ __forceinline__ float ng_head_delta(float y, float g) {
+    if (WHICH == 0) { const float o = tanhf(y); return g * (1.f - o * o); }
+    const float sg = ng_sigmoid(y);
+    return g * sg * (1.f - sg);
+}
 // x = (feature, view, distance)  (:28-34, :50)
 __device__ __forceinline__ void ng_input(const float* __restrict__ feat, const float* __restrict__ anchor, float3 cam, int i, float (&x)[NG_IN]) {
     const float4* f4 = reinterpret_cast<const float4*>(feat + (size_t)i * NG_FEAT);
 #pragma unroll
     for (int q = 0; q < NG_FEAT / 4; q++) { const float4 v = f4[q]; x[4 * q] = v.x; x[4 * q + 1] = v.y; x[4 * q + 2] = v.z; x[4 * q + 3] = v.w; }
-    const float ox = anchor[3 * (size_t)i] - cam.x, oy = anchor[3 * (size_t)i + 1] - cam.y, oz = anchor[3 * (size_t)i + 2] - cam.z;
-    const float dist = sqrtf(ox * ox + oy * oy + oz * oz);
-    x[32] = ox / dist; x[33] = oy / dist; x[34] = oz / dist; x[35] = dist;
+    const float4 vd = ng_view(make_float3(anchor[3 * (size_t)i], anchor[3 * (size_t)i + 1], anchor[3 * (size_t)i + 2]), cam);
+    x[32] = vd.x; x[33] = vd.y; x[34] = vd.z; x[35] = vd.w;
 }
 
 // hidden layer: h = relu(W1 x + b1); W1 is [32][din], din = 35 or 36 (wave-uniform -> scalar loads)
@@ -211,11 +279,10 @@ __device__ __forceinline__ void ng_bw_small(const NgModel& m, const float (&x)[N
         float g = 0.f;
         if (sel) g = WHICH == 0 ? g_opacity[r] : (WHICH == 1 ? g_color[2 * r] : g_color[2 * r + 1]);
         if (WHICH == 0 && g_no) g += g_no[c * K + j];                  // gradient of the un-masked neural_opacity output, if any
-        if (WHICH == 0) { const float o = tanhf(y[j]); d2[j] = g * (1.f - o * o); }
-        else { const float sg = ng_sigmoid(y[j]); d2[j] = g * sg * (1.f - sg); }
+        d2[j] = ng_head_delta<WHICH>(y[j], g);
     }
     ng_backprop<K>(m.W1[MM], m.W2T[MM], m.din[MM], s_h, lane, d2, dx, act_h + c * NG_HS + MM * NG_HID, delta1 + c * (4 * NG_HID) + MM * NG_HID);
-    constexpr int col0 = WHICH == 0 ? 0 : (WHICH == 1 ? 8 * K : 9 * K);          // layout [k | 7k | k | k] = opacity, cov, color, raydrop
+    constexpr int col0 = ng_col0(MM, K);
 #pragma unroll
     for (int j = 0; j < K; j++) d2row[col0 + j] = d2[j];
 }
@@ -305,7 +372,7 @@ __global__ void __launch_bounds__(NG_BLOCK) k_ng_backward(int N, int n_vis, NgMo
         ng_backprop<7 * K>(m.W1[NG_COV], m.W2T[NG_COV], m.din[NG_COV], s_h, lane, d2, dx, act_h + c * NG_HS + NG_COV * NG_HID,
                            delta1 + c * (4 * NG_HID) + NG_COV * NG_HID);
 #pragma unroll
-        for (int q = 0; q < 7 * K; q++) d2row[K + q] = d2[q];
+        for (int q = 0; q < 7 * K; q++) d2row[ng_col0(NG_COV, K) + q] = d2[q];
     }
     // --- opacity (tanh), colour and ray-drop (sigmoid) MLPs
     ng_bw_small<K, NG_OPA, 0>(m, x, dx, i, c, nv, s_h, lane, sel_flags, slot, g_opacity, g_color, g_no, act_h, delta1, d2row);
@@ -314,11 +381,7 @@ __global__ void __launch_bounds__(NG_BLOCK) k_ng_backward(int N, int n_vis, NgMo
     // --- input: feature directly; view = ob/|ob|, dist = |ob| back to the anchor position
 #pragma unroll
     for (int q = 0; q < NG_FEAT; q++) df[q] = dx[q];
-    const float dist = x[35], vx = x[32], vy = x[33], vz = x[34];
-    const float dv = dx[32] * vx + dx[33] * vy + dx[34] * vz;
-    da[0] += dx[32] / dist - vx * (dv / dist) + dx[35] * vx;
-    da[1] += dx[33] / dist - vy * (dv / dist) + dx[35] * vy;
-    da[2] += dx[34] / dist - vz * (dv / dist) + dx[35] * vz;
+    ng_view_backward(dx[32], dx[33], dx[34], dx[35], make_float4(x[32], x[33], x[34], x[35]), da);
 #pragma unroll
     for (int q = 0; q < 3; q++) d_anchor[3 * (size_t)i + q] = da[q];
 #pragma unroll
@@ -338,9 +401,6 @@ __global__ void __launch_bounds__(NG_BLOCK) k_ng_backward(int N, int n_vis, NgMo
 // the caller adds up.  Nothing per-anchor is written except the dense input gradients.
 typedef float ng_f16v __attribute__((ext_vector_type(16)));
 #define NG_LS 65                                   // LDS stride of the [unit][anchor] arrays: transposed reads hit distinct banks
-#define NG_COV_TILES(K) ((7 * (K) + 31) / 32)
-#define NG_G2_TILES(K) (3 + NG_COV_TILES(K))       // opacity, covariance (1-3), colour, ray-drop
-#define NG_PARTIAL_FLOATS(K) ((5 + NG_G2_TILES(K)) * 1024 + 128)
 
 __device__ __forceinline__ int ng_crow(int e, int lane) { return (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5); }   // row of accumulator element e
 // wave-wide sum on the VALU alone: four DPP steps leave every 16-lane row holding its total, four lane reads add the rows (the
@@ -378,9 +438,7 @@ __device__ __forceinline__ float4 ng_stage_inputs(const float* __restrict__ feat
     float4 vd = make_float4(0.f, 0.f, 0.f, 0.f);
     if (active) {
         const size_t i = (size_t)tile * NG_BLOCK + lane;
-        const float ox = anchor[3 * i] - cam.x, oy = anchor[3 * i + 1] - cam.y, oz = anchor[3 * i + 2] - cam.z;
-        const float dist = sqrtf(ox * ox + oy * oy + oz * oz);
-        vd = make_float4(ox / dist, oy / dist, oz / dist, dist);
+        vd = ng_view(make_float3(anchor[3 * i], anchor[3 * i + 1], anchor[3 * i + 2]), cam);
     }
     s_x[32 * NG_LS + lane] = vd.x; s_x[33 * NG_LS + lane] = vd.y; s_x[34 * NG_LS + lane] = vd.z; s_x[35 * NG_LS + lane] = vd.w;
     return vd;
@@ -508,11 +566,11 @@ __device__ __forceinline__ void ng_mfma_backprop(const NgModel& m, int MM, const
 
 // the per-anchor stage of one of the three k-output MLPs (lane = anchor): y -> delta2, both through s_d2.  WHICH 0 = opacity (tanh),
 // 1 = colour, 2 = ray-drop (sigmoid)
-template <int K, int WHICH>
+template <int K, int MM, int WHICH>
 __device__ __forceinline__ void ng_small_deltas(bool active, int i, size_t c, int lane, const uint32_t* __restrict__ sel_flags, const uint32_t* __restrict__ slot,
                                                 const float* __restrict__ g_opacity, const float* __restrict__ g_color, const float* __restrict__ g_no,
                                                 float* s_d2, float* s_db2) {
-    constexpr int col0 = WHICH == 0 ? 0 : (WHICH == 1 ? 8 * K : 9 * K);          // layout [k | 7k | k | k] = opacity, cov, color, raydrop
+    constexpr int col0 = ng_col0(MM, K);
 #pragma unroll
     for (int j = 0; j < K; j++) {
         float d = 0.f;
@@ -523,8 +581,7 @@ __device__ __forceinline__ void ng_small_deltas(bool active, int i, size_t c, in
             float g = 0.f;
             if (sel) g = WHICH == 0 ? g_opacity[r] : (WHICH == 1 ? g_color[2 * r] : g_color[2 * r + 1]);
             if (WHICH == 0 && g_no) g += g_no[c * K + j];
-            if (WHICH == 0) { const float o = tanhf(y); d = g * (1.f - o * o); }
-            else { const float sg = ng_sigmoid(y); d = g * sg * (1.f - sg); }
+            d = ng_head_delta<WHICH>(y, g);
         }
         s_d2[j * NG_LS + lane] = d;
         const float sum = ng_wave_sum(d);
@@ -599,8 +656,8 @@ __global__ void __launch_bounds__(NG_BLOCK) k_ng_backward_mfma(int N, NgModel m,
         // --- covariance MLP: scaling = s[3:6] * sigmoid(sr[0:3]), rot = normalize(sr[3:7]); and the direct paths of xyz / scaling
         ng_mfma_recompute<7 * K>(m, NG_COV, s_x, s_h, s_d2, lane);
         {
-            float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f, s4 = 0.f, s5 = 0.f;
-            if (active) { const float* sc = scaling + 6 * (size_t)i; s0 = sc[0]; s1 = sc[1]; s2 = sc[2]; s3 = sc[3]; s4 = sc[4]; s5 = sc[5]; }
+            float s[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            if (active) { const float* sc = scaling + 6 * (size_t)i; s[0] = sc[0]; s[1] = sc[1]; s[2] = sc[2]; s[3] = sc[3]; s[4] = sc[4]; s[5] = sc[5]; }
             float* dofs = d_offset + 3 * (size_t)(active ? i : 0) * K;
 #pragma unroll
             for (int j = 0; j < K; j++) {
@@ -611,44 +668,35 @@ __global__ void __launch_bounds__(NG_BLOCK) k_ng_backward_mfma(int N, NgModel m,
                     for (int q = 0; q < 7; q++) sr[q] = s_d2[(7 * j + q) * NG_LS + lane];
                     const bool sel = sel_flags[(size_t)i * K + j] != 0u;
                     const size_t r = sel ? slot[(size_t)i * K + j] : 0;
-                    float gx = 0.f, gy = 0.f, gz = 0.f, gs0 = 0.f, gs1 = 0.f, gs2 = 0.f, gr0 = 0.f, gr1 = 0.f, gr2 = 0.f, gr3 = 0.f;
+                    float3 gx = make_float3(0.f, 0.f, 0.f), gs = gx;
+                    float4 gr = make_float4(0.f, 0.f, 0.f, 0.f);
                     if (sel) {
-                        gx = g_xyz[3 * r]; gy = g_xyz[3 * r + 1]; gz = g_xyz[3 * r + 2];
-                        gs0 = g_scaling[3 * r]; gs1 = g_scaling[3 * r + 1]; gs2 = g_scaling[3 * r + 2];
-                        gr0 = g_rot[4 * r]; gr1 = g_rot[4 * r + 1]; gr2 = g_rot[4 * r + 2]; gr3 = g_rot[4 * r + 3];
+                        gx = make_float3(g_xyz[3 * r], g_xyz[3 * r + 1], g_xyz[3 * r + 2]);
+                        gs = make_float3(g_scaling[3 * r], g_scaling[3 * r + 1], g_scaling[3 * r + 2]);
+                        gr = make_float4(g_rot[4 * r], g_rot[4 * r + 1], g_rot[4 * r + 2], g_rot[4 * r + 3]);
                     }
                     const float* of = offset + 3 * ((size_t)i * K + j);
-                    const float o0 = of[0], o1 = of[1], o2 = of[2];
-                    dofs[3 * j] = gx * s0; dofs[3 * j + 1] = gy * s1; dofs[3 * j + 2] = gz * s2;
-                    ds[0] += gx * o0; ds[1] += gy * o1; ds[2] += gz * o2;
-                    da[0] += gx; da[1] += gy; da[2] += gz;
-                    const float g0 = ng_sigmoid(sr[0]), g1s = ng_sigmoid(sr[1]), g2s = ng_sigmoid(sr[2]);
-                    ds[3] += gs0 * g0; ds[4] += gs1 * g1s; ds[5] += gs2 * g2s;
-                    d[0] = gs0 * s3 * g0 * (1.f - g0); d[1] = gs1 * s4 * g1s * (1.f - g1s); d[2] = gs2 * s5 * g2s * (1.f - g2s);
-                    const float q0 = sr[3], q1 = sr[4], q2 = sr[5], q3 = sr[6];
-                    const float qn = fmaxf(sqrtf(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3), 1e-12f);
-                    const float r0 = q0 / qn, r1 = q1 / qn, r2 = q2 / qn, r3 = q3 / qn;
-                    const float dotp = gr0 * r0 + gr1 * r1 + gr2 * r2 + gr3 * r3;
-                    d[3] = (gr0 - r0 * dotp) / qn; d[4] = (gr1 - r1 * dotp) / qn; d[5] = (gr2 - r2 * dotp) / qn; d[6] = (gr3 - r3 * dotp) / qn;
+                    const float3 dof = ng_cov_delta(sr, s, make_float3(of[0], of[1], of[2]), gx, gs, gr, d, ds, da);
+                    dofs[3 * j] = dof.x; dofs[3 * j + 1] = dof.y; dofs[3 * j + 2] = dof.z;
                 }
 #pragma unroll
                 for (int q = 0; q < 7; q++) {
                     s_d2[(7 * j + q) * NG_LS + lane] = d[q];
                     const float sum = ng_wave_sum(d[q]);
-                    if (lane == 0) s_db2[K + 7 * j + q] += sum;
+                    if (lane == 0) s_db2[ng_col0(NG_COV, K) + 7 * j + q] += sum;
                 }
             }
         }
         ng_mfma_backprop<7 * K>(m, NG_COV, s_x, s_h, s_d1, s_d2, lane, dxa, g1[NG_COV], g1[4], &g2[1]);
         // --- opacity (tanh), colour and ray-drop (sigmoid) MLPs
         ng_mfma_recompute<K>(m, NG_OPA, s_x, s_h, s_d2, lane);
-        ng_small_deltas<K, 0>(active, i, c, lane, sel_flags, slot, g_opacity, g_color, g_no, s_d2, s_db2);
+        ng_small_deltas<K, NG_OPA, 0>(active, i, c, lane, sel_flags, slot, g_opacity, g_color, g_no, s_d2, s_db2);
         ng_mfma_backprop<K>(m, NG_OPA, s_x, s_h, s_d1, s_d2, lane, dxa, g1[NG_OPA], g1[4], &g2[0]);
         ng_mfma_recompute<K>(m, NG_COL, s_x, s_h, s_d2, lane);
-        ng_small_deltas<K, 1>(active, i, c, lane, sel_flags, slot, g_opacity, g_color, g_no, s_d2, s_db2);
+        ng_small_deltas<K, NG_COL, 1>(active, i, c, lane, sel_flags, slot, g_opacity, g_color, g_no, s_d2, s_db2);
         ng_mfma_backprop<K>(m, NG_COL, s_x, s_h, s_d1, s_d2, lane, dxa, g1[NG_COL], g1[4], &g2[1 + NC]);
         ng_mfma_recompute<K>(m, NG_RD, s_x, s_h, s_d2, lane);
-        ng_small_deltas<K, 2>(active, i, c, lane, sel_flags, slot, g_opacity, g_color, g_no, s_d2, s_db2);
+        ng_small_deltas<K, NG_RD, 2>(active, i, c, lane, sel_flags, slot, g_opacity, g_color, g_no, s_d2, s_db2);
         ng_mfma_backprop<K>(m, NG_RD, s_x, s_h, s_d1, s_d2, lane, dxa, g1[NG_RD], g1[4], &g2[2 + NC]);
 
         // --- input gradients: the feature part leaves in accumulator layout (a lane holds one column of 16 anchors: 128-byte
@@ -664,10 +712,7 @@ __global__ void __launch_bounds__(NG_BLOCK) k_ng_backward_mfma(int N, NgModel m,
         __builtin_amdgcn_wave_barrier();
         if (active) {
             const float dx32 = s_d1[0 * NG_LS + lane], dx33 = s_d1[1 * NG_LS + lane], dx34 = s_d1[2 * NG_LS + lane], dx35 = s_d1[3 * NG_LS + lane];
-            const float dv = dx32 * vx + dx33 * vy + dx34 * vz;
-            da[0] += dx32 / dist - vx * (dv / dist) + dx35 * vx;
-            da[1] += dx33 / dist - vy * (dv / dist) + dx35 * vy;
-            da[2] += dx34 / dist - vz * (dv / dist) + dx35 * vz;
+            ng_view_backward(dx32, dx33, dx34, dx35, make_float4(vx, vy, vz, dist), da);
 #pragma unroll
             for (int q = 0; q < 3; q++) d_anchor[3 * (size_t)i + q] = da[q];
 #pragma unroll
@@ -676,7 +721,7 @@ __global__ void __launch_bounds__(NG_BLOCK) k_ng_backward_mfma(int N, NgModel m,
         __builtin_amdgcn_wave_barrier();
     }
     // --- this wave's partial sums: tiles [t or o][q or t] as 32 x 32 blocks, then the output-layer bias sums
-    float* out = partial + (size_t)blockIdx.x * NG_PARTIAL_FLOATS(K);
+    float* out = partial + (size_t)blockIdx.x * ng_partial_floats(K);
 #pragma unroll
     for (int t = 0; t < 5; t++)
 #pragma unroll
@@ -741,25 +786,24 @@ __global__ void __launch_bounds__(NG_BLOCK) k_ng_decode_mfma(int N, NgModel m, f
     ng_mfma_recompute<7 * K>(m, NG_COV, s_x, s_h, s_y, lane);          // its outputs land on x (dead behind the hidden layer)
     if (!active) return;
     const float* sc = scaling + 6 * (size_t)i;
-    const float s0 = sc[0], s1 = sc[1], s2 = sc[2], s3 = sc[3], s4 = sc[4], s5 = sc[5];
-    const float ax = anchor[3 * (size_t)i], ay = anchor[3 * (size_t)i + 1], az = anchor[3 * (size_t)i + 2];
+    const float s[6] = {sc[0], sc[1], sc[2], sc[3], sc[4], sc[5]};
+    const float3 a = make_float3(anchor[3 * (size_t)i], anchor[3 * (size_t)i + 1], anchor[3 * (size_t)i + 2]);
     const size_t c = vis_idx[i];
 #pragma unroll
     for (int j = 0; j < K; j++) {
         if (!sel_flags[(size_t)i * K + j]) continue;
-        const size_t r = slot[(size_t)i * K + j];
         const float* of = offset + 3 * ((size_t)i * K + j);
-        o_xyz[3 * r] = ax + of[0] * s0; o_xyz[3 * r + 1] = ay + of[1] * s1; o_xyz[3 * r + 2] = az + of[2] * s2;      // :111-112
-        o_color[2 * r] = ng_sigmoid(col[j]); o_color[2 * r + 1] = ng_sigmoid(rd[j]);                                // :85-87
-        o_opacity[r] = neural_opacity[c * K + j];                                                                    // :71
         float sr[7];
 #pragma unroll
         for (int q = 0; q < 7; q++) sr[q] = s_y[(7 * j + q) * NG_LS + lane];
-        o_scaling[3 * r] = s3 * ng_sigmoid(sr[0]); o_scaling[3 * r + 1] = s4 * ng_sigmoid(sr[1]);                    // :107
-        o_scaling[3 * r + 2] = s5 * ng_sigmoid(sr[2]);
-        const float q0 = sr[3], q1 = sr[4], q2 = sr[5], q3 = sr[6];
-        const float qn = fmaxf(sqrtf(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3), 1e-12f);                               // F.normalize, :108
-        o_rot[4 * r] = q0 / qn; o_rot[4 * r + 1] = q1 / qn; o_rot[4 * r + 2] = q2 / qn; o_rot[4 * r + 3] = q3 / qn;
+        const NgRow v = ng_decode_row(a, make_float3(of[0], of[1], of[2]), s, col[j], rd[j], sr);
+        const float op = neural_opacity[c * K + j];                                                                  // :71
+        const size_t r = slot[(size_t)i * K + j];
+        o_xyz[3 * r] = v.xyz.x; o_xyz[3 * r + 1] = v.xyz.y; o_xyz[3 * r + 2] = v.xyz.z;
+        o_color[2 * r] = v.color.x; o_color[2 * r + 1] = v.color.y;
+        o_opacity[r] = op;
+        o_scaling[3 * r] = v.scaling.x; o_scaling[3 * r + 1] = v.scaling.y; o_scaling[3 * r + 2] = v.scaling.z;
+        o_rot[4 * r] = v.rot.x; o_rot[4 * r + 1] = v.rot.y; o_rot[4 * r + 2] = v.rot.z; o_rot[4 * r + 3] = v.rot.w;
     }
 }
 
@@ -798,11 +842,10 @@ __global__ void __launch_bounds__(NG_BLOCK) k_ng_opacity_mfma(int N, NgModel m, 
     const size_t c = vis_idx[i];
 #pragma unroll
     for (int j = 0; j < K; j++) {
-        const float o = tanhf(s_y[j * NG_LS + lane]);                 // nn.Tanh closes the opacity MLP (gaussian_model.py:118)
-        neural_opacity[c * K + j] = o;
-        const bool keep = o > 0.0f;                                    // :67
-        mask[c * K + j] = keep ? 1 : 0;
-        sel_flags[(size_t)i * K + j] = keep ? 1u : 0u;
+        const NgOpacity r = ng_opacity_out(s_y[j * NG_LS + lane]);
+        neural_opacity[c * K + j] = r.o;
+        mask[c * K + j] = r.keep ? 1 : 0;
+        sel_flags[(size_t)i * K + j] = r.keep ? 1u : 0u;
     }
 }
 
@@ -923,7 +966,7 @@ namespace {
 int ng_model(const lidargs_ng_model* in, lg::NgModel* out) {
     if (!in) return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "neural_gaussians: NULL model");
     const int k = in->n_offsets;
-    if (!(k == 4 || k == 5 || k == 6 || k == 8 || k == 10)) return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "neural_gaussians: n_offsets must be 4, 5, 6, 8 or 10");
+    if (!lg::ng_valid_k(k)) return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "neural_gaussians: n_offsets must be 4, 5, 6, 8 or 10");
     out->k = k;
     out->din[lg::NG_OPA] = 35 + (in->add_opacity_dist ? 1 : 0);
     out->din[lg::NG_COV] = 35 + (in->add_cov_dist ? 1 : 0);
@@ -934,21 +977,53 @@ int ng_model(const lidargs_ng_model* in, lg::NgModel* out) {
     }
     return 0;
 }
+int ng_fail(const char* name, const char* what) {
+    char msg[192];
+    snprintf(msg, sizeof msg, "%s: %s", name, what);
+    return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, msg);
+}
+// What an entry point that launches the decode's kernels does first: the model, the pointers it cannot do without (`need`, the camera
+// centre and the scratch block), the scratch size, its carve, the camera.  Returns an error code (< 0; `name` opens its text), 1 where
+// N <= 0 leaves nothing to do, 0 to go on.
+struct NgCall { lg::NgModel m; lg::NgScratch s; float3 cam; };
+int ng_begin(const char* name, int N, const lidargs_ng_model* model, std::initializer_list<const void*> need, const float* cam_center,
+             char* scratch, size_t scratch_bytes, bool w2t, NgCall* c) {
+    if (int rc = ng_model(model, &c->m)) return rc;
+    if (N <= 0) return 1;
+    bool all = cam_center && scratch;
+    for (const void* p : need) all = all && p;
+    if (!all) return ng_fail(name, "NULL pointer");
+    for (int q = 0; w2t && q < 4; q++) if (!c->m.W2T[q]) return ng_fail(name, "model.W2T (transposed second-layer weights) is required");
+    if (scratch_bytes < lidargs_ng_scratch_bytes(N, c->m.k)) return ng_fail(name, "scratch too small");
+    lg::ng_carve(scratch, (size_t)N, (size_t)c->m.k, &c->s);
+    c->cam = make_float3(cam_center[0], cam_center[1], cam_center[2]);
+    return 0;
+}
+int ng_cus() {
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+    return cus;
+}
+// LIDARGS_NG_PER_LANE_DECODE=1 (read once per process): the one-anchor-per-lane forward, which a model without W2T gets in any case
+bool ng_per_lane() {
+    static const bool on = [] { const char* e = getenv("LIDARGS_NG_PER_LANE_DECODE"); return e && atoi(e) != 0; }();
+    return on;
+}
 // k <= 6: the forward's two MLP launches on 16x16x4 tiles (k_ng_opacity_t16 / k_ng_decode_t16: persistent workgroups of twelve waves, weights in
 // LDS); k = 8, 10 and LIDARGS_NG_FORWARD_T16=0 (A/B, test variant): the 32x32x2 kernels, one wave per workgroup
-static bool ng_forward_t16(int k) {
+bool ng_forward_t16(int k) {
     if (k > 6) return false;
     const char* e = getenv("LIDARGS_NG_FORWARD_T16");
     return !(e && e[0] == '0');
 }
-static int ng_forward_grid(int N) {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    const int need = ((N + 31) / 32 + NGF_WAVES - 1) / NGF_WAVES;
+int ng_forward_grid(int N) {
+    const int cus = ng_cus(), need = ((N + 31) / 32 + NGF_WAVES - 1) / NGF_WAVES;
     return need < cus ? (need > 0 ? need : 1) : cus;
 }
-#define NG_DISPATCH(K_, CALL) switch (K_) { case 4: { constexpr int K = 4; CALL; } break; case 5: { constexpr int K = 5; CALL; } break; \
-    case 6: { constexpr int K = 6; CALL; } break; case 8: { constexpr int K = 8; CALL; } break; default: { constexpr int K = 10; CALL; } break; }
+#define NG_CASE(V, ...) { constexpr int K = V; __VA_ARGS__; } break
+#define NG_DISPATCH(K_, ...) switch (K_) { case 4: NG_CASE(4, __VA_ARGS__); case 5: NG_CASE(5, __VA_ARGS__); case 6: NG_CASE(6, __VA_ARGS__); \
+    case 8: NG_CASE(8, __VA_ARGS__); default: NG_CASE(10, __VA_ARGS__); }
+#define NG_DISPATCH_T16(K_, ...) switch (K_) { case 4: NG_CASE(4, __VA_ARGS__); case 5: NG_CASE(5, __VA_ARGS__); default: NG_CASE(6, __VA_ARGS__); }   // the 16x16x4 kernels: k <= 6
 #define NG_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return lg::api_fail(LIDARGS_ERR_HIP, hipGetErrorString(e_)); } while (0)
 }  // namespace
 
@@ -962,31 +1037,21 @@ static int ng_forward_select(int N, const lidargs_ng_model* model, const uint8_t
                              const float* anchor, const float* cam_center, float* neural_opacity, uint8_t* mask,
                              int* counts_host, char* scratch, size_t scratch_bytes, void* stream_, bool wait) {
     hipStream_t stream = (hipStream_t)stream_;
-    lg::NgModel m;
-    if (int rc = ng_model(model, &m)) return rc;
-    if (N < 0 || !counts_host || !cam_center) return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "ng_forward_select: bad argument");
+    NgCall c;
+    if (int rc = ng_model(model, &c.m)) return rc;                     // (in front of this entry point's own checks; ng_begin repeats it)
+    if (N < 0 || !counts_host || !cam_center) return ng_fail("ng_forward_select", "bad argument");
     counts_host[0] = counts_host[1] = 0;
-    if (N == 0) return 0;
-    if (!anchor_feat || !anchor || !neural_opacity || !mask || !scratch) return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "ng_forward_select: NULL pointer");
-    if (scratch_bytes < lidargs_ng_scratch_bytes(N, m.k)) return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "ng_forward_select: scratch too small");
-    lg::NgScratch s; lg::ng_carve(scratch, (size_t)N, (size_t)m.k, &s);
-    const float3 cam = make_float3(cam_center[0], cam_center[1], cam_center[2]);
+    if (int rc = ng_begin("ng_forward_select", N, model, {anchor_feat, anchor, neural_opacity, mask}, cam_center, scratch, scratch_bytes, false, &c)) return rc < 0 ? rc : 0;
+    const lg::NgModel& m = c.m;
+    const lg::NgScratch& s = c.s;
     hipLaunchKernelGGL(lg::k_ng_visflags, dim3((N + 255) / 256), dim3(256), 0, stream, N, visible_mask, s.vis_flags);
     lg::launch_exclusive_scan(s.vis_flags, s.vis_idx, (size_t)N, s.totals, s.scan, stream);
-    static const bool per_lane = [] { const char* e = getenv("LIDARGS_NG_PER_LANE_DECODE"); return e && atoi(e) != 0; }();
-    if (per_lane || !m.W2T[0]) {
-        NG_DISPATCH(m.k, hipLaunchKernelGGL(lg::k_ng_opacity<K>, dim3((N + 63) / 64), dim3(64), 0, stream, N, m, cam, anchor_feat, anchor, s.vis_flags,
-                                            s.vis_idx, neural_opacity, mask, s.sel_flags));
-    } else if (ng_forward_t16(m.k)) {
-        const int grid = ng_forward_grid(N);
-#define NG_OPA_T16(K_) hipLaunchKernelGGL(lg::k_ng_opacity_t16<K_>, dim3(grid), dim3(64 * NGF_WAVES), 0, stream, N, m, cam, anchor_feat, anchor, s.vis_flags, \
-                                            s.vis_idx, neural_opacity, mask, s.sel_flags)
-        if (m.k == 4) NG_OPA_T16(4); else if (m.k == 5) NG_OPA_T16(5); else NG_OPA_T16(6);
-#undef NG_OPA_T16
-    } else {
-        NG_DISPATCH(m.k, hipLaunchKernelGGL(lg::k_ng_opacity_mfma<K>, dim3((N + 63) / 64), dim3(64), 0, stream, N, m, cam, anchor_feat, anchor, s.vis_flags,
-                                            s.vis_idx, neural_opacity, mask, s.sel_flags));
-    }
+    auto launch = [&](auto kernel, int grid, int block) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, stream, N, m, c.cam, anchor_feat, anchor, s.vis_flags, s.vis_idx, neural_opacity, mask, s.sel_flags);
+    };
+    if (ng_per_lane() || !m.W2T[0]) { NG_DISPATCH(m.k, launch(lg::k_ng_opacity<K>, (N + 63) / 64, 64)); }
+    else if (ng_forward_t16(m.k)) { NG_DISPATCH_T16(m.k, launch(lg::k_ng_opacity_t16<K>, ng_forward_grid(N), 64 * NGF_WAVES)); }
+    else { NG_DISPATCH(m.k, launch(lg::k_ng_opacity_mfma<K>, (N + 63) / 64, 64)); }
     lg::launch_exclusive_scan(s.sel_flags, s.slot, (size_t)N * m.k, s.totals + 1, s.scan, stream);
     if (!wait) {                                                       // counts_host is pinned memory of the caller's, who waits (an event behind this call)
         NG_HIP(hipMemcpyAsync(counts_host, s.totals, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
@@ -1014,29 +1079,18 @@ int lidargs_ng_forward_decode(int N, const lidargs_ng_model* model, const float*
                               float* out_xyz, float* out_color, float* out_opacity, float* out_scaling, float* out_rot,
                               char* scratch, size_t scratch_bytes, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    lg::NgModel m;
-    if (int rc = ng_model(model, &m)) return rc;
-    if (N <= 0) return 0;
-    if (!anchor_feat || !anchor || !offset || !scaling || !cam_center || !neural_opacity || !scratch)
-        return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "ng_forward_decode: NULL pointer");
-    if (scratch_bytes < lidargs_ng_scratch_bytes(N, m.k)) return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "ng_forward_decode: scratch too small");
-    lg::NgScratch s; lg::ng_carve(scratch, (size_t)N, (size_t)m.k, &s);
-    const float3 cam = make_float3(cam_center[0], cam_center[1], cam_center[2]);
-    static const bool per_lane = [] { const char* e = getenv("LIDARGS_NG_PER_LANE_DECODE"); return e && atoi(e) != 0; }();
-    if (per_lane || !m.W2T[0] || !m.W2T[1] || !m.W2T[2] || !m.W2T[3]) {     // the matrix-pipe decode reads the transposed second-layer weights
-    NG_DISPATCH(m.k, hipLaunchKernelGGL(lg::k_ng_decode<K>, dim3((N + 63) / 64), dim3(64), 0, stream, N, m, cam, anchor_feat, anchor, offset, scaling,
-                                        s.vis_flags, s.vis_idx, s.sel_flags, s.slot, neural_opacity, out_xyz, out_color, out_opacity, out_scaling, out_rot));
-    } else if (ng_forward_t16(m.k)) {
-        const int grid = ng_forward_grid(N);
-#define NG_DEC_T16(K_) hipLaunchKernelGGL(lg::k_ng_decode_t16<K_>, dim3(grid), dim3(64 * NGF_WAVES), 0, stream, N, m, cam, anchor_feat, anchor, offset, scaling, \
-                                        s.vis_flags, s.vis_idx, s.sel_flags, s.slot, neural_opacity, out_xyz, out_color, out_opacity, out_scaling, out_rot)
-        if (m.k == 4) NG_DEC_T16(4); else if (m.k == 5) NG_DEC_T16(5); else NG_DEC_T16(6);
-#undef NG_DEC_T16
-    } else {
-    NG_DISPATCH(m.k, hipLaunchKernelGGL(lg::k_ng_decode_mfma<K>, dim3((N + 63) / 64), dim3(64), 0, stream, N, m, cam, anchor_feat, anchor, offset, scaling,
-                                        s.vis_flags, s.vis_idx, s.sel_flags, s.slot, neural_opacity, out_xyz, out_color, out_opacity, out_scaling, out_rot));
-    }
-
+    NgCall c;
+    if (int rc = ng_begin("ng_forward_decode", N, model, {anchor_feat, anchor, offset, scaling, neural_opacity}, cam_center, scratch, scratch_bytes, false, &c)) return rc < 0 ? rc : 0;
+    const lg::NgModel& m = c.m;
+    const lg::NgScratch& s = c.s;
+    auto launch = [&](auto kernel, int grid, int block) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, stream, N, m, c.cam, anchor_feat, anchor, offset, scaling, s.vis_flags, s.vis_idx, s.sel_flags, s.slot,
+                           neural_opacity, out_xyz, out_color, out_opacity, out_scaling, out_rot);
+    };
+    if (ng_per_lane() || !m.W2T[0] || !m.W2T[1] || !m.W2T[2] || !m.W2T[3]) {     // the matrix-pipe decode reads the transposed second-layer weights
+        NG_DISPATCH(m.k, launch(lg::k_ng_decode<K>, (N + 63) / 64, 64));
+    } else if (ng_forward_t16(m.k)) { NG_DISPATCH_T16(m.k, launch(lg::k_ng_decode_t16<K>, ng_forward_grid(N), 64 * NGF_WAVES)); }
+    else { NG_DISPATCH(m.k, launch(lg::k_ng_decode_mfma<K>, (N + 63) / 64, 64)); }
     NG_HIP(hipGetLastError());
     return 0;
 }
@@ -1048,28 +1102,17 @@ int lidargs_ng_backward(int N, int n_visible, const lidargs_ng_model* model, con
                         float* dL_dscaling_in, float* act_x, float* act_h, float* delta1, float* delta2,
                         char* scratch, size_t scratch_bytes, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    lg::NgModel m;
-    if (int rc = ng_model(model, &m)) return rc;
-    if (N <= 0) return 0;
-    if (!anchor_feat || !anchor || !offset || !scaling || !cam_center || !dL_danchor_feat || !dL_danchor || !dL_doffset || !dL_dscaling_in || !scratch)
-        return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "ng_backward: NULL pointer");
-    for (int q = 0; q < 4; q++) if (!m.W2T[q]) return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "ng_backward: model.W2T (transposed second-layer weights) is required");
-    if (n_visible > 0 && (!act_x || !act_h || !delta1 || !delta2)) return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "ng_backward: NULL activation buffer");
-    if (scratch_bytes < lidargs_ng_scratch_bytes(N, m.k)) return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "ng_backward: scratch too small");
-    lg::NgScratch s; lg::ng_carve(scratch, (size_t)N, (size_t)m.k, &s);
-    const float3 cam = make_float3(cam_center[0], cam_center[1], cam_center[2]);
-    NG_DISPATCH(m.k, hipLaunchKernelGGL(lg::k_ng_backward<K>, dim3((N + 63) / 64), dim3(64), 0, stream, N, n_visible, m, cam, anchor_feat, anchor, offset,
-                                        scaling, s.vis_flags, s.vis_idx, s.sel_flags, s.slot, dL_dxyz, dL_dcolor, dL_dopacity, dL_dscaling, dL_drot, dL_dneural_opacity,
-                                        dL_danchor_feat, dL_danchor, dL_doffset, dL_dscaling_in, act_x, act_h, delta1, delta2));
+    NgCall c;
+    if (int rc = ng_begin("ng_backward", N, model, {anchor_feat, anchor, offset, scaling, dL_danchor_feat, dL_danchor, dL_doffset, dL_dscaling_in}, cam_center,
+                          scratch, scratch_bytes, true, &c)) return rc < 0 ? rc : 0;
+    if (n_visible > 0 && (!act_x || !act_h || !delta1 || !delta2)) return ng_fail("ng_backward", "NULL activation buffer");
+    NG_DISPATCH(c.m.k, hipLaunchKernelGGL(lg::k_ng_backward<K>, dim3((N + 63) / 64), dim3(64), 0, stream, N, n_visible, c.m, c.cam, anchor_feat, anchor, offset,
+                                          scaling, c.s.vis_flags, c.s.vis_idx, c.s.sel_flags, c.s.slot, dL_dxyz, dL_dcolor, dL_dopacity, dL_dscaling, dL_drot, dL_dneural_opacity,
+                                          dL_danchor_feat, dL_danchor, dL_doffset, dL_dscaling_in, act_x, act_h, delta1, delta2));
     NG_HIP(hipGetLastError());
     return 0;
 }
 
-static int ng_cus() {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    return cus;
-}
 // k <= 6: k_ng_backward_t16 (16x16x4 tiles, one workgroup of eight waves per CU, one partial row per workgroup); k = 8, 10 (its LDS does
 // not hold their delta2 rows for eight waves) and LIDARGS_NG_BACKWARD_T16=0 (A/B, test variant): k_ng_backward_mfma, one wave per SIMD
 static bool ng_use_t16(int k) {
@@ -1086,10 +1129,10 @@ static thread_local int t_ng_rows_reported[16] = {0};
 static int ng_partial_rows(int k) { return ng_use_t16(k) ? (ng_t16_two_pass() ? 2 : 1) * ng_cus() : 4 * ng_cus(); }
 int lidargs_ng_backward_partials(int n_offsets, int* waves, int* floats_per_wave) {
     const int k = n_offsets;
-    if (!(k == 4 || k == 5 || k == 6 || k == 8 || k == 10) || !waves || !floats_per_wave) return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "ng_backward_partials: bad argument");
+    if (!lg::ng_valid_k(k) || !waves || !floats_per_wave) return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "ng_backward_partials: bad argument");
     *waves = ng_partial_rows(k);
     t_ng_rows_reported[k] = *waves;
-    *floats_per_wave = (5 + 3 + (7 * k + 31) / 32) * 1024 + 128;
+    *floats_per_wave = lg::ng_partial_floats(k);
     return 0;
 }
 int lidargs_ng_backward_mfma(int N, const lidargs_ng_model* model, const float* anchor_feat, const float* anchor,
@@ -1098,42 +1141,31 @@ int lidargs_ng_backward_mfma(int N, const lidargs_ng_model* model, const float* 
                              const float* dL_drot, const float* dL_dneural_opacity, float* dL_danchor_feat, float* dL_danchor, float* dL_doffset,
                              float* dL_dscaling_in, float* partials, char* scratch, size_t scratch_bytes, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    lg::NgModel m;
-    if (int rc = ng_model(model, &m)) return rc;
-    if (N <= 0) return 0;
-    if (!anchor_feat || !anchor || !offset || !scaling || !cam_center || !dL_danchor_feat || !dL_danchor || !dL_doffset || !dL_dscaling_in || !partials || !scratch)
-        return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "ng_backward_mfma: NULL pointer");
-    for (int q = 0; q < 4; q++) if (!m.W2T[q]) return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "ng_backward_mfma: model.W2T (transposed second-layer weights) is required");
-    if (scratch_bytes < lidargs_ng_scratch_bytes(N, m.k)) return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "ng_backward_mfma: scratch too small");
-    lg::NgScratch s; lg::ng_carve(scratch, (size_t)N, (size_t)m.k, &s);
-    const float3 cam = make_float3(cam_center[0], cam_center[1], cam_center[2]);
+    NgCall c;
+    if (int rc = ng_begin("ng_backward_mfma", N, model, {anchor_feat, anchor, offset, scaling, dL_danchor_feat, dL_danchor, dL_doffset, dL_dscaling_in, partials},
+                          cam_center, scratch, scratch_bytes, true, &c)) return rc < 0 ? rc : 0;
+    const lg::NgModel& m = c.m;
+    const lg::NgScratch& s = c.s;
     const int waves = ng_partial_rows(m.k);
     if (t_ng_rows_reported[m.k] && t_ng_rows_reported[m.k] != waves)
         return lg::api_fail(LIDARGS_ERR_STATE, "ng_backward_mfma: the backward variant (LIDARGS_NG_BACKWARD_T16 / LIDARGS_NG_T16_PASSES) changed since lidargs_ng_backward_partials sized the partial rows; call it again");
-#define NG_T16_LAUNCH(K_, P_) hipLaunchKernelGGL((lg::k_ng_backward_t16<K_, P_>), dim3(ng_cus()), dim3(64 * NGT_WAVES), 0, stream, N, m, cam, anchor_feat, anchor, offset, \
-                                        scaling, s.vis_flags, s.vis_idx, s.sel_flags, s.slot, dL_dxyz, dL_dcolor, dL_dopacity, dL_dscaling, dL_drot, dL_dneural_opacity, \
-                                        dL_danchor_feat, dL_danchor, dL_doffset, dL_dscaling_in, partials, stagger)
+    auto launch = [&](auto kernel, int grid, int block, auto... tail) {       // tail: what a kernel takes behind the partial rows
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, stream, N, m, c.cam, anchor_feat, anchor, offset, scaling, s.vis_flags, s.vis_idx, s.sel_flags, s.slot,
+                           dL_dxyz, dL_dcolor, dL_dopacity, dL_dscaling, dL_drot, dL_dneural_opacity, dL_danchor_feat, dL_danchor, dL_doffset, dL_dscaling_in, partials, tail...);
+    };
     if (ng_use_t16(m.k)) {
         const char* sg = getenv("LIDARGS_NG_T16_STAGGER");
-        const int stagger = sg ? atoi(sg) : 0;
-        if (ng_t16_two_pass()) {
-            if (m.k == 4) { NG_T16_LAUNCH(4, 2); NG_T16_LAUNCH(4, 1); } else if (m.k == 5) { NG_T16_LAUNCH(5, 2); NG_T16_LAUNCH(5, 1); } else { NG_T16_LAUNCH(6, 2); NG_T16_LAUNCH(6, 1); }
-        } else {
-            if (m.k == 4) NG_T16_LAUNCH(4, 0); else if (m.k == 5) NG_T16_LAUNCH(5, 0); else NG_T16_LAUNCH(6, 0);
-        }
-    } else {
-        NG_DISPATCH(m.k, hipLaunchKernelGGL(lg::k_ng_backward_mfma<K>, dim3(waves), dim3(64), 0, stream, N, m, cam, anchor_feat, anchor, offset,
-                                            scaling, s.vis_flags, s.vis_idx, s.sel_flags, s.slot, dL_dxyz, dL_dcolor, dL_dopacity, dL_dscaling, dL_drot, dL_dneural_opacity,
-                                            dL_danchor_feat, dL_danchor, dL_doffset, dL_dscaling_in, partials));
-    }
-#undef NG_T16_LAUNCH
+        const int stagger = sg ? atoi(sg) : 0, grid = ng_cus(), block = 64 * NGT_WAVES;
+        if (ng_t16_two_pass()) { NG_DISPATCH_T16(m.k, launch(lg::k_ng_backward_t16<K, 2>, grid, block, stagger); launch(lg::k_ng_backward_t16<K, 1>, grid, block, stagger)); }
+        else { NG_DISPATCH_T16(m.k, launch(lg::k_ng_backward_t16<K, 0>, grid, block, stagger)); }
+    } else { NG_DISPATCH(m.k, launch(lg::k_ng_backward_mfma<K>, waves, 64)); }
     NG_HIP(hipGetLastError());
     return 0;
 }
 
 int lidargs_ng_transpose_w2(int n_offsets, const float* const* W2, float* out, void* stream_) {
     const int k = n_offsets;
-    if (!(k == 4 || k == 5 || k == 6 || k == 8 || k == 10) || !W2 || !out || !W2[0] || !W2[1] || !W2[2] || !W2[3])
+    if (!lg::ng_valid_k(k) || !W2 || !out || !W2[0] || !W2[1] || !W2[2] || !W2[3])
         return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "ng_transpose_w2: bad argument");
     lg::NgW2 a; a.k = k;
     for (int m = 0; m < 4; m++) a.w[m] = W2[m];
@@ -1142,12 +1174,12 @@ int lidargs_ng_transpose_w2(int n_offsets, const float* const* W2, float* out, v
     return 0;
 }
 static int ng_grad_map(int k, const int* din, lg::NgGradMap* g) {
-    if (!(k == 4 || k == 5 || k == 6 || k == 8 || k == 10) || !din) return 1;
-    g->k = k; g->nc = (7 * k + 31) / 32; g->per_wave = (5 + 3 + g->nc) * 1024 + 128;
+    if (!lg::ng_valid_k(k) || !din) return 1;
+    g->k = k; g->nc = NG_COV_TILES(k); g->per_wave = lg::ng_partial_floats(k);
     int off = 0;
     for (int m = 0; m < 4; m++) {
         if (din[m] < 32 || din[m] > 36) return 1;
-        const int dout = m == 1 ? 7 * k : k;
+        const int dout = lg::ng_dout(m, k);
         g->din[m] = din[m]; g->base[m] = off;
         off += 32 * din[m] + 32 + dout * 32 + dout;
     }

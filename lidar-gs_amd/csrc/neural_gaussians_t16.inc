@@ -263,11 +263,7 @@ __device__ __forceinline__ void ngt_small_deltas(bool active, int a, int hh, con
         const int j = hh * JH + jj;
         if (j < K) {
             float d = 0.f;
-            if (active) {
-                const float y = s_d2[j * NGT_LS + a];
-                if (WHICH == 0) { const float o = tanhf(y); d = gg[jj] * (1.f - o * o); }
-                else { const float sg = ng_sigmoid(y); d = gg[jj] * sg * (1.f - sg); }
-            }
+            if (active) d = ng_head_delta<WHICH>(s_d2[j * NGT_LS + a], gg[jj]);
             s_d2[j * NGT_LS + a] = d;
         }
     }
@@ -289,7 +285,7 @@ __device__ __forceinline__ void ngt_stage_weights(const NgModel& m, float* __res
 #pragma unroll
     for (int mm = 0; mm < 4; mm++) {
         const bool on = ((MLPS >> mm) & 1) != 0;
-        const int dout = mm == 1 ? 7 * K : K;
+        const int dout = ng_dout(mm, K);
         const int din = on ? m.din[mm] : 36;
         const float* __restrict__ W1 = m.W1[mm];
         const float* __restrict__ W2 = m.W2[mm];
@@ -321,7 +317,7 @@ __device__ __forceinline__ void ngt_stage_weights(const NgModel& m, float* __res
     }
 #pragma unroll
     for (int mm = 0; mm < 4; mm++) {                                   // (zeros where nothing is staged: a product's padding steps may run into a
-        const int dout = mm == 1 ? 7 * K : K, obase = mm == 0 ? 0 : (mm == 1 ? K : (mm == 2 ? 8 * K : 9 * K));   //  neighbour's rows -- times zero: they must be finite)
+        const int dout = ng_dout(mm, K), obase = ng_col0(mm, K);   //  neighbour's rows -- times zero: they must be finite)
 #pragma unroll
         for (int it = 0; it < C1; it++) { const int q = tid + it * NT; if (q < 32 * NGT_WS) sW1[mm * 32 * NGT_WS + q] = v1[mm][it]; }
 #pragma unroll
@@ -346,8 +342,9 @@ __global__ void __launch_bounds__(64 * NGT_WAVES) k_ng_backward_t16(int N, NgMod
                                                                     float* __restrict__ d_feat, float* __restrict__ d_anchor, float* __restrict__ d_offset,
                                                                     float* __restrict__ d_scaling, float* __restrict__ partial, int stagger) {
     static_assert(10 * K <= 64, "one lane per output column");
-    constexpr int NC = NG_COV_TILES(K), D2R = NGT_D2R(K), PER = NG_PARTIAL_FLOATS(K);
+    constexpr int NC = NG_COV_TILES(K), D2R = NGT_D2R(K), PER = ng_partial_floats(K);
     constexpr int ORC = (7 * K + 15) / 16;
+    constexpr int C_OPA = ng_col0(NG_OPA, K), C_COV = ng_col0(NG_COV, K), C_COL = ng_col0(NG_COL, K), C_RD = ng_col0(NG_RD, K);
     static_assert(16 * ORC <= 32 * NC, "the covariance head's G2 tiles fit its blocks of the partial row");
     static_assert(NGT_WAVES * NGT_WAVE_FLOATS(K) >= PER, "the fold reuses the waves' arrays");
     __shared__ float s_all[NGT_WEIGHT_FLOATS(K) + NGT_WAVES * NGT_WAVE_FLOATS(K)];
@@ -514,11 +511,7 @@ __global__ void __launch_bounds__(64 * NGT_WAVES) k_ng_backward_t16(int N, NgMod
             }
             if (hh == 0) {
                 float4 vd = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (active) {                                          // (view direction, distance) (:28-34), as ng_input forms them
-                    const float ox = nax - cam.x, oy = nay - cam.y, oz = naz - cam.z;
-                    const float dd = sqrtf(ox * ox + oy * oy + oz * oz);
-                    vd = make_float4(ox / dd, oy / dd, oz / dd, dd);
-                }
+                if (active) vd = ng_view(make_float3(nax, nay, naz), cam);
                 s_x[32 * NGT_LS + a] = vd.x; s_x[33 * NGT_LS + a] = vd.y; s_x[34 * NGT_LS + a] = vd.z; s_x[35 * NGT_LS + a] = vd.w;
                 s_x[36 * NGT_LS + a] = active ? 1.f : 0.f;             // the constant input: the first-layer bias gradients fall out of G1
             }
@@ -535,14 +528,14 @@ __global__ void __launch_bounds__(64 * NGT_WAVES) k_ng_backward_t16(int N, NgMod
         // whole rows per instruction (4-byte-aligned vector types: 19 vector-memory instructions instead of 60).  In the launch of its own
         // the stage's rows are requested in front of the MLP's recompute (45 registers the single launch does not have) and arrive behind it.
         constexpr int JH = (K + 1) / 2;
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f, s4 = 0.f, s5 = 0.f;
+        float s[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         float3 gxyz[JH], gsc[JH], gof[JH];
         float4 grot[JH];
         auto cov_fetch = [&]() {
             const size_t ic = i < N ? i : N - 1;                       // (unconditional loads: see ngt_row)
             const row4 sa = *reinterpret_cast<const row4*>(scaling + 6 * ic);
             const row2 sb = *reinterpret_cast<const row2*>(scaling + 6 * ic + 4);
-            s0 = sa.x; s1 = sa.y; s2 = sa.z; s3 = sa.w; s4 = sb.x; s5 = sb.y;
+            s[0] = sa.x; s[1] = sa.y; s[2] = sa.z; s[3] = sa.w; s[4] = sb.x; s[5] = sb.y;
 #pragma unroll
             for (int jj = 0; jj < JH; jj++) {
                 const int j = hh * JH + jj, jc = j < K ? j : K - 1;
@@ -561,36 +554,23 @@ __global__ void __launch_bounds__(64 * NGT_WAVES) k_ng_backward_t16(int N, NgMod
             }
         };
         if constexpr (PASS == 1) cov_fetch();
-        ngt_recompute<NG_COV, 7 * K, K>(sW1, sb1, sW2, sb2, s_x, s_t, s_d2, lane);
+        ngt_recompute<NG_COV, 7 * K, C_COV>(sW1, sb1, sW2, sb2, s_x, s_t, s_d2, lane);
         NGT_TICK(2);
         if constexpr (PASS != 1) cov_fetch();
         {
             float ds[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            float dof[JH][3];
+            float3 dof[JH];
 #pragma unroll
             for (int jj = 0; jj < JH; jj++) {
                 const int j = hh * JH + jj;
                 float d[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-                dof[jj][0] = 0.f; dof[jj][1] = 0.f; dof[jj][2] = 0.f;
+                dof[jj] = make_float3(0.f, 0.f, 0.f);
                 const bool on = active && j < K;
                 if (on) {
                     float sr[7];
 #pragma unroll
                     for (int q = 0; q < 7; q++) sr[q] = s_d2[(7 * j + q) * NGT_LS + a];
-                    const float gx = gxyz[jj].x, gy = gxyz[jj].y, gz = gxyz[jj].z, gs0 = gsc[jj].x, gs1 = gsc[jj].y, gs2 = gsc[jj].z;
-                    const float gr0 = grot[jj].x, gr1 = grot[jj].y, gr2 = grot[jj].z, gr3 = grot[jj].w;
-                    const float o0 = gof[jj].x, o1 = gof[jj].y, o2 = gof[jj].z;
-                    dof[jj][0] = gx * s0; dof[jj][1] = gy * s1; dof[jj][2] = gz * s2;      // stored behind the stage's last load (one counter orders both)
-                    ds[0] += gx * o0; ds[1] += gy * o1; ds[2] += gz * o2;
-                    da[0] += gx; da[1] += gy; da[2] += gz;
-                    const float g0 = ng_sigmoid(sr[0]), g1s = ng_sigmoid(sr[1]), g2s = ng_sigmoid(sr[2]);
-                    ds[3] += gs0 * g0; ds[4] += gs1 * g1s; ds[5] += gs2 * g2s;
-                    d[0] = gs0 * s3 * g0 * (1.f - g0); d[1] = gs1 * s4 * g1s * (1.f - g1s); d[2] = gs2 * s5 * g2s * (1.f - g2s);
-                    const float q0 = sr[3], q1 = sr[4], q2 = sr[5], q3 = sr[6];
-                    const float qn = fmaxf(sqrtf(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3), 1e-12f);
-                    const float r0 = q0 / qn, r1 = q1 / qn, r2 = q2 / qn, r3 = q3 / qn;
-                    const float dotp = gr0 * r0 + gr1 * r1 + gr2 * r2 + gr3 * r3;
-                    d[3] = (gr0 - r0 * dotp) / qn; d[4] = (gr1 - r1 * dotp) / qn; d[5] = (gr2 - r2 * dotp) / qn; d[6] = (gr3 - r3 * dotp) / qn;
+                    dof[jj] = ng_cov_delta(sr, s, gof[jj], gxyz[jj], gsc[jj], grot[jj], d, ds, da);   // stored behind the stage's last load (one counter orders both)
                 }
                 if (j < K) {
 #pragma unroll
@@ -605,7 +585,7 @@ __global__ void __launch_bounds__(64 * NGT_WAVES) k_ng_backward_t16(int N, NgMod
 #pragma unroll
                 for (int jj = 0; jj < JH; jj++) {
                     const int j = hh * JH + jj;
-                    if (j < K) put3(d_offset, (size_t)i * K + j, dof[jj][0], dof[jj][1], dof[jj][2]);
+                    if (j < K) put3(d_offset, (size_t)i * K + j, dof[jj].x, dof[jj].y, dof[jj].z);
                 }
             }
             // the halves' shares of the per-anchor sums meet; d_scaling is complete here, d_anchor waits for the view's share
@@ -620,9 +600,9 @@ __global__ void __launch_bounds__(64 * NGT_WAVES) k_ng_backward_t16(int N, NgMod
         }
         __builtin_amdgcn_wave_barrier();
         NGT_TICK(3);
-        db2 += ngt_bias_sums<7 * K>(s_d2, lane, K);
+        db2 += ngt_bias_sums<7 * K>(s_d2, lane, C_COV);
         NGT_TICK(4);
-        ngt_backprop<NG_COV, 7 * K, K, D2R>(sW1, sW2, s_x, s_t, s_d2, lane, dx, g1[NG_COV], g1n[NG_COV >> 1], g2c);
+        ngt_backprop<NG_COV, 7 * K, C_COV, D2R>(sW1, sW2, s_x, s_t, s_d2, lane, dx, g1[NG_COV], g1n[NG_COV >> 1], g2c);
         }
         NGT_TICK(5);
         if constexpr (PASS != 1) {
@@ -634,23 +614,23 @@ __global__ void __launch_bounds__(64 * NGT_WAVES) k_ng_backward_t16(int N, NgMod
             ngt_small_fetch_cond<K, 2>(active, cidx, hh, slj, g_opacity, g_color, g_no, ggr);
         }
         if constexpr (PASS != 2) ngt_small_fetch<K, 0>(active, cidx, hh, slj, g_opacity, g_color, g_no, ggo);
-        ngt_recompute<NG_OPA, K, 0>(sW1, sb1, sW2, sb2, s_x, s_t, s_d2, lane);
+        ngt_recompute<NG_OPA, K, C_OPA>(sW1, sb1, sW2, sb2, s_x, s_t, s_d2, lane);
         ngt_small_deltas<K, 0>(active, a, hh, ggo, s_d2);
         __builtin_amdgcn_wave_barrier();
-        db2 += ngt_bias_sums<K>(s_d2, lane, 0);
-        ngt_backprop<NG_OPA, K, 0, D2R>(sW1, sW2, s_x, s_t, s_d2, lane, dx, g1[NG_OPA], g1n[NG_OPA >> 1], g2o);
+        db2 += ngt_bias_sums<K>(s_d2, lane, C_OPA);
+        ngt_backprop<NG_OPA, K, C_OPA, D2R>(sW1, sW2, s_x, s_t, s_d2, lane, dx, g1[NG_OPA], g1n[NG_OPA >> 1], g2o);
         if constexpr (PASS != 2) ngt_small_fetch<K, 1>(active, cidx, hh, slj, g_opacity, g_color, g_no, ggc);
-        ngt_recompute<NG_COL, K, 8 * K>(sW1, sb1, sW2, sb2, s_x, s_t, s_d2, lane);
+        ngt_recompute<NG_COL, K, C_COL>(sW1, sb1, sW2, sb2, s_x, s_t, s_d2, lane);
         ngt_small_deltas<K, 1>(active, a, hh, ggc, s_d2);
         __builtin_amdgcn_wave_barrier();
-        db2 += ngt_bias_sums<K>(s_d2, lane, 8 * K);
-        ngt_backprop<NG_COL, K, 8 * K, D2R>(sW1, sW2, s_x, s_t, s_d2, lane, dx, g1[NG_COL], g1n[NG_COL >> 1], g2l);
+        db2 += ngt_bias_sums<K>(s_d2, lane, C_COL);
+        ngt_backprop<NG_COL, K, C_COL, D2R>(sW1, sW2, s_x, s_t, s_d2, lane, dx, g1[NG_COL], g1n[NG_COL >> 1], g2l);
         if constexpr (PASS != 2) ngt_small_fetch<K, 2>(active, cidx, hh, slj, g_opacity, g_color, g_no, ggr);
-        ngt_recompute<NG_RD, K, 9 * K>(sW1, sb1, sW2, sb2, s_x, s_t, s_d2, lane);
+        ngt_recompute<NG_RD, K, C_RD>(sW1, sb1, sW2, sb2, s_x, s_t, s_d2, lane);
         ngt_small_deltas<K, 2>(active, a, hh, ggr, s_d2);
         __builtin_amdgcn_wave_barrier();
-        db2 += ngt_bias_sums<K>(s_d2, lane, 9 * K);
-        ngt_backprop<NG_RD, K, 9 * K, D2R>(sW1, sW2, s_x, s_t, s_d2, lane, dx, g1[NG_RD], g1n[NG_RD >> 1], g2r);
+        db2 += ngt_bias_sums<K>(s_d2, lane, C_RD);
+        ngt_backprop<NG_RD, K, C_RD, D2R>(sW1, sW2, s_x, s_t, s_d2, lane, dx, g1[NG_RD], g1n[NG_RD >> 1], g2r);
         }
         NGT_TICK(6);
         // --- input gradients: the feature part leaves in accumulator layout (16 lanes = 64 bytes of an anchor's row); the view /
@@ -683,12 +663,8 @@ __global__ void __launch_bounds__(64 * NGT_WAVES) k_ng_backward_t16(int N, NgMod
             }
         }
         if (active && hh == 0) {
-            const float vx = s_x[32 * NGT_LS + a], vy = s_x[33 * NGT_LS + a], vz = s_x[34 * NGT_LS + a], dist = s_x[35 * NGT_LS + a];   // the tile's own inputs
-            const float dx32 = s_t[0 * NGT_LS + a], dx33 = s_t[1 * NGT_LS + a], dx34 = s_t[2 * NGT_LS + a], dx35 = s_t[3 * NGT_LS + a];
-            const float dv = dx32 * vx + dx33 * vy + dx34 * vz;
-            da[0] += dx32 / dist - vx * (dv / dist) + dx35 * vx;
-            da[1] += dx33 / dist - vy * (dv / dist) + dx35 * vy;
-            da[2] += dx34 / dist - vz * (dv / dist) + dx35 * vz;
+            const float4 vd = make_float4(s_x[32 * NGT_LS + a], s_x[33 * NGT_LS + a], s_x[34 * NGT_LS + a], s_x[35 * NGT_LS + a]);   // the tile's own inputs
+            ng_view_backward(s_t[0 * NGT_LS + a], s_t[1 * NGT_LS + a], s_t[2 * NGT_LS + a], s_t[3 * NGT_LS + a], vd, da);
             if (PASS == 1) { da[0] += pa.x; da[1] += pa.y; da[2] += pa.z; }
             put3(d_anchor, (size_t)i, da[0], da[1], da[2]);
         }
@@ -831,36 +807,34 @@ __global__ void __launch_bounds__(64 * NGF_WAVES) k_ng_opacity_t16(int N, NgMode
         }
         if (hh == 0) {
             float4 vd = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (active) {                                              // (view direction, distance) (:28-34), as ng_input forms them
-                const float ox = an.x - cam.x, oy = an.y - cam.y, oz = an.z - cam.z;
-                const float dd = sqrtf(ox * ox + oy * oy + oz * oz);
-                vd = make_float4(ox / dd, oy / dd, oz / dd, dd);
-            }
+            if (active) vd = ng_view(an, cam);
             s_x[32 * NGT_LS + a] = vd.x; s_x[33 * NGT_LS + a] = vd.y; s_x[34 * NGT_LS + a] = vd.z; s_x[35 * NGT_LS + a] = vd.w;
         }
         __builtin_amdgcn_wave_barrier();
-        ngt_recompute<NG_OPA, K, 0>(sW1, sb1, sW2, sb2, s_x, s_t, s_y, lane);
+        ngt_recompute<NG_OPA, K, ng_col0(NG_OPA, K)>(sW1, sb1, sW2, sb2, s_x, s_t, s_y, lane);
         if (active) {
             float o[JH];
+            uint32_t keep[JH];
 #pragma unroll
             for (int jj = 0; jj < JH; jj++) {
                 const int j = hh * JH + jj < K ? hh * JH + jj : K - 1;
-                o[jj] = tanhf(s_y[j * NGT_LS + a]);                   // nn.Tanh closes the opacity MLP (gaussian_model.py:118); keep = o > 0 (:67)
+                const NgOpacity r = ng_opacity_out(s_y[j * NGT_LS + a]);
+                o[jj] = r.o; keep[jj] = r.keep ? 1u : 0u;
             }
             const size_t w0 = (size_t)cidx * K + hh * JH, f0 = (size_t)i * K + hh * JH;
             if (K == 6) {                                              // (the lane's three offsets are neighbours: one store per array)
                 *reinterpret_cast<row3*>(neural_opacity + w0) = row3{o[0], o[1], o[JH - 1]};
-                *reinterpret_cast<ngt_u3*>(sel_flags + f0) = ngt_u3{o[0] > 0.f ? 1u : 0u, o[1] > 0.f ? 1u : 0u, o[JH - 1] > 0.f ? 1u : 0u};
+                *reinterpret_cast<ngt_u3*>(sel_flags + f0) = ngt_u3{keep[0], keep[1], keep[JH - 1]};
             } else if (K == 4) {
                 *reinterpret_cast<row2*>(neural_opacity + w0) = row2{o[0], o[1]};
-                *reinterpret_cast<ngt_u2*>(sel_flags + f0) = ngt_u2{o[0] > 0.f ? 1u : 0u, o[1] > 0.f ? 1u : 0u};
+                *reinterpret_cast<ngt_u2*>(sel_flags + f0) = ngt_u2{keep[0], keep[1]};
             }
 #pragma unroll
             for (int jj = 0; jj < JH; jj++) {
                 const int j = hh * JH + jj;
                 if (j < K) {
-                    mask[w0 + jj] = o[jj] > 0.0f ? 1 : 0;
-                    if (K != 6 && K != 4) { neural_opacity[w0 + jj] = o[jj]; sel_flags[f0 + jj] = o[jj] > 0.0f ? 1u : 0u; }
+                    mask[w0 + jj] = (uint8_t)keep[jj];
+                    if (K != 6 && K != 4) { neural_opacity[w0 + jj] = o[jj]; sel_flags[f0 + jj] = keep[jj]; }
                 }
             }
         }
@@ -898,7 +872,7 @@ __global__ void __launch_bounds__(64 * NGF_WAVES) k_ng_decode_t16(int N, NgModel
         // which the MLPs run)
         uint32_t vis = 0u, cidx = 0u, nsel[JH], nslot[JH];
         float3 an = make_float3(0.f, 0.f, 0.f), of[JH];
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f, s4 = 0.f, s5 = 0.f;
+        float s[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         float4 nf[4];
 #pragma unroll
         for (int jj = 0; jj < JH; jj++) { nsel[jj] = 0u; nslot[jj] = 0u; of[jj] = make_float3(0.f, 0.f, 0.f); }
@@ -908,7 +882,7 @@ __global__ void __launch_bounds__(64 * NGF_WAVES) k_ng_decode_t16(int N, NgModel
             if (i >= N) vis = 0u;
             const row4 sa = *reinterpret_cast<const row4*>(scaling + 6 * ic);
             const row2 sb = *reinterpret_cast<const row2*>(scaling + 6 * ic + 4);
-            s0 = sa.x; s1 = sa.y; s2 = sa.z; s3 = sa.w; s4 = sb.x; s5 = sb.y;
+            s[0] = sa.x; s[1] = sa.y; s[2] = sa.z; s[3] = sa.w; s[4] = sb.x; s[5] = sb.y;
 #pragma unroll
             for (int jj = 0; jj < JH; jj++) {
                 const int j = hh * JH + jj, jc = j < K ? j : K - 1;
@@ -948,16 +922,12 @@ __global__ void __launch_bounds__(64 * NGF_WAVES) k_ng_decode_t16(int N, NgModel
         }
         if (hh == 0) {
             float4 vd = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (active) {
-                const float ox = an.x - cam.x, oy = an.y - cam.y, oz = an.z - cam.z;
-                const float dd = sqrtf(ox * ox + oy * oy + oz * oz);
-                vd = make_float4(ox / dd, oy / dd, oz / dd, dd);
-            }
+            if (active) vd = ng_view(an, cam);
             s_x[32 * NGT_LS + a] = vd.x; s_x[33 * NGT_LS + a] = vd.y; s_x[34 * NGT_LS + a] = vd.z; s_x[35 * NGT_LS + a] = vd.w;
         }
         __builtin_amdgcn_wave_barrier();
-        ngt_recompute<NG_COL, K, 8 * K>(sW1, sb1, sW2, sb2, s_x, s_t, s_yc, lane);
-        ngt_recompute<NG_RD, K, 9 * K>(sW1, sb1, sW2, sb2, s_x, s_t, s_yr, lane);
+        ngt_recompute<NG_COL, K, ng_col0(NG_COL, K)>(sW1, sb1, sW2, sb2, s_x, s_t, s_yc, lane);
+        ngt_recompute<NG_RD, K, ng_col0(NG_RD, K)>(sW1, sb1, sW2, sb2, s_x, s_t, s_yr, lane);
         float colv[JH], rdv[JH];                                       // (the covariance outputs overwrite these rows too)
 #pragma unroll
         for (int jj = 0; jj < JH; jj++) {
@@ -965,22 +935,21 @@ __global__ void __launch_bounds__(64 * NGF_WAVES) k_ng_decode_t16(int N, NgModel
             colv[jj] = s_yc[j * NGT_LS + a]; rdv[jj] = s_yr[j * NGT_LS + a];
         }
         __builtin_amdgcn_wave_barrier();
-        ngt_recompute<NG_COV, 7 * K, K>(sW1, sb1, sW2, sb2, s_x, s_t, s_x, lane);     // its outputs land on x (dead behind the hidden layer)
+        ngt_recompute<NG_COV, 7 * K, ng_col0(NG_COV, K)>(sW1, sb1, sW2, sb2, s_x, s_t, s_x, lane);     // its outputs land on x (dead behind the hidden layer)
 #pragma unroll
         for (int jj = 0; jj < JH; jj++) {
             const int j = hh * JH + jj;
             if (j < K && vis != 0u && nsel[jj] != 0u) {
                 const size_t r = nslot[jj];
-                put3(o_xyz, r, an.x + of[jj].x * s0, an.y + of[jj].y * s1, an.z + of[jj].z * s2);                        // :111-112
-                put2(o_color, r, ng_sigmoid(colv[jj]), ng_sigmoid(rdv[jj]));                                             // :85-87
-                o_opacity[r] = nop[jj];
                 float sr[7];
 #pragma unroll
                 for (int q = 0; q < 7; q++) sr[q] = s_x[(7 * j + q) * NGT_LS + a];
-                put3(o_scaling, r, s3 * ng_sigmoid(sr[0]), s4 * ng_sigmoid(sr[1]), s5 * ng_sigmoid(sr[2]));             // :107
-                const float q0 = sr[3], q1 = sr[4], q2 = sr[5], q3 = sr[6];
-                const float qn = fmaxf(sqrtf(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3), 1e-12f);                           // F.normalize, :108
-                put4(o_rot, r, q0 / qn, q1 / qn, q2 / qn, q3 / qn);
+                const NgRow v = ng_decode_row(an, of[jj], s, colv[jj], rdv[jj], sr);
+                put3(o_xyz, r, v.xyz.x, v.xyz.y, v.xyz.z);
+                put2(o_color, r, v.color.x, v.color.y);
+                o_opacity[r] = nop[jj];
+                put3(o_scaling, r, v.scaling.x, v.scaling.y, v.scaling.z);
+                put4(o_rot, r, v.rot.x, v.rot.y, v.rot.z, v.rot.w);
             }
         }
         __builtin_amdgcn_wave_barrier();

@@ -254,3 +254,51 @@ def test_decode_queued_behind_the_selection_equals_the_waiting_form(hip_lib_buil
     assert queued["xyz"].shape == (M, 3) and queued["rot"].shape == (M, 4)
     for key in queued:
         assert np.array_equal(queued[key], waited[key]), key
+
+
+# The decode's per-row branches at the smallest shapes where they all occur: an invisible anchor, a visible anchor none of whose offsets is
+# selected, and a partial last tile.  33 = one whole 32-anchor tile and one row, and half a 64-anchor tile; 97 = the same with several
+# tiles; k = 5: the odd count whose lane halves own 3 + 2 offsets; k = 8: the 32x32x2 path.  (N, k, seed, visible, visible with no offset
+# selected, M); the seeds were chosen on the oracle so that no neural opacity lies within 2e-3 of zero (min |opacity| 0.0069, 0.0023,
+# 0.0020): rounding cannot flip the mask.
+SMALL_CASES = [(33, 5, 221, 24, 1, 50), (33, 8, 233, 22, 15, 16), (97, 5, 203, 73, 9, 102)]
+SMALL_FORMS = {"default": {}, "t16_one_launch": {"LIDARGS_NG_T16_PASSES": "1"},
+               "tiles_32x32": {"LIDARGS_NG_BACKWARD_T16": "0", "LIDARGS_NG_FORWARD_T16": "0"}, "act_buffers": {"LIDARGS_NG_ACT_BUFFERS": "1"}}
+_small_oracle = {}
+
+
+def small_oracle(N, k, seed):
+    """The oracle's forward and backward of a small case, computed once and shared by the case's forms."""
+    if (N, k, seed) not in _small_oracle:
+        p, cam, vis, rng = sc.make_anchor_model(N, k, seed, (True, False, True))
+        f = ng.forward(p, cam, vis)
+        M = f["xyz"].shape[0]
+        ups = [rng.normal(size=s).astype(np.float32) for s in ((M, 3), (M, 2), (M, 1), (M, 3), (M, 4))]
+        _small_oracle[(N, k, seed)] = (p, cam, vis, f, ups, ng.backward(p, f, *ups))
+    return _small_oracle[(N, k, seed)]
+
+
+@pytest.mark.parametrize("case,form", [(c, n) for c in SMALL_CASES for n in SMALL_FORMS if c[1] == 5 or n in ("default", "act_buffers")],
+                         ids=lambda v: v if isinstance(v, str) else "N%d_k%d" % v[:2])
+def test_decode_row_branches_at_small_shapes(case, form, hip_lib_built, monkeypatch):
+    N, k, seed, n_vis, n_unselected, M = case
+    for name, value in SMALL_FORMS[form].items():
+        monkeypatch.setenv(name, value)
+    p, cam, vis, f, ups, g = small_oracle(N, k, seed)
+    selected = np.asarray(f["mask"]).reshape(-1, k).any(1)             # per visible anchor: any offset kept
+    assert (int(vis.sum()), int((~selected).sum()), f["xyz"].shape[0]) == (n_vis, n_unselected, M)
+    r = run_hip(p, cam, vis, ups)
+    flips = int((r["mask"] != f["mask"]).sum())
+    assert flips == 0, f"{flips} opacity-sign flips"
+    hid = f["_ctx"]["hid"]["opacity"]                                  # the opacities' scale: see test_decode_matches_oracle_random
+    op_scale = float((np.abs(hid) @ np.abs(p["opacity_W2"]).T + np.abs(p["opacity_b2"])).max())
+    for key in ("xyz", "color", "opacity", "scaling", "rot", "neural_opacity"):
+        parity(key, r[key], f[key], scale=(op_scale if "opacity" in key else None))
+    for key in ("anchor_feat", "anchor", "offset", "scaling"):
+        parity("d" + key, r["g_" + key], g[key])
+    for key in PARAM_KEYS:
+        parity("d" + key, r["g_" + key], g[key], rtol=5e-4)
+    idle = ~vis
+    idle[np.flatnonzero(vis)[~selected]] = True                        # invisible, or visible with nothing selected: no gradient at all
+    for key in ("anchor_feat", "anchor", "offset", "scaling"):
+        assert not r["g_" + key][idle].any(), key
