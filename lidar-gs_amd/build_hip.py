@@ -5,6 +5,7 @@
 Output: lidar-gs_amd/diff_lidargs_rasterization/liblidargs_hip.so  (git-ignored, travels with gpurun)
         lidar-gs_amd/lidargs_optim/liblidargs_optim.so             (the optimizer step: csrc/adam.hip alone, include_optim/)
         lidar-gs_amd/liblidargs_decode_options.so                  (feature bank + appearance in front of the decode: csrc/decode_options.hip alone, include_decode/)
+        lidar-gs_amd/tinycudann/liblidargs_tcnn.so                 (the tinycudann stand-in: csrc/raydrop_mlp.hip alone, include_tcnn/)
 
 Per-file flags: the per-Gaussian kernels (preprocess.hip) are HBM-bound, so they are built with
 -ffp-contract=off: every expression rounds as written, which keeps the unit vectors s = p/|p| that
@@ -50,7 +51,13 @@ DECODE_INCLUDE = os.path.join(HERE, "..", "include_decode")
 DECODE_SOURCES = {
     "decode_options.hip": [],
 }
-_OWN_TARGET = {**OPTIM_SOURCES, **DECODE_SOURCES}          # sources that are not part of liblidargs_hip.so
+# The tinycudann stand-in (frequency encoding, fused MLP): a target and a header directory of its own, like the two above.
+TCNN_OUT = os.path.join(HERE, "tinycudann", "liblidargs_tcnn.so")
+TCNN_INCLUDE = os.path.join(HERE, "..", "include_tcnn")
+TCNN_SOURCES = {
+    "raydrop_mlp.hip": [],
+}
+_OWN_TARGET = {**OPTIM_SOURCES, **DECODE_SOURCES, **TCNN_SOURCES}          # sources that are not part of liblidargs_hip.so
 
 
 def build_id():
@@ -61,7 +68,8 @@ def build_id():
     files = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC)) + sorted(
         os.path.join(HERE, "..", "include", f) for f in os.listdir(os.path.join(HERE, "..", "include"))) + sorted(
         os.path.join(OPTIM_INCLUDE, f) for f in os.listdir(OPTIM_INCLUDE)) + sorted(
-        os.path.join(DECODE_INCLUDE, f) for f in os.listdir(DECODE_INCLUDE)) + [os.path.abspath(__file__)]
+        os.path.join(DECODE_INCLUDE, f) for f in os.listdir(DECODE_INCLUDE)) + sorted(
+        os.path.join(TCNN_INCLUDE, f) for f in os.listdir(TCNN_INCLUDE)) + [os.path.abspath(__file__)]
     for f in files:
         h.update(os.path.basename(f).encode()); h.update(open(f, "rb").read())
     return h.hexdigest()[:12]
@@ -102,12 +110,17 @@ def decode_needs_build():
                   + [os.path.join(DECODE_INCLUDE, f) for f in os.listdir(DECODE_INCLUDE)] + [__file__])
 
 
+def tcnn_needs_build():
+    return _stale(TCNN_OUT, [os.path.join(CSRC, f) for f in TCNN_SOURCES]
+                  + [os.path.join(TCNN_INCLUDE, f) for f in os.listdir(TCNN_INCLUDE)] + [__file__])
+
+
 def build(force=False, verbose=False):
     """Up-to-date check and build under an exclusive file lock: the ranks of `bench.py --gpus N` (one process per GPU) all call this
     at start-up, and only the first may compile -- the others wait and then find the library up to date.  The link goes to a
     temporary name and is moved into place, so a process that loaded the library earlier never sees a half-written file.
-    Builds the three libraries, each when its own dependencies are newer; returns the main library's path."""
-    if not force and not needs_build() and not optim_needs_build() and not decode_needs_build():
+    Builds the four libraries, each when its own dependencies are newer; returns the main library's path."""
+    if not force and not needs_build() and not optim_needs_build() and not decode_needs_build() and not tcnn_needs_build():
         return OUT
     import fcntl
     os.makedirs(OBJ, exist_ok=True)
@@ -120,6 +133,8 @@ def build(force=False, verbose=False):
                 _build_locked(OPTIM_SOURCES, OPTIM_OUT, verbose)
             if force or decode_needs_build():
                 _build_locked(DECODE_SOURCES, DECODE_OUT, verbose)
+            if force or tcnn_needs_build():
+                _build_locked(TCNN_SOURCES, TCNN_OUT, verbose)
             return OUT
         finally:
             fcntl.flock(lock, fcntl.LOCK_UN)
