@@ -601,6 +601,45 @@ int lidargs_debug_emit_instances(size_t P, int compact, int tile_rows, int tiles
 int lidargs_debug_tile_ranges(size_t R, int key_bytes, const void* tile_sorted, const unsigned* R_dev, unsigned* ranges, int tiles, unsigned* zero,
                               int n_zero, int prezeroed, void* stream);
 
+/* Test hooks of the two per-Gaussian stages (no reference counterpart as entry points; never called by the binding): the library's own
+ * launchers of the preprocess and of the backward's last two launches on caller-supplied arrays, so that tests/ can hold every array they
+ * write against a float64 restatement (tests/preprocess_ref.py).  Device pointers; nothing waits for the stream; no dispatch is decided
+ * here.  Each returns 0 or a negative LIDARGS_ERR_*, the latter before any device work.
+ *
+ * lidargs_debug_preprocess: the 3-D preprocess of a width x height frame of P Gaussians with the parameters a forward derives from the
+ * same image size (column steps, 16 x 4 grid).  Inputs as lidargs_forward's (scales + rotations or cov3D_precomp); near_f / far_f the
+ * range limits as floats; [shell_lo, shell_hi) the range shell (-inf, inf: none); [tile_x_lo, tile_x_hi) the window of 16-pixel tile
+ * columns that is binned (0, ceil(width / 16): all); compact: 4-byte span records; prune: the conservative footprint pruning on (an
+ * argument, not LIDARGS_NO_PRUNE: one process can ask for both); n_valid (nullable): device word, rows at and behind *n_valid are padding
+ * and are culled unread.
+ *   rec f32[16 P]: the splat records (written for binned Gaussians alone); rowspan u32[P] (the same); spans u32[P] (compact) or u32[4 P];
+ *   key u32[P]: the float bits of the range, 0xFFFFFFFF for Gaussians binned nowhere; touched u8[P]: cleared; totals u32[LG_TOTALS_WORDS =
+ *   920]: cleared by the hook, then the 64 slots of block sums (words 8..: four u64 instance totals for tile heights 4 / 8 / 16 / 32 per
+ *   slot; words 536..: (~smallest, largest) visible key per slot; words 664..: two u64 per slot, visible Gaussians and the reference's
+ *   tiles_touched); radii i32[P]; radii_xy i32[2 P] (nullable); coltab f32[2 width], rowtab f32[2 height]: the pixel-ray tables (both or
+ *   neither).
+ *   Refused: P < 0, height < 2, an image too large for a forward; a window outside the grid; compact where the image has more than 256
+ *   tile columns or rows; a NULL required pointer.  P = 0: returns 0, nothing is launched or written.
+ *
+ * lidargs_debug_gaussian_backward: a backward's first launch (the touched lists, the cleared lines, the zeroed rows) on touched u8[P] and
+ * gacc f32[4 line_f4 P] (line_f4 = 4: the 64-byte line of the 3-D variant, 8: the surfel variant's), and its last launch, the
+ * per-Gaussian chain on the listed Gaussians' lines (line_f4 = 4 alone).  In a backward the blend fills the cleared lines between the
+ * two, so `stage` picks the launches: 1 = the first alone; 2 = the chain alone, on gacc as the caller filled it and on tlist / tcount as
+ * a stage-1 call left them; 0 = both (the chain then reads the zeros the first launch left in the marked lines).  The twelve gradient
+ * arrays are lidargs_backward's; NULL ones are skipped, except that a call that runs the chain requires the ones lidargs_backward
+ * requires.  tlist u8[P + 256], tcount u16[P / 256 + 64].
+ *   Refused: P < 0; line_f4 not 4 or 8; stage not 0, 1, 2, or not 1 with line_f4 = 8; a NULL required pointer.  P = 0: returns 0. */
+int lidargs_debug_preprocess(int P, int width, int height, const float* means3D, const float* colors, const float* opacities, const float* scales,
+                             float scale_modifier, const float* rotations, const float* cov3D_precomp, const float* viewmatrix, const float* beams,
+                             float near_f, float far_f, float shell_lo, float shell_hi, int tile_x_lo, int tile_x_hi, int compact, int prune,
+                             const unsigned* n_valid, float* rec, unsigned* rowspan, unsigned* spans, unsigned* key, unsigned char* touched,
+                             unsigned* totals, int* radii, int* radii_xy, float* coltab, float* rowtab, void* stream);
+int lidargs_debug_gaussian_backward(int P, int line_f4, int stage, const unsigned char* touched, float* gacc, const float* means3D,
+                                    const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                                    const float* viewmatrix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                                    float* dL_ddepths, float* dL_dmean3D, float* dL_dsphere_means3D, float* dL_dbasis_u1, float* dL_dbasis_u2,
+                                    float* dL_dcov3D, float* dL_dscale, float* dL_drot, unsigned char* tlist, unsigned short* tcount, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

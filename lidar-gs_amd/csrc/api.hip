@@ -512,6 +512,23 @@ struct FrameMode {
     const uint32_t* n_valid = nullptr;
 };
 
+// The preprocess' parameters of a whole frame on `grid`: no column wedge, full span records, pruning on, every row valid.  The forward,
+// the visible filter and the test hook (lidargs_debug_preprocess) all start from here, so the column steps are the same values for each.
+lg::PreprocessParams preprocess_params(int P, const lg::TileGrid& grid, float scale_modifier, float near_f, float far_f, float shell_lo,
+                                       float shell_hi, const float* viewmatrix) {
+    lg::PreprocessParams pp;
+    pp.P = P; pp.W = grid.W; pp.H = grid.H; pp.TH = grid.TH; pp.tiles_x = grid.tiles_x; pp.tiles_y = grid.tiles_y;
+    pp.scale_modifier = scale_modifier;
+    pp.near_f = near_f; pp.far_f = far_f; pp.shell_lo = shell_lo; pp.shell_hi = shell_hi;
+    pp.tile_x_lo = 0; pp.tile_x_hi = grid.tiles_x; pp.compact = 0; pp.prune = 1;
+    const float pi_f = 3.14159265358979323846f;
+    pp.col_step = 2 * pi_f / grid.W; pp.inv_col_step = (1.f / pp.col_step) * 1.000001f;                                  // R3/cr/forward.cu:334
+    pp.tan_col_step = tanf(2 * pi_f / grid.W);                         // R3/cr/forward.cu:362
+    pp.view = viewmatrix;
+    pp.n_valid = nullptr;
+    return pp;
+}
+
 int forward_impl(lidargs_alloc_fn geometry_alloc, void* geometry_user, lidargs_alloc_fn binning_alloc, void* binning_user,
                  lidargs_alloc_fn image_alloc, void* image_user, int P, const float* background, int width, int height,
                  const float* means3D, const float* colors_precomp, const float* opacities, const float* scales,
@@ -547,11 +564,7 @@ int forward_impl(lidargs_alloc_fn geometry_alloc, void* geometry_user, lidargs_a
     lg::ImgView img; lg::img_carve(img_p, width, height, grid4.num_tiles(), &img);
     LG_HIP(hipMemsetAsync(geom.totals, 0, LG_TOTALS_WORDS * sizeof(uint32_t), stream));
 
-    lg::PreprocessParams pp;
-    pp.P = P; pp.W = width; pp.H = height; pp.TH = 4; pp.tiles_x = grid4.tiles_x; pp.tiles_y = grid4.tiles_y;
-    pp.scale_modifier = scale_modifier;
-    pp.near_f = near_f; pp.far_f = far_f; pp.shell_lo = shell_lo; pp.shell_hi = shell_hi;
-    pp.tile_x_lo = 0; pp.tile_x_hi = grid4.tiles_x;
+    lg::PreprocessParams pp = preprocess_params(P, grid4, scale_modifier, near_f, far_f, shell_lo, shell_hi, viewmatrix);
     pp.compact = lg::compact_spans(grid4.tiles_x, height) ? 1 : 0;
     pp.prune = lg::prune_footprints() ? 1 : 0;
     if (col_lo >= 0) {                                                   // column wedge: whole 16-pixel tile columns
@@ -559,10 +572,6 @@ int forward_impl(lidargs_alloc_fn geometry_alloc, void* geometry_user, lidargs_a
             return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward: a column wedge must be [multiple of 16, multiple of 16 or width)%s");
         pp.tile_x_lo = col_lo / LG_TILE_W; pp.tile_x_hi = (col_hi + LG_TILE_W - 1) / LG_TILE_W;
     }
-    const float pi_f = 3.14159265358979323846f;
-    pp.col_step = 2 * pi_f / width; pp.inv_col_step = (1.f / pp.col_step) * 1.000001f;                                    // R3/cr/forward.cu:334
-    pp.tan_col_step = tanf(2 * pi_f / width);                          // R3/cr/forward.cu:362
-    pp.view = viewmatrix;
     pp.n_valid = mode.n_valid;
 
     lg::launch_preprocess(pp, means3D, scales, rotations, opacities, colors_precomp, cov3D_precomp, beams, radii, radii_xy,
@@ -767,16 +776,8 @@ int lidargs_visible_filter(lidargs_alloc_fn geometry_alloc, void* geometry_user,
         return fail(LIDARGS_ERR_INVALID_ARGUMENT, "visible_filter: NULL required pointer%s");
     if (!cov3D_precomp && (!scales || !rotations)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "visible_filter: need scales+rotations or cov3D_precomp%s");
     const lg::TileGrid grid = lg::make_grid(width, height, lg::tile_rows());
-    lg::PreprocessParams pp;
-    pp.P = P; pp.W = width; pp.H = height; pp.TH = grid.TH; pp.tiles_x = grid.tiles_x; pp.tiles_y = grid.tiles_y;
-    pp.scale_modifier = scale_modifier;
-    pp.near_f = (float)lidar_near; pp.far_f = (float)lidar_far;
-    pp.shell_lo = -std::numeric_limits<float>::infinity(); pp.shell_hi = std::numeric_limits<float>::infinity();
-    pp.tile_x_lo = 0; pp.tile_x_hi = grid.tiles_x; pp.compact = 0; pp.prune = 1;
-    const float pi_f = 3.14159265358979323846f;
-    pp.col_step = 2 * pi_f / width; pp.inv_col_step = (1.f / pp.col_step) * 1.000001f;
-    pp.tan_col_step = tanf(2 * pi_f / width);
-    pp.view = viewmatrix;
+    const float inf = std::numeric_limits<float>::infinity();
+    const lg::PreprocessParams pp = preprocess_params(P, grid, scale_modifier, (float)lidar_near, (float)lidar_far, -inf, inf, viewmatrix);
     lg::GeomView none; memset(&none, 0, sizeof none);
     lg::launch_preprocess(pp, means3D, scales, rotations, nullptr, nullptr, cov3D_precomp, beam_inclinations, radii, radii_xy, none,
                           nullptr, true, stream);
@@ -923,6 +924,76 @@ int lidargs_debug_tile_ranges(size_t R, int key_bytes, const void* tile_sorted, 
     lg::launch_tile_ranges(static_cast<const uint32_t*>(tile_sorted), R, reinterpret_cast<uint2*>(ranges), tiles, stream, R_dev, key_bytes == 2, zero, n_zero,
                            prezeroed != 0);
     LG_STAGE_CHECK("debug tile ranges");
+    return 0;
+}
+
+// Test hooks of the two per-Gaussian stages (preprocess.hip): the product's own launchers on caller-supplied arrays; no dispatch is decided here.
+int lidargs_debug_preprocess(int P, int width, int height, const float* means3D, const float* colors, const float* opacities, const float* scales,
+                             float scale_modifier, const float* rotations, const float* cov3D_precomp, const float* viewmatrix, const float* beams,
+                             float near_f, float far_f, float shell_lo, float shell_hi, int tile_x_lo, int tile_x_hi, int compact, int prune,
+                             const unsigned* n_valid, float* rec, unsigned* rowspan, unsigned* spans, unsigned* key, unsigned char* touched,
+                             unsigned* totals, int* radii, int* radii_xy, float* coltab, float* rowtab, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const int debug = 0;
+    if (P < 0 || width <= 0 || height < 2 || height > 65535 || width > 65535 * 16) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_preprocess: bad sizes%s");
+    const lg::TileGrid grid4 = lg::make_grid(width, height, 4);
+    if (tile_x_lo < 0 || tile_x_hi <= tile_x_lo || tile_x_hi > grid4.tiles_x) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_preprocess: the tile-column window lies outside the grid%s");
+    if (compact && !lg::compact_spans(grid4.tiles_x, height)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_preprocess: compact span records do not hold this image%s");
+    if (!means3D || !colors || !opacities || !viewmatrix || !beams || !rec || !rowspan || !spans || !key || !touched || !totals || !radii)   // radii_xy: optional
+        return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_preprocess: NULL required pointer%s");
+    if (!cov3D_precomp && (!scales || !rotations)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_preprocess: need scales+rotations or cov3D_precomp%s");
+    if ((coltab == nullptr) != (rowtab == nullptr)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_preprocess: the two ray tables come together%s");
+    if (P == 0) return 0;
+    lg::PreprocessParams pp = preprocess_params(P, grid4, scale_modifier, near_f, far_f, shell_lo, shell_hi, viewmatrix);
+    pp.tile_x_lo = tile_x_lo; pp.tile_x_hi = tile_x_hi; pp.compact = compact ? 1 : 0; pp.prune = prune ? 1 : 0; pp.n_valid = n_valid;
+    lg::GeomView geom; memset(&geom, 0, sizeof geom);
+    geom.rec = reinterpret_cast<float4*>(rec); geom.rowspan = rowspan; geom.spans = reinterpret_cast<uint4*>(spans); geom.key_a = key;
+    geom.touched = touched; geom.totals = totals;
+    lg::ImgView img; memset(&img, 0, sizeof img);
+    img.coltab = reinterpret_cast<float2*>(coltab); img.rowtab = reinterpret_cast<float2*>(rowtab);
+    LG_HIP(hipMemsetAsync(totals, 0, LG_TOTALS_WORDS * sizeof(uint32_t), stream));     // as forward_impl does
+    lg::launch_preprocess(pp, means3D, scales, rotations, opacities, colors, cov3D_precomp, beams, radii, radii_xy, geom, coltab ? &img : nullptr, false, stream);
+    LG_STAGE_CHECK("debug preprocess");
+    return 0;
+}
+
+int lidargs_debug_gaussian_backward(int P, int line_f4, int stage, const unsigned char* touched, float* gacc, const float* means3D,
+                                    const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                                    const float* viewmatrix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                                    float* dL_ddepths, float* dL_dmean3D, float* dL_dsphere_means3D, float* dL_dbasis_u1, float* dL_dbasis_u2,
+                                    float* dL_dcov3D, float* dL_dscale, float* dL_drot, unsigned char* tlist, unsigned short* tcount, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const int debug = 0;
+    if (P < 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_gaussian_backward: bad size%s");
+    if (line_f4 != 4 && line_f4 != 8) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_gaussian_backward: line_f4 must be 4 or 8%s");
+    if (stage < 0 || stage > 2 || (line_f4 == 8 && stage != 1)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_gaussian_backward: stage must be 0, 1 or 2, and 1 for the surfel line%s");
+    if (!touched || !gacc || !tlist || !tcount) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_gaussian_backward: NULL required pointer%s");
+    const bool chain = stage != 1;
+    // the chain's rows, as backward_impl requires them (dL_dconic, dL_ddepths, dL_dsphere_means3D, dL_dbasis_u1/u2 stay optional)
+    if (chain && (!means3D || !viewmatrix || !dL_dmean2D || !dL_dopacity || !dL_dcolor || !dL_dmean3D || !dL_dscale || !dL_drot ||
+                  (cov3D_precomp && !dL_dcov3D)))
+        return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_gaussian_backward: NULL required pointer%s");
+    if (chain && !cov3D_precomp && (!scales || !rotations)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_gaussian_backward: need scales+rotations or cov3D_precomp%s");
+    if (P == 0) return 0;
+    lg::ZeroRows zr;
+    zr.add(dL_dmean2D, 4); zr.add(dL_dconic, 4); zr.add(dL_dopacity, 1); zr.add(dL_dcolor, 2); zr.add(dL_ddepths, 1); zr.add(dL_dmean3D, 3);
+    zr.add(dL_dsphere_means3D, 3); zr.add(dL_dbasis_u1, 3); zr.add(dL_dbasis_u2, 3); zr.add(dL_dcov3D, 6); zr.add(dL_dscale, 3); zr.add(dL_drot, 4);
+    if (stage != 2) {
+        lg::launch_zero_touched(touched, reinterpret_cast<float4*>(gacc), line_f4, (size_t)P, tlist, tcount, zr, stream);
+        LG_STAGE_CHECK("debug zero touched");
+    }
+    if (!chain) return 0;
+    lg::GaussBwdArgs gb;
+    gb.P = P; gb.scale_modifier = scale_modifier;
+    gb.view = viewmatrix;
+    gb.means3D = means3D; gb.scales = scales; gb.rotations = rotations; gb.cov3D_precomp = cov3D_precomp; gb.radii = nullptr;
+    gb.gacc = gacc; gb.tlist = tlist; gb.tcount = tcount;
+    gb.dL_dmean2D = dL_dmean2D; gb.dL_dconic = dL_dconic; gb.dL_dopacity = dL_dopacity; gb.dL_dcolor = dL_dcolor;
+    gb.dL_ddepths = dL_ddepths; gb.dL_dbasis_u1 = dL_dbasis_u1; gb.dL_dbasis_u2 = dL_dbasis_u2;
+    gb.dL_dsphere = dL_dsphere_means3D; gb.dL_dmean3D = dL_dmean3D; gb.dL_dcov3D = dL_dcov3D; gb.dL_dscale = dL_dscale;
+    gb.dL_drot = dL_drot;
+    lg::launch_gaussian_backward(gb, stream);
+    LG_STAGE_CHECK("debug gaussian backward");
     return 0;
 }
 

@@ -29,6 +29,7 @@ import torch
 
 import lidargs_scenes as sc
 from oracle import lgo
+from preprocess_ref import k1_one as _k1      # K1 for one Gaussian, as the source writes it
 
 F64 = torch.float64
 
@@ -155,38 +156,6 @@ def test_blend_gradients_are_autograd_of_the_forward_loop(run):
     _close("dL_dsphere", g["dL_dsphere"], gs)
     _close("dL_dmean2D.xy", g["dL_dmeans2D"][:, :2], ge)
     assert np.all(g["dL_dmeans2D"][:, 3] == 0.0)                                             # :780
-
-
-def _mat3_cols(*c):
-    """glm::mat3(a, b, c, d, e, f, g, h, i): consecutive triples are COLUMNS -> math matrix [row, col]."""
-    return torch.stack([torch.stack(c[0:3]), torch.stack(c[3:6]), torch.stack(c[6:9])], 1)
-
-
-def _k1(means3D, scales, rotations, vm, mod=1.0):
-    """preprocessCUDA's per-Gaussian outputs for one Gaussian, as written (R3/cr/forward.cu:216-253, :95-119, :146-169, :298-322, :369-372).
-    Returns (conic [3], dist, u1 [3], u2 [3], sphere [3], (a, b, c))."""
-    p = means3D
-    pv = torch.stack([vm[0] * p[0] + vm[4] * p[1] + vm[8] * p[2] + vm[12], vm[1] * p[0] + vm[5] * p[1] + vm[9] * p[2] + vm[13],
-                      vm[2] * p[0] + vm[6] * p[1] + vm[10] * p[2] + vm[14]])                   # transformPoint4x3, auxiliary.h:94-102
-    dist = torch.sqrt((pv * pv).sum())
-    one, zero = torch.ones((), dtype=F64), torch.zeros((), dtype=F64)
-    S = torch.diag(torch.stack([mod * scales[0], mod * scales[1], mod * scales[2]]))
-    r, x, y, z = rotations
-    R = _mat3_cols(1 - 2 * (y * y + z * z), 2 * (x * y - r * z), 2 * (x * z + r * y),
-                   2 * (x * y + r * z), 1 - 2 * (x * x + z * z), 2 * (y * z - r * x),
-                   2 * (x * z - r * y), 2 * (y * z + r * x), 1 - 2 * (x * x + y * y))
-    M = S @ R
-    Sigma = M.T @ M                                                                        # :244
-    dirv = pv / dist                                                                       # normalize_f3
-    u1 = torch.stack([dirv[1], -dirv[0], zero]); u1 = u1 / torch.sqrt((u1 * u1).sum())
-    u2 = torch.stack([dirv[1] * u1[2] - dirv[2] * u1[1], dirv[2] * u1[0] - dirv[0] * u1[2], dirv[0] * u1[1] - dirv[1] * u1[0]])
-    Pm = _mat3_cols(u1[0], u1[1], u1[2], u2[0], u2[1], u2[2], zero, zero, zero)
-    Wm = _mat3_cols(vm[0], vm[4], vm[8], vm[1], vm[5], vm[9], vm[2], vm[6], vm[10])
-    Tm = Wm @ Pm
-    cov = Tm.T @ Sigma.T @ Tm                                                              # :162
-    a = (cov[0, 0] + 0.01) / (dist * dist); b = cov[1, 0] / (dist * dist); c = (cov[1, 1] + 0.01) / (dist * dist)   # cov[0][1] = column 0, row 1
-    abc = torch.stack([a, b, c])
-    return abc, dist, u1, u2, pv / dist, one
 
 
 def test_whole_chain_gradients_are_autograd_of_k1_and_the_forward_loop(run):

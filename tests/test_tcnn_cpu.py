@@ -29,7 +29,7 @@ def test_header_parses_and_library_exports_exactly_the_declared_functions(hip_li
     assert set(typed) == DECLARED
     exports = lambda so: set(re.findall(r" T (lidargs_\w+)", subprocess.run(["nm", "-D", "--defined-only", so], capture_output=True, text=True).stdout))
     assert exports(build_hip.TCNN_OUT) == DECLARED and exports(hip_lib_built).isdisjoint(DECLARED)
-    assert len(lidargs_abi.signatures()) == 84                                 # nothing was added under include/
+    assert len(lidargs_abi.signatures()) == 86                                 # nothing was added under include/
     i, z, p = ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p                   # written from the header by eye
     assert typed["lidargs_tcnn_frequency_forward"] == (i, (i, i, i, p, p, p))
     assert typed["lidargs_tcnn_frequency_backward"] == (i, (i, i, i, p, p, p, p))
