@@ -6,6 +6,7 @@ Output: lidar-gs_amd/diff_lidargs_rasterization/liblidargs_hip.so  (git-ignored,
         lidar-gs_amd/lidargs_optim/liblidargs_optim.so             (the optimizer step: csrc/adam.hip alone, include_optim/)
         lidar-gs_amd/liblidargs_decode_options.so                  (feature bank + appearance in front of the decode: csrc/decode_options.hip alone, include_decode/)
         lidar-gs_amd/tinycudann/liblidargs_tcnn.so                 (the tinycudann stand-in: csrc/raydrop_mlp.hip alone, include_tcnn/)
+        lidar-gs_amd/liblidargs_rangeview.so                       (point cloud <-> range image: csrc/range_view.hip alone, include_rangeview/)
 
 Per-file flags: the per-Gaussian kernels (preprocess.hip) are HBM-bound, so they are built with
 -ffp-contract=off: every expression rounds as written, which keeps the unit vectors s = p/|p| that
@@ -57,7 +58,13 @@ TCNN_INCLUDE = os.path.join(HERE, "..", "include_tcnn")
 TCNN_SOURCES = {
     "raydrop_mlp.hip": [],
 }
-_OWN_TARGET = {**OPTIM_SOURCES, **DECODE_SOURCES, **TCNN_SOURCES}          # sources that are not part of liblidargs_hip.so
+# The range-view conversion (point cloud -> range image and back): a target and a header directory of its own, like the three above.
+RANGEVIEW_OUT = os.path.join(HERE, "liblidargs_rangeview.so")
+RANGEVIEW_INCLUDE = os.path.join(HERE, "..", "include_rangeview")
+RANGEVIEW_SOURCES = {
+    "range_view.hip": ["-ffp-contract=off"],       # the row and the column of a point are compared pixel for pixel with the reference's float32 evaluation
+}
+_OWN_TARGET = {**OPTIM_SOURCES, **DECODE_SOURCES, **TCNN_SOURCES, **RANGEVIEW_SOURCES}          # sources that are not part of liblidargs_hip.so
 
 
 def build_id():
@@ -69,7 +76,8 @@ def build_id():
         os.path.join(HERE, "..", "include", f) for f in os.listdir(os.path.join(HERE, "..", "include"))) + sorted(
         os.path.join(OPTIM_INCLUDE, f) for f in os.listdir(OPTIM_INCLUDE)) + sorted(
         os.path.join(DECODE_INCLUDE, f) for f in os.listdir(DECODE_INCLUDE)) + sorted(
-        os.path.join(TCNN_INCLUDE, f) for f in os.listdir(TCNN_INCLUDE)) + [os.path.abspath(__file__)]
+        os.path.join(TCNN_INCLUDE, f) for f in os.listdir(TCNN_INCLUDE)) + sorted(
+        os.path.join(RANGEVIEW_INCLUDE, f) for f in os.listdir(RANGEVIEW_INCLUDE)) + [os.path.abspath(__file__)]
     for f in files:
         h.update(os.path.basename(f).encode()); h.update(open(f, "rb").read())
     return h.hexdigest()[:12]
@@ -115,12 +123,18 @@ def tcnn_needs_build():
                   + [os.path.join(TCNN_INCLUDE, f) for f in os.listdir(TCNN_INCLUDE)] + [__file__])
 
 
+def rangeview_needs_build():
+    return _stale(RANGEVIEW_OUT, [os.path.join(CSRC, f) for f in RANGEVIEW_SOURCES]
+                  + [os.path.join(RANGEVIEW_INCLUDE, f) for f in os.listdir(RANGEVIEW_INCLUDE)] + [__file__])
+
+
 def build(force=False, verbose=False):
     """Up-to-date check and build under an exclusive file lock: the ranks of `bench.py --gpus N` (one process per GPU) all call this
     at start-up, and only the first may compile -- the others wait and then find the library up to date.  The link goes to a
     temporary name and is moved into place, so a process that loaded the library earlier never sees a half-written file.
-    Builds the four libraries, each when its own dependencies are newer; returns the main library's path."""
-    if not force and not needs_build() and not optim_needs_build() and not decode_needs_build() and not tcnn_needs_build():
+    Builds the five libraries, each when its own dependencies are newer; returns the main library's path."""
+    if not force and not needs_build() and not optim_needs_build() and not decode_needs_build() and not tcnn_needs_build() \
+            and not rangeview_needs_build():
         return OUT
     import fcntl
     os.makedirs(OBJ, exist_ok=True)
@@ -135,6 +149,8 @@ def build(force=False, verbose=False):
                 _build_locked(DECODE_SOURCES, DECODE_OUT, verbose)
             if force or tcnn_needs_build():
                 _build_locked(TCNN_SOURCES, TCNN_OUT, verbose)
+            if force or rangeview_needs_build():
+                _build_locked(RANGEVIEW_SOURCES, RANGEVIEW_OUT, verbose)
             return OUT
         finally:
             fcntl.flock(lock, fcntl.LOCK_UN)
