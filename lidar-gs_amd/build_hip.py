@@ -1,12 +1,12 @@
-"""Compile the gfx950 rasterizer into an in-tree shared library (no torch involved).
+"""Compile the gfx950 libraries into in-tree shared libraries (no torch involved).
 
     python lidar-gs_amd/build_hip.py [--force]
 
-Output: lidar-gs_amd/diff_lidargs_rasterization/liblidargs_hip.so  (git-ignored, travels with gpurun)
-        lidar-gs_amd/lidargs_optim/liblidargs_optim.so             (the optimizer step: csrc/adam.hip alone, include_optim/)
-        lidar-gs_amd/liblidargs_decode_options.so                  (feature bank + appearance in front of the decode: csrc/decode_options.hip alone, include_decode/)
-        lidar-gs_amd/tinycudann/liblidargs_tcnn.so                 (the tinycudann stand-in: csrc/raydrop_mlp.hip alone, include_tcnn/)
-        lidar-gs_amd/liblidargs_rangeview.so                       (point cloud <-> range image: csrc/range_view.hip alone, include_rangeview/)
+TARGETS below is the one description of what is built: per library its name, its output (git-ignored), its sources with their per-file
+flags, and the directory of the public headers that declare exactly what it exports.  `hip` is the main library (the rasterizers and
+everything include/ declares); every other entry is a single source with a header directory of its own, so that liblidargs_hip.so
+exports exactly what include/ declares.  Staleness (stale, deps), the build loop (build) and the content hash (build_id, build_id_files)
+are all derived from the table: a further library is one more entry.
 
 Per-file flags: the per-Gaussian kernels (preprocess.hip) are HBM-bound, so they are built with
 -ffp-contract=off: every expression rounds as written, which keeps the unit vectors s = p/|p| that
@@ -14,12 +14,14 @@ feed the cancellation-prone blend difference (s - q) bit-identical to an un-fuse
 The blend kernels (render.hip) keep FMA contraction.  The sharded path's file (shard.hip) holds kernels of both kinds and says
 which is which by `#pragma clang fp contract` in front of each part: a flag would speak for the whole file.
 """
+import collections
 import os
 import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 OUT = os.path.join(HERE, "diff_lidargs_rasterization", "liblidargs_hip.so")
@@ -39,46 +41,56 @@ SOURCES = {
     "knn.hip": ["-ffp-contract=off"],              # the 3-NN squared distances and the voxel quotients are compared bit for bit; the box bound prunes exactly only without contraction
     "metrics.hip": ["-ffp-contract=off"],          # the SSIM map and the float32 means round as scikit-image / torch write them
 }
-# The optimizer's library: a target of its own, so that liblidargs_hip.so exports exactly what include/ declares.
-OPTIM_OUT = os.path.join(HERE, "lidargs_optim", "liblidargs_optim.so")
-OPTIM_INCLUDE = os.path.join(HERE, "..", "include_optim")
-OPTIM_SOURCES = {
-    "adam.hip": ["-ffp-contract=off"],             # torch's op-by-op roundings; the steps its device kernels fuse are written as fmaf
-}
-# The decode's two model options (use_feat_bank, appearance_dim > 0): new entry points beside the decode's, a target and a header
-# directory of their own like the optimizer's.
-DECODE_OUT = os.path.join(HERE, "liblidargs_decode_options.so")
-DECODE_INCLUDE = os.path.join(HERE, "..", "include_decode")
-DECODE_SOURCES = {
-    "decode_options.hip": [],
-}
-# The tinycudann stand-in (frequency encoding, fused MLP): a target and a header directory of its own, like the two above.
-TCNN_OUT = os.path.join(HERE, "tinycudann", "liblidargs_tcnn.so")
-TCNN_INCLUDE = os.path.join(HERE, "..", "include_tcnn")
-TCNN_SOURCES = {
-    "raydrop_mlp.hip": [],
-}
-# The range-view conversion (point cloud -> range image and back): a target and a header directory of its own, like the three above.
-RANGEVIEW_OUT = os.path.join(HERE, "liblidargs_rangeview.so")
-RANGEVIEW_INCLUDE = os.path.join(HERE, "..", "include_rangeview")
-RANGEVIEW_SOURCES = {
-    "range_view.hip": ["-ffp-contract=off"],       # the row and the column of a point are compared pixel for pixel with the reference's float32 evaluation
-}
-_OWN_TARGET = {**OPTIM_SOURCES, **DECODE_SOURCES, **TCNN_SOURCES, **RANGEVIEW_SOURCES}          # sources that are not part of liblidargs_hip.so
+Target = collections.namedtuple("Target", "name out sources include")      # sources: {file of csrc/: [per-file flags]}; include: its header directory
+TARGETS = {t.name: t for t in (
+    Target("hip", OUT, SOURCES, os.path.join(ROOT, "include")),
+    Target("optim", os.path.join(HERE, "lidargs_optim", "liblidargs_optim.so"), {
+        "adam.hip": ["-ffp-contract=off"],         # torch's op-by-op roundings; the steps its device kernels fuse are written as fmaf
+    }, os.path.join(ROOT, "include_optim")),
+    # the decode's two model options (use_feat_bank, appearance_dim > 0): entry points beside the decode's
+    Target("decode_options", os.path.join(HERE, "liblidargs_decode_options.so"), {
+        "decode_options.hip": [],
+    }, os.path.join(ROOT, "include_decode")),
+    # the tinycudann stand-in (frequency encoding, fused MLP)
+    Target("tcnn", os.path.join(HERE, "tinycudann", "liblidargs_tcnn.so"), {
+        "raydrop_mlp.hip": [],
+    }, os.path.join(ROOT, "include_tcnn")),
+    # the range-view conversion (point cloud -> range image and back)
+    Target("rangeview", os.path.join(HERE, "liblidargs_rangeview.so"), {
+        "range_view.hip": ["-ffp-contract=off"],   # the row and the column of a point are compared pixel for pixel with the reference's float32 evaluation
+    }, os.path.join(ROOT, "include_rangeview")),
+)}
+
+
+def _listed(d, keep=lambda f: True):
+    return sorted(os.path.join(d, f) for f in os.listdir(d) if keep(f))
+
+
+def deps(target):
+    """What a library is rebuilt for: its own sources, every shared file of csrc/ that is not a .hip (headers and .inc, whichever
+    target includes them: more than needed, never less), every header of its include directory and this file."""
+    return ([os.path.join(CSRC, f) for f in target.sources] + _listed(CSRC, lambda f: not f.endswith(".hip"))
+            + _listed(target.include) + [os.path.abspath(__file__)])
+
+
+def stale(target):
+    if not os.path.exists(target.out):
+        return True
+    t = os.path.getmtime(target.out)
+    return any(os.path.getmtime(d) > t for d in deps(target))
+
+
+def build_id_files():
+    """Everything the libraries are built from: csrc/, every target's public headers, this file."""
+    return _listed(CSRC) + [f for t in TARGETS.values() for f in _listed(t.include)] + [os.path.abspath(__file__)]
 
 
 def build_id():
-    """A content hash of everything the libraries are built from (csrc/, the public headers of both, this file): the same on every box that holds the
-    same sources -- what the profile tools stamp their summaries with and bench.py compares against (the GPU boxes have no .git)."""
+    """A content hash of build_id_files() (name, then contents): the same on every box that holds the same sources -- what the
+    profile tools stamp their summaries with and bench.py compares against (the GPU boxes have no .git)."""
     import hashlib
     h = hashlib.sha1()
-    files = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC)) + sorted(
-        os.path.join(HERE, "..", "include", f) for f in os.listdir(os.path.join(HERE, "..", "include"))) + sorted(
-        os.path.join(OPTIM_INCLUDE, f) for f in os.listdir(OPTIM_INCLUDE)) + sorted(
-        os.path.join(DECODE_INCLUDE, f) for f in os.listdir(DECODE_INCLUDE)) + sorted(
-        os.path.join(TCNN_INCLUDE, f) for f in os.listdir(TCNN_INCLUDE)) + sorted(
-        os.path.join(RANGEVIEW_INCLUDE, f) for f in os.listdir(RANGEVIEW_INCLUDE)) + [os.path.abspath(__file__)]
-    for f in files:
+    for f in build_id_files():
         h.update(os.path.basename(f).encode()); h.update(open(f, "rb").read())
     return h.hexdigest()[:12]
 
@@ -96,61 +108,21 @@ def box_id():
     return None
 
 
-def _stale(out, deps):
-    if not os.path.exists(out):
-        return True
-    t = os.path.getmtime(out)
-    return any(os.path.getmtime(d) > t for d in deps)
-
-
-def needs_build():
-    return _stale(OUT, [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f not in _OWN_TARGET]
-                  + [os.path.join(HERE, "..", "include", "lidargs_rasterizer.h"), __file__])
-
-
-def optim_needs_build():
-    return _stale(OPTIM_OUT, [os.path.join(CSRC, f) for f in OPTIM_SOURCES]
-                  + [os.path.join(OPTIM_INCLUDE, f) for f in os.listdir(OPTIM_INCLUDE)] + [__file__])
-
-
-def decode_needs_build():
-    return _stale(DECODE_OUT, [os.path.join(CSRC, f) for f in DECODE_SOURCES]
-                  + [os.path.join(DECODE_INCLUDE, f) for f in os.listdir(DECODE_INCLUDE)] + [__file__])
-
-
-def tcnn_needs_build():
-    return _stale(TCNN_OUT, [os.path.join(CSRC, f) for f in TCNN_SOURCES]
-                  + [os.path.join(TCNN_INCLUDE, f) for f in os.listdir(TCNN_INCLUDE)] + [__file__])
-
-
-def rangeview_needs_build():
-    return _stale(RANGEVIEW_OUT, [os.path.join(CSRC, f) for f in RANGEVIEW_SOURCES]
-                  + [os.path.join(RANGEVIEW_INCLUDE, f) for f in os.listdir(RANGEVIEW_INCLUDE)] + [__file__])
-
-
 def build(force=False, verbose=False):
     """Up-to-date check and build under an exclusive file lock: the ranks of `bench.py --gpus N` (one process per GPU) all call this
     at start-up, and only the first may compile -- the others wait and then find the library up to date.  The link goes to a
     temporary name and is moved into place, so a process that loaded the library earlier never sees a half-written file.
-    Builds the five libraries, each when its own dependencies are newer; returns the main library's path."""
-    if not force and not needs_build() and not optim_needs_build() and not decode_needs_build() and not tcnn_needs_build() \
-            and not rangeview_needs_build():
+    Builds every library of TARGETS that is stale; returns the main library's path."""
+    if not force and not any(stale(t) for t in TARGETS.values()):
         return OUT
     import fcntl
     os.makedirs(OBJ, exist_ok=True)
     with open(os.path.join(OBJ, ".lock"), "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
         try:
-            if force or needs_build():
-                _build_locked(SOURCES, OUT, verbose)
-            if force or optim_needs_build():
-                _build_locked(OPTIM_SOURCES, OPTIM_OUT, verbose)
-            if force or decode_needs_build():
-                _build_locked(DECODE_SOURCES, DECODE_OUT, verbose)
-            if force or tcnn_needs_build():
-                _build_locked(TCNN_SOURCES, TCNN_OUT, verbose)
-            if force or rangeview_needs_build():
-                _build_locked(RANGEVIEW_SOURCES, RANGEVIEW_OUT, verbose)
+            for t in TARGETS.values():
+                if force or stale(t):
+                    _build_locked(t.sources, t.out, verbose)
             return OUT
         finally:
             fcntl.flock(lock, fcntl.LOCK_UN)

@@ -12,8 +12,8 @@
 // as fmaf.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
 #include "../../include_optim/lidargs_optim.h"
+#include "lidargs_status.h"
 
 namespace {
 
@@ -94,13 +94,6 @@ __global__ __launch_bounds__(ADAM_THREADS) void k_adam(const AdamArgs a) {
     }
 }
 
-thread_local char g_err[256] = "";
-
-int fail(int code, const char* msg, const char* detail = "") {
-    snprintf(g_err, sizeof g_err, "adam_step: %s%s", msg, detail);
-    return code;
-}
-
 }  // namespace
 
 extern "C" {
@@ -110,18 +103,19 @@ int lidargs_optim_abi_version(void) { return LIDARGS_OPTIM_ABI_VERSION; }
 const char* lidargs_optim_last_error(void) { return g_err; }
 
 int lidargs_adam_step(int n_tensors, const lidargs_adam_tensor* table, double beta1, double beta2, double eps, void* stream) {
-    if (n_tensors < 0 || n_tensors > LIDARGS_ADAM_MAX_TENSORS) return fail(-1, "n_tensors out of range");
-    if (n_tensors > 0 && !table) return fail(-1, "NULL table");
+    const char* what = "adam_step";
+    if (n_tensors < 0 || n_tensors > LIDARGS_ADAM_MAX_TENSORS) return fail(-1, what, "n_tensors out of range");
+    if (n_tensors > 0 && !table) return fail(-1, what, "NULL table");
     AdamArgs a;
     uint64_t chunks = 0;
     a.aligned = 0;
     for (int i = 0; i < LIDARGS_ADAM_MAX_TENSORS; i++) {
         if (i >= n_tensors) { a.t[i] = lidargs_adam_tensor{nullptr, nullptr, nullptr, nullptr, 0, 0.f, 0.f}; a.chunk_end[i] = 0xFFFFFFFFu; continue; }
         const lidargs_adam_tensor& t = table[i];
-        if (t.n < 0) return fail(-1, "negative size");
-        if (t.n > 0 && (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq)) return fail(-1, "NULL pointer with n > 0");
+        if (t.n < 0) return fail(-1, what, "negative size");
+        if (t.n > 0 && (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq)) return fail(-1, what, "NULL pointer with n > 0");
         chunks += ((uint64_t)t.n + ADAM_CHUNK - 1) / ADAM_CHUNK;
-        if (chunks > 0x7FFFFFFFull) return fail(-1, "too many elements for one call");
+        if (chunks > 0x7FFFFFFFull) return fail(-1, what, "too many elements for one call");
         a.t[i] = t;
         a.chunk_end[i] = (uint32_t)chunks;
         const uintptr_t bits = (uintptr_t)t.param | (uintptr_t)t.grad | (uintptr_t)t.exp_avg | (uintptr_t)t.exp_avg_sq;
@@ -134,9 +128,7 @@ int lidargs_adam_step(int n_tensors, const lidargs_adam_tensor* table, double be
     a.w2 = (float)(1.0 - beta2);
     a.eps = (float)eps;
     hipLaunchKernelGGL(k_adam, dim3((unsigned)chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(-4, "launch: ", hipGetErrorString(e));
-    return 0;
+    return launched(-4, what);
 }
 
 }  // extern "C"

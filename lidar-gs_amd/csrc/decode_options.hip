@@ -20,8 +20,8 @@
 //   k_appearance_fold / k_appearance_backward   one small launch each: a thread per element.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
 #include "../../include_decode/lidargs_decode_options.h"
+#include "lidargs_status.h"
 
 namespace {
 
@@ -294,19 +294,6 @@ __global__ void __launch_bounds__(256) k_appearance_backward(int din, int A, App
     }
 }
 
-thread_local char g_err[256] = "";
-
-int fail(int code, const char* msg, const char* detail = "") {
-    snprintf(g_err, sizeof g_err, "%s%s", msg, detail);
-    return code;
-}
-
-int launched(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { snprintf(g_err, sizeof g_err, "%s: launch: %s", what, hipGetErrorString(e)); return LIDARGS_NG_OPTIONS_ERR_HIP; }
-    return 0;
-}
-
 int bank_backward_rows(int N) {
     const int rounds = (N + BK_ANCHORS - 1) / BK_ANCHORS;
     return rounds < 1 ? 1 : (rounds > BK_BWD_MAX_BLOCKS ? BK_BWD_MAX_BLOCKS : rounds);
@@ -321,15 +308,15 @@ const char* lidargs_ng_options_last_error(void) { return g_err; }
 
 int lidargs_ng_bank_forward(int N, const uint8_t* visible_mask, const float* anchor_feat, const float* anchor, const float* cam_center,
                             const float* W1, const float* b1, const float* W2, const float* b2, float* feat_out, void* stream) {
-    if (N < 0) return fail(LIDARGS_NG_OPTIONS_ERR_INVALID_ARGUMENT, "ng_bank_forward: bad sizes");
-    if (!cam_center || !W1 || !b1 || !W2 || !b2) return fail(LIDARGS_NG_OPTIONS_ERR_INVALID_ARGUMENT, "ng_bank_forward: NULL pointer");
+    if (N < 0) return fail(LIDARGS_NG_OPTIONS_ERR_INVALID_ARGUMENT, "ng_bank_forward", "bad sizes");
+    if (!cam_center || !W1 || !b1 || !W2 || !b2) return fail(LIDARGS_NG_OPTIONS_ERR_INVALID_ARGUMENT, "ng_bank_forward", "NULL pointer");
     if (N == 0) return 0;
-    if (!anchor_feat || !anchor || !feat_out) return fail(LIDARGS_NG_OPTIONS_ERR_INVALID_ARGUMENT, "ng_bank_forward: NULL pointer");
+    if (!anchor_feat || !anchor || !feat_out) return fail(LIDARGS_NG_OPTIONS_ERR_INVALID_ARGUMENT, "ng_bank_forward", "NULL pointer");
     const int rounds = (N + BK_ANCHORS - 1) / BK_ANCHORS;
     const float3 cam = make_float3(cam_center[0], cam_center[1], cam_center[2]);
     hipLaunchKernelGGL(k_bank_forward, dim3(rounds < BK_FWD_MAX_BLOCKS ? rounds : BK_FWD_MAX_BLOCKS), dim3(BK_THREADS), 0, (hipStream_t)stream,
                        N, visible_mask, anchor_feat, anchor, cam, W1, b1, W2, b2, feat_out);
-    return launched("ng_bank_forward");
+    return launched(LIDARGS_NG_OPTIONS_ERR_HIP, "ng_bank_forward");
 }
 
 size_t lidargs_ng_bank_backward_partial_floats(int N) { return (size_t)bank_backward_rows(N < 0 ? 0 : N) * BK_PARAMS; }
@@ -338,47 +325,47 @@ int lidargs_ng_bank_backward(int N, const uint8_t* visible_mask, const float* an
                              const float* W1, const float* b1, const float* W2, const float* b2, const float* dL_dfeat_out,
                              float* dL_danchor_feat, float* dL_danchor, float* dL_dparams, float* partials, size_t partial_floats,
                              void* stream) {
-    if (N < 0) return fail(LIDARGS_NG_OPTIONS_ERR_INVALID_ARGUMENT, "ng_bank_backward: bad sizes");
-    if (!cam_center || !W1 || !b1 || !W2 || !b2) return fail(LIDARGS_NG_OPTIONS_ERR_INVALID_ARGUMENT, "ng_bank_backward: NULL pointer");
+    if (N < 0) return fail(LIDARGS_NG_OPTIONS_ERR_INVALID_ARGUMENT, "ng_bank_backward", "bad sizes");
+    if (!cam_center || !W1 || !b1 || !W2 || !b2) return fail(LIDARGS_NG_OPTIONS_ERR_INVALID_ARGUMENT, "ng_bank_backward", "NULL pointer");
     if (N == 0) return 0;
     if (!anchor_feat || !anchor || !dL_dfeat_out || !dL_danchor_feat || !dL_danchor || !dL_dparams || !partials)
-        return fail(LIDARGS_NG_OPTIONS_ERR_INVALID_ARGUMENT, "ng_bank_backward: NULL pointer");
-    if (partial_floats < lidargs_ng_bank_backward_partial_floats(N)) return fail(LIDARGS_NG_OPTIONS_ERR_INVALID_ARGUMENT, "ng_bank_backward: partials too small");
+        return fail(LIDARGS_NG_OPTIONS_ERR_INVALID_ARGUMENT, "ng_bank_backward", "NULL pointer");
+    if (partial_floats < lidargs_ng_bank_backward_partial_floats(N)) return fail(LIDARGS_NG_OPTIONS_ERR_INVALID_ARGUMENT, "ng_bank_backward", "partials too small");
     const int rows = bank_backward_rows(N);
     const float3 cam = make_float3(cam_center[0], cam_center[1], cam_center[2]);
     hipLaunchKernelGGL(k_bank_backward, dim3(rows), dim3(BK_THREADS), 0, (hipStream_t)stream, N, visible_mask, anchor_feat, anchor, cam,
                        W1, b1, W2, b2, dL_dfeat_out, dL_danchor_feat, dL_danchor, partials);
     hipLaunchKernelGGL(k_bank_fold, dim3((BK_PARAMS + 3) / 4), dim3(256), 0, (hipStream_t)stream, rows, partials, dL_dparams);
-    return launched("ng_bank_backward");
+    return launched(LIDARGS_NG_OPTIONS_ERR_HIP, "ng_bank_backward");
 }
 
 int lidargs_ng_appearance_fold(int din, int A, const float* W1_color, const float* b1_color, const float* e_color, const float* W1_raydrop,
                                const float* b1_raydrop, const float* e_raydrop, float* W1_out, float* b1_out, void* stream) {
-    if ((din != 35 && din != 36) || A < 1 || A > (1 << 20)) return fail(LIDARGS_NG_OPTIONS_ERR_INVALID_ARGUMENT, "ng_appearance_fold: bad sizes");
+    if ((din != 35 && din != 36) || A < 1 || A > (1 << 20)) return fail(LIDARGS_NG_OPTIONS_ERR_INVALID_ARGUMENT, "ng_appearance_fold", "bad sizes");
     if (!W1_color || !b1_color || !e_color || !W1_raydrop || !b1_raydrop || !e_raydrop || !W1_out || !b1_out)
-        return fail(LIDARGS_NG_OPTIONS_ERR_INVALID_ARGUMENT, "ng_appearance_fold: NULL pointer");
+        return fail(LIDARGS_NG_OPTIONS_ERR_INVALID_ARGUMENT, "ng_appearance_fold", "NULL pointer");
     AppHeads hd = {};
     hd.W1[0] = W1_color; hd.W1[1] = W1_raydrop; hd.b1[0] = b1_color; hd.b1[1] = b1_raydrop; hd.e[0] = e_color; hd.e[1] = e_raydrop;
     const int threads = 2 * 32 * din + 64;
     hipLaunchKernelGGL(k_appearance_fold, dim3((threads + 255) / 256), dim3(256), 0, (hipStream_t)stream, din, A, hd, W1_out, b1_out);
-    return launched("ng_appearance_fold");
+    return launched(LIDARGS_NG_OPTIONS_ERR_HIP, "ng_appearance_fold");
 }
 
 int lidargs_ng_appearance_backward(int din, int A, const float* W1_color, const float* e_color, const float* W1_raydrop,
                                    const float* e_raydrop, const float* dW1_main_color, const float* db1_color,
                                    const float* dW1_main_raydrop, const float* db1_raydrop, float* dW1_full, float* de_color,
                                    float* de_raydrop, void* stream) {
-    if ((din != 35 && din != 36) || A < 1 || A > (1 << 20)) return fail(LIDARGS_NG_OPTIONS_ERR_INVALID_ARGUMENT, "ng_appearance_backward: bad sizes");
+    if ((din != 35 && din != 36) || A < 1 || A > (1 << 20)) return fail(LIDARGS_NG_OPTIONS_ERR_INVALID_ARGUMENT, "ng_appearance_backward", "bad sizes");
     if (!W1_color || !e_color || !W1_raydrop || !e_raydrop || !dW1_main_color || !db1_color || !dW1_main_raydrop || !db1_raydrop ||
         !dW1_full || !de_color || !de_raydrop)
-        return fail(LIDARGS_NG_OPTIONS_ERR_INVALID_ARGUMENT, "ng_appearance_backward: NULL pointer");
+        return fail(LIDARGS_NG_OPTIONS_ERR_INVALID_ARGUMENT, "ng_appearance_backward", "NULL pointer");
     AppHeads hd = {};
     hd.W1[0] = W1_color; hd.W1[1] = W1_raydrop; hd.e[0] = e_color; hd.e[1] = e_raydrop;
     hd.dW1[0] = dW1_main_color; hd.dW1[1] = dW1_main_raydrop; hd.db1[0] = db1_color; hd.db1[1] = db1_raydrop;
     hd.de[0] = de_color; hd.de[1] = de_raydrop;
     const long long threads = 2LL * 32 * (din + A) + 2LL * A;
     hipLaunchKernelGGL(k_appearance_backward, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, din, A, hd, dW1_full);
-    return launched("ng_appearance_backward");
+    return launched(LIDARGS_NG_OPTIONS_ERR_HIP, "ng_appearance_backward");
 }
 
 }  // extern "C"

@@ -17,8 +17,8 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
 #include "../../include_rangeview/lidargs_range_view.h"
+#include "lidargs_status.h"
 
 namespace {
 
@@ -188,13 +188,6 @@ __global__ void __launch_bounds__(RV_THREADS) k_rv_points(int H, int W, const fl
     }
 }
 
-thread_local char g_err[256] = "";
-
-int fail(int code, const char* what, const char* msg, const char* detail = "") {
-    snprintf(g_err, sizeof g_err, "%s: %s%s", what, msg, detail);
-    return code;
-}
-
 // 0, or the message of what is wrong with the image size and the row rule
 const char* check_rows(int H, int W, const float* beams, float fov) {
     if (H <= 0 || W <= 0 || (long long)H * W > RV_MAX_PIXELS) return "bad image size";
@@ -249,9 +242,7 @@ int lidargs_rv_project(int N, const float* points, int H, int W, const float* be
                            make_rows(H, beams, fov_up, fov), (float)(2 * 3.141592653589793 / W), max_depth, make_xform(world_to_sensor), flags, keys);
     }
     hipLaunchKernelGGL(k_rv_resolve, dim3(blocks_for(n)), dim3(RV_THREADS), 0, stream, n, keys, points, out_pano, out_intensity);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(-4, what, "launch: ", hipGetErrorString(e));
-    return 0;
+    return launched(-4, what);
 }
 
 int lidargs_rv_unproject(int H, int W, const float* pano, const float* intensity, const float* beams, float fov_up, float fov,
@@ -268,9 +259,7 @@ int lidargs_rv_unproject(int H, int W, const float* pano, const float* intensity
     hipLaunchKernelGGL(k_rv_scan, dim3(1), dim3(RV_THREADS), 0, stream, tiles, tile_count, out_count);
     hipLaunchKernelGGL(k_rv_points, dim3(tiles), dim3(RV_THREADS), 0, stream, H, W, pano, intensity, make_rows(H, beams, fov_up, fov),
                        make_xform(sensor_to_world), tile_count, reinterpret_cast<float4*>(out_points));
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(-4, what, "launch: ", hipGetErrorString(e));
-    return 0;
+    return launched(-4, what);
 }
 
 int lidargs_rv_ray_dirs(int H, int W, const float* beams, float fov_up, float fov, float* out_dirs, void* stream_) {
@@ -278,9 +267,7 @@ int lidargs_rv_ray_dirs(int H, int W, const float* beams, float fov_up, float fo
     if (const char* m = check_rows(H, W, beams, fov)) return fail(-1, what, m);
     if (!out_dirs) return fail(-1, what, "NULL pointer");
     hipLaunchKernelGGL(k_rv_ray_dirs, dim3(blocks_for((long long)H * W)), dim3(RV_THREADS), 0, (hipStream_t)stream_, H, W, make_rows(H, beams, fov_up, fov), out_dirs);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(-4, what, "launch: ", hipGetErrorString(e));
-    return 0;
+    return launched(-4, what);
 }
 
 }  // extern "C"

@@ -17,8 +17,8 @@
 // Rows behind n are zero rows (x = 0 gives h = 0 without biases, dout = 0 gives delta = 0): masked in the loads and stores only.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
 #include "../../include_tcnn/lidargs_tcnn.h"
+#include "lidargs_status.h"
 
 namespace {
 
@@ -356,13 +356,6 @@ __global__ __launch_bounds__(FREQ_THREADS) void k_freq_bwd(size_t elems, int n_f
     dx[e] = s;
 }
 
-thread_local char g_err[256] = "";
-
-int fail(int code, const char* what, const char* msg, const char* detail = "") {
-    snprintf(g_err, sizeof g_err, "%s: %s%s", what, msg, detail);
-    return code;
-}
-
 bool sizes_ok(int n_in, int layers, int n_out) {
     return n_in >= 1 && n_in <= WIDTH && layers >= 1 && layers <= LIDARGS_TCNN_MAX_HIDDEN_LAYERS && n_out >= 1 && n_out <= LIDARGS_TCNN_MAX_OUT;
 }
@@ -416,9 +409,7 @@ int lidargs_tcnn_frequency_forward(int n, int dims, int n_freq, const float* x, 
     const size_t blocks = (total + FREQ_THREADS - 1) / FREQ_THREADS;
     if (blocks > 0x7FFFFFFFull) return fail(-1, what, "too many elements for one call");
     hipLaunchKernelGGL(k_freq_fwd, dim3((unsigned)blocks), dim3(FREQ_THREADS), 0, (hipStream_t)stream, total, n_freq, x, out);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(-4, what, "launch: ", hipGetErrorString(e));
-    return 0;
+    return launched(-4, what);
 }
 
 int lidargs_tcnn_frequency_backward(int n, int dims, int n_freq, const float* x, const float* dout, float* dx, void* stream) {
@@ -431,9 +422,7 @@ int lidargs_tcnn_frequency_backward(int n, int dims, int n_freq, const float* x,
     const size_t blocks = (elems + FREQ_THREADS - 1) / FREQ_THREADS;
     if (blocks > 0x7FFFFFFFull) return fail(-1, what, "too many elements for one call");
     hipLaunchKernelGGL(k_freq_bwd, dim3((unsigned)blocks), dim3(FREQ_THREADS), 0, (hipStream_t)stream, elems, n_freq, x, dout, dx);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(-4, what, "launch: ", hipGetErrorString(e));
-    return 0;
+    return launched(-4, what);
 }
 
 int lidargs_tcnn_mlp_forward(int n, int n_in, int n_hidden_layers, int n_out, int out_act, const float* params, const float* x,
@@ -445,9 +434,7 @@ int lidargs_tcnn_mlp_forward(int n, int n_in, int n_hidden_layers, int n_out, in
     const Mlp m = {n, n_in, n_hidden_layers, n_out, out_act, ((uintptr_t)params & 15) == 0, params, x};
     const unsigned blocks = (unsigned)(((long long)n + 16 * FWD_RT - 1) / (16 * FWD_RT));
     hipLaunchKernelGGL(k_mlp_fwd, dim3(blocks), dim3(THREADS), 0, (hipStream_t)stream, m, out);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(-4, what, "launch: ", hipGetErrorString(e));
-    return 0;
+    return launched(-4, what);
 }
 
 int lidargs_tcnn_mlp_backward(int n, int n_in, int n_hidden_layers, int n_out, int out_act, const float* params, const float* x,
@@ -459,20 +446,16 @@ int lidargs_tcnn_mlp_backward(int n, int n_in, int n_hidden_layers, int n_out, i
     const size_t n_params = param_count(n_in, n_hidden_layers, n_out);
     const int blocks = bwd_blocks(n);
     if (blocks > 0 && (!partials || partial_floats < (size_t)blocks * n_params)) return fail(-1, what, "partials too small");
-    hipError_t e;
     if (blocks > 0) {
         const Mlp m = {n, n_in, n_hidden_layers, n_out, out_act, ((uintptr_t)params & 15) == 0, params, x};
         const size_t lds = ((size_t)(n_hidden_layers + 1) * 16 * BWD_RT * LS + 16 * BWD_RT * DYS) * sizeof(float);
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp_bwd), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp_bwd), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return fail(-4, what, "LDS size: ", hipGetErrorString(e));
         hipLaunchKernelGGL(k_mlp_bwd, dim3((unsigned)blocks), dim3(THREADS), lds, (hipStream_t)stream, m, dout, dx, partials, n_params, bwd_tiles(n));
-        e = hipGetLastError();
-        if (e != hipSuccess) return fail(-4, what, "launch: ", hipGetErrorString(e));
+        if (const int rc = launched(-4, what)) return rc;
     }
     hipLaunchKernelGGL(k_mlp_fold, dim3((unsigned)((n_params + 255) / 256)), dim3(256), 0, (hipStream_t)stream, partials, blocks, n_params, dparams);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail(-4, what, "fold launch: ", hipGetErrorString(e));
-    return 0;
+    return launched(-4, what, "fold launch: ");
 }
 
 }  // extern "C"

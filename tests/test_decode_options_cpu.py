@@ -3,8 +3,6 @@ equals the fixture made by executing the reference (tests/golden/make_decode_opt
 exported and typed; the front-end's refusals that happen before any device call."""
 import ctypes
 import os
-import re
-import subprocess
 import types
 
 import numpy as np
@@ -17,7 +15,6 @@ import lidargs_scenes as sc
 from test_neural_gaussians_cpu import close
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INCLUDE_DECODE = os.path.join(ROOT, "include_decode")
 CASES = ("c", "d", "e", "f")
 NEW = {"lidargs_ng_bank_forward", "lidargs_ng_bank_backward", "lidargs_ng_bank_backward_partial_floats", "lidargs_ng_appearance_fold",
        "lidargs_ng_appearance_backward", "lidargs_ng_options_abi_version", "lidargs_ng_options_last_error"}
@@ -62,17 +59,10 @@ def test_new_entry_points_are_declared_exported_and_typed(hip_lib_built):
     """The options' library (liblidargs_decode_options.so, include_decode/) beside the decode's: exactly the declared functions are
     exported, every one typed by lidargs_abi from the header, none of them in liblidargs_hip.so, and the header is plain C."""
     import build_hip
-    import lidargs_abi
+    import native_lib_checks
     import neural_gaussians as prod
-    assert os.path.exists(build_hip.DECODE_OUT), "build_hip.build() must build the options' library too"
-    assert "decode_options.hip" not in build_hip.SOURCES and "decode_options.hip" in build_hip.DECODE_SOURCES
-    typed = lidargs_abi.signatures(INCLUDE_DECODE)
-    assert set(typed) == NEW
-    exports = lambda so: set(re.findall(r" T (lidargs_\w+)", subprocess.run(["nm", "-D", "--defined-only", so], capture_output=True, text=True).stdout))
-    assert exports(build_hip.DECODE_OUT) == NEW and exports(hip_lib_built).isdisjoint(NEW)
-    for name, (restype, argtypes) in typed.items():
-        fn = getattr(prod._options_lib(), name)
-        assert fn.restype is restype and tuple(fn.argtypes) == argtypes, name
+    typed = native_lib_checks.check_library(build_hip.TARGETS["decode_options"], NEW, prod._options_lib(), hip_lib_built)
+    assert "decode_options.hip" in build_hip.TARGETS["decode_options"].sources
     i, z, p = ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p                  # written from the header by eye
     assert typed["lidargs_ng_bank_forward"] == (i, (i,) + (p,) * 10)
     assert typed["lidargs_ng_bank_backward"] == (i, (i,) + (p,) * 13 + (z, p))
@@ -80,9 +70,6 @@ def test_new_entry_points_are_declared_exported_and_typed(hip_lib_built):
     assert typed["lidargs_ng_appearance_fold"] == (i, (i, i) + (p,) * 9)
     assert typed["lidargs_ng_appearance_backward"] == (i, (i, i) + (p,) * 12)
     assert prod._options_lib().lidargs_ng_options_abi_version() == prod.OPTIONS_ABI_VERSION == 1
-    for h in sorted(os.listdir(INCLUDE_DECODE)):
-        r = subprocess.run(["gcc", "-std=c99", "-fsyntax-only", "-Wall", "-Werror", "-x", "c", os.path.join(INCLUDE_DECODE, h)], capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
 
 
 def test_entry_points_validate_before_any_device_work(hip_lib_built):

@@ -5,7 +5,6 @@ moves between the two classes in both directions, and the optimizer surgery of t
 replace a tensor) leaves param_groups and state consistent.  No device call is made here."""
 import ctypes
 import os
-import re
 import subprocess
 
 import pytest
@@ -17,44 +16,26 @@ import build_hip
 build_hip.build()          # importing lidargs_optim needs its library (a no-op when it is up to date)
 import lidargs_abi  # noqa: E402
 import lidargs_optim  # noqa: E402
+import native_lib_checks  # noqa: E402
 from lidargs_optim import Adam  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INCLUDE_OPTIM = os.path.join(ROOT, "include_optim")
-HEADER = os.path.join(INCLUDE_OPTIM, "lidargs_optim.h")
+DECLARED = {"lidargs_adam_step", "lidargs_adam_max_tensors", "lidargs_optim_last_error", "lidargs_optim_abi_version"}
 K = 6      # offsets per anchor
 PER_ANCHOR = {"anchor": (3,), "offset": (K, 3), "anchor_feat": (32,), "opacity": (1,), "scaling": (6,), "rotation": (4,)}
 
 
-def _optim_lib(hip_lib_built):
-    assert os.path.exists(build_hip.OPTIM_OUT), "build_hip.build() must build the optimizer's library too"
-    return build_hip.OPTIM_OUT
-
-
-def _exports(path):
-    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    return set(re.findall(r" T (lidargs_\w+)", out))
-
-
 def test_second_library_exports_exactly_its_header(hip_lib_built):
-    so = _optim_lib(hip_lib_built)
-    typed = lidargs_abi.signatures(INCLUDE_OPTIM)
-    assert set(typed) == {"lidargs_adam_step", "lidargs_adam_max_tensors", "lidargs_optim_last_error", "lidargs_optim_abi_version"}
-    exported = _exports(so)
-    assert exported - set(typed) == set(), "exported but not declared in include_optim/"
-    assert set(typed) - exported == set(), "declared in include_optim/ but not exported"
-    for name, (restype, argtypes) in typed.items():
-        fn = getattr(lidargs_optim._lib, name)
-        assert fn.restype is restype and tuple(fn.argtypes) == argtypes, name
+    typed = native_lib_checks.check_library(build_hip.TARGETS["optim"], DECLARED, lidargs_optim._lib, hip_lib_built)
+    assert "adam.hip" in build_hip.TARGETS["optim"].sources
     i, d, p = ctypes.c_int, ctypes.c_double, ctypes.c_void_p
     assert typed["lidargs_adam_step"] == (i, (i, p, d, d, d, p))          # read from the header by eye
     assert typed["lidargs_optim_last_error"] == (ctypes.c_char_p, ())
     assert lidargs_optim._lib.lidargs_optim_abi_version() == 1 and lidargs_optim.MAX_TENSORS == 64
 
 
-def test_header_is_plain_c_and_the_struct_mirror_matches_it(tmp_path):
-    r = subprocess.run(["gcc", "-std=c99", "-fsyntax-only", "-Wall", "-Werror", "-x", "c", HEADER], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+def test_header_is_plain_c_and_the_struct_mirror_matches_it(tmp_path):     # plain C: check_library compiles it with -Wall -Werror
     src = tmp_path / "layout.c"
     fields = [f for f, _ in lidargs_optim._Tensor._fields_]
     src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "lidargs_optim.h"\nint main(void) { printf("%zu", sizeof(lidargs_adam_tensor));\n'
@@ -66,10 +47,10 @@ def test_header_is_plain_c_and_the_struct_mirror_matches_it(tmp_path):
 
 
 def test_main_library_is_unchanged_by_the_second(hip_lib_built):
-    main = _exports(hip_lib_built)
+    main = native_lib_checks.exports(hip_lib_built)
     assert main == set(lidargs_abi.signatures()) and len(main) == 86
     assert not any("adam" in n or "optim" in n for n in main)
-    assert _exports(_optim_lib(hip_lib_built)).isdisjoint(main)
+    assert native_lib_checks.exports(build_hip.TARGETS["optim"].out).isdisjoint(main)
     assert "adam.hip" not in build_hip.SOURCES and os.path.abspath(build_hip.build()) == os.path.abspath(hip_lib_built)
     from diff_lidargs_rasterization import _C
     assert _C._lib.lidargs_abi_version() == lidargs_abi.ABI_VERSION       # load() with today's arguments: as before

@@ -4,8 +4,6 @@ back-projection to 1e-12), its keyed minimum is the sequential loop, the fifth l
 declares, and the front refuses what it cannot take without needing a device."""
 import ctypes
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,7 +12,6 @@ import torch
 import range_view_ref as ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INCLUDE_RV = os.path.join(ROOT, "include_rangeview")
 DECLARED = {"lidargs_rv_scratch_bytes", "lidargs_rv_project", "lidargs_rv_unproject", "lidargs_rv_ray_dirs", "lidargs_rv_last_error",
             "lidargs_rv_abi_version"}
 TAGS = ("u16", "w16", "n16", "u64", "w64", "n64", "fov")
@@ -96,35 +93,17 @@ def test_margin_mask_keeps_most_points_and_drops_the_boundary_ones():
 
 def test_header_parses_and_library_exports_exactly_the_declared_functions(hip_lib_built):
     import build_hip
-    import lidargs_abi
-    assert os.path.exists(build_hip.RANGEVIEW_OUT), "build_hip.build() must build the range-view library too"
-    assert "range_view.hip" not in build_hip.SOURCES and build_hip.RANGEVIEW_SOURCES == {"range_view.hip": ["-ffp-contract=off"]}
-    typed = lidargs_abi.signatures(INCLUDE_RV)
-    assert set(typed) == DECLARED
-    exports = lambda so: set(re.findall(r" T (lidargs_\w+)", subprocess.run(["nm", "-D", "--defined-only", so], capture_output=True, text=True).stdout))
-    assert exports(build_hip.RANGEVIEW_OUT) == DECLARED and exports(hip_lib_built).isdisjoint(DECLARED)
+    import native_lib_checks
+    import range_view as rv
+    typed = native_lib_checks.check_library(build_hip.TARGETS["rangeview"], DECLARED, rv._lib, hip_lib_built)
+    assert build_hip.TARGETS["rangeview"].sources == {"range_view.hip": ["-ffp-contract=off"]}
     i, z, f, p = ctypes.c_int, ctypes.c_size_t, ctypes.c_float, ctypes.c_void_p              # written from the header by eye
     assert typed["lidargs_rv_scratch_bytes"] == (z, (i, i))
     assert typed["lidargs_rv_project"] == (i, (i, p, i, i, p, f, f, f, p, i, p, p, p, z, p))
     assert typed["lidargs_rv_unproject"] == (i, (i, i, p, p, p, f, f, p, p, p, p, z, p))
     assert typed["lidargs_rv_ray_dirs"] == (i, (i, i, p, f, f, p, p))
     assert typed["lidargs_rv_last_error"] == (ctypes.c_char_p, ()) and typed["lidargs_rv_abi_version"] == (i, ())
-    import range_view as rv
-    for name, (restype, argtypes) in typed.items():
-        fn = getattr(rv._lib, name)
-        assert fn.restype is restype and tuple(fn.argtypes) == argtypes, name
     assert rv._lib.lidargs_rv_abi_version() == rv.ABI_VERSION == 1 and rv.PIXEL_ROWS == 1
-    for h in sorted(os.listdir(INCLUDE_RV)):
-        r = subprocess.run(["gcc", "-std=c99", "-fsyntax-only", "-Wall", "-Werror", "-x", "c", os.path.join(INCLUDE_RV, h)], capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
-
-
-def test_build_id_and_staleness_know_the_new_target(hip_lib_built):
-    import build_hip
-    assert not build_hip.rangeview_needs_build()
-    assert "RANGEVIEW_INCLUDE" in build_hip.build_id.__code__.co_names, "build_id() must hash include_rangeview/"
-    assert "range_view.hip" in os.listdir(build_hip.CSRC)                                  # csrc/ is hashed whole
-    assert "range_view.hip" in build_hip._OWN_TARGET                                       # and is no dependency of liblidargs_hip.so
 
 
 def test_entry_points_validate_before_any_device_work(hip_lib_built):

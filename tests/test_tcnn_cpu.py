@@ -3,9 +3,6 @@ exports exactly what its header declares, the restatement tests/tcnn_ref.py has 
 gradients, and the config handling (refusals, the `degree` warning, the widths) works without a device."""
 import ctypes
 import math
-import os
-import re
-import subprocess
 import warnings
 
 import pytest
@@ -13,8 +10,6 @@ import torch
 
 import tcnn_ref as ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INCLUDE_TCNN = os.path.join(ROOT, "include_tcnn")
 DECLARED = {"lidargs_tcnn_frequency_forward", "lidargs_tcnn_frequency_backward", "lidargs_tcnn_param_count", "lidargs_tcnn_mlp_forward",
             "lidargs_tcnn_forward_row_tile", "lidargs_tcnn_backward_row_tile", "lidargs_tcnn_backward_blocks",
             "lidargs_tcnn_backward_partial_floats", "lidargs_tcnn_mlp_backward", "lidargs_tcnn_last_error", "lidargs_tcnn_abi_version"}
@@ -23,12 +18,10 @@ DECLARED = {"lidargs_tcnn_frequency_forward", "lidargs_tcnn_frequency_backward",
 def test_header_parses_and_library_exports_exactly_the_declared_functions(hip_lib_built):
     import build_hip
     import lidargs_abi
-    assert os.path.exists(build_hip.TCNN_OUT), "build_hip.build() must build the stand-in's library too"
-    assert "raydrop_mlp.hip" not in build_hip.SOURCES and "raydrop_mlp.hip" in build_hip.TCNN_SOURCES
-    typed = lidargs_abi.signatures(INCLUDE_TCNN)
-    assert set(typed) == DECLARED
-    exports = lambda so: set(re.findall(r" T (lidargs_\w+)", subprocess.run(["nm", "-D", "--defined-only", so], capture_output=True, text=True).stdout))
-    assert exports(build_hip.TCNN_OUT) == DECLARED and exports(hip_lib_built).isdisjoint(DECLARED)
+    import native_lib_checks
+    import tinycudann as tcnn
+    typed = native_lib_checks.check_library(build_hip.TARGETS["tcnn"], DECLARED, tcnn._lib, hip_lib_built)
+    assert "raydrop_mlp.hip" in build_hip.TARGETS["tcnn"].sources
     assert len(lidargs_abi.signatures()) == 86                                 # nothing was added under include/
     i, z, p = ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p                   # written from the header by eye
     assert typed["lidargs_tcnn_frequency_forward"] == (i, (i, i, i, p, p, p))
@@ -37,22 +30,7 @@ def test_header_parses_and_library_exports_exactly_the_declared_functions(hip_li
     assert typed["lidargs_tcnn_mlp_forward"] == (i, (i, i, i, i, i, p, p, p, p))
     assert typed["lidargs_tcnn_backward_partial_floats"] == (z, (i, i, i, i))
     assert typed["lidargs_tcnn_mlp_backward"] == (i, (i, i, i, i, i) + (p,) * 6 + (z, p))
-    import tinycudann as tcnn
-    for name, (restype, argtypes) in typed.items():
-        fn = getattr(tcnn._lib, name)
-        assert fn.restype is restype and tuple(fn.argtypes) == argtypes, name
     assert tcnn._lib.lidargs_tcnn_abi_version() == tcnn.ABI_VERSION == 1
-    for h in sorted(os.listdir(INCLUDE_TCNN)):
-        r = subprocess.run(["gcc", "-std=c99", "-fsyntax-only", "-Wall", "-Werror", "-x", "c", os.path.join(INCLUDE_TCNN, h)], capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
-
-
-def test_build_id_and_staleness_know_the_new_target(hip_lib_built):
-    import build_hip
-    assert not build_hip.tcnn_needs_build()
-    deps = build_hip.build_id.__code__.co_names
-    assert "TCNN_INCLUDE" in deps, "build_id() must hash include_tcnn/"
-    assert "raydrop_mlp.hip" in os.listdir(build_hip.CSRC)                     # csrc/ is hashed whole
 
 
 def test_entry_points_validate_before_any_device_work(hip_lib_built):
