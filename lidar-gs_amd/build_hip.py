@@ -6,7 +6,8 @@ TARGETS below is the one description of what is built: per library its name, its
 flags, and the directory of the public headers that declare exactly what it exports.  `hip` is the main library (the rasterizers and
 everything include/ declares); every other entry is a single source with a header directory of its own, so that liblidargs_hip.so
 exports exactly what include/ declares.  Staleness (stale, deps), the build loop (build) and the content hash (build_id, build_id_files)
-are all derived from the table: a further library is one more entry.
+are all derived from the table: a further library is one more entry.  PACKAGE_TARGETS is a second table of the same kind for the
+libraries of stand-in packages whose source lies in the package: built, checked for staleness and loaded like the others, outside the build id.
 
 Per-file flags: the per-Gaussian kernels (preprocess.hip) are HBM-bound, so they are built with
 -ffp-contract=off: every expression rounds as written, which keeps the unit vectors s = p/|p| that
@@ -61,6 +62,25 @@ TARGETS = {t.name: t for t in (
     }, os.path.join(ROOT, "include_rangeview")),
 )}
 
+# Libraries of stand-in packages.  They are not entries of TARGETS because that table is pinned: tests/test_build_targets_cpu.py asserts its
+# five names, that every .hip directly in csrc/ belongs to one of them and that build_id_files() is csrc/, their headers and this file --
+# the id of what bench.py measures, which is nothing of these.  The same tuple plus the directory of the sources.
+PackageTarget = collections.namedtuple("PackageTarget", Target._fields + ("csrc",))
+PACKAGE_TARGETS = {t.name: t for t in (
+    # the torch_scatter stand-in (scatter_max / scatter_min with the winning position)
+    PackageTarget("scatter", os.path.join(HERE, "torch_scatter", "liblidargs_scatter.so"), {
+        "scatter.hip": [],
+    }, os.path.join(ROOT, "include_scatter"), os.path.join(HERE, "torch_scatter", "csrc")),
+)}
+
+
+def all_targets():
+    return list(TARGETS.values()) + list(PACKAGE_TARGETS.values())
+
+
+def _csrc(target):
+    return getattr(target, "csrc", CSRC)
+
 
 def _listed(d, keep=lambda f: True):
     return sorted(os.path.join(d, f) for f in os.listdir(d) if keep(f))
@@ -69,7 +89,7 @@ def _listed(d, keep=lambda f: True):
 def deps(target):
     """What a library is rebuilt for: its own sources, every shared file of csrc/ that is not a .hip (headers and .inc, whichever
     target includes them: more than needed, never less), every header of its include directory and this file."""
-    return ([os.path.join(CSRC, f) for f in target.sources] + _listed(CSRC, lambda f: not f.endswith(".hip"))
+    return ([os.path.join(_csrc(target), f) for f in target.sources] + _listed(CSRC, lambda f: not f.endswith(".hip"))
             + _listed(target.include) + [os.path.abspath(__file__)])
 
 
@@ -112,30 +132,31 @@ def build(force=False, verbose=False):
     """Up-to-date check and build under an exclusive file lock: the ranks of `bench.py --gpus N` (one process per GPU) all call this
     at start-up, and only the first may compile -- the others wait and then find the library up to date.  The link goes to a
     temporary name and is moved into place, so a process that loaded the library earlier never sees a half-written file.
-    Builds every library of TARGETS that is stale; returns the main library's path."""
-    if not force and not any(stale(t) for t in TARGETS.values()):
+    Builds every library of TARGETS and PACKAGE_TARGETS that is stale; returns the main library's path."""
+    if not force and not any(stale(t) for t in all_targets()):
         return OUT
     import fcntl
     os.makedirs(OBJ, exist_ok=True)
     with open(os.path.join(OBJ, ".lock"), "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
         try:
-            for t in TARGETS.values():
+            for t in all_targets():
                 if force or stale(t):
-                    _build_locked(t.sources, t.out, verbose)
+                    _build_locked(t, verbose)
             return OUT
         finally:
             fcntl.flock(lock, fcntl.LOCK_UN)
 
 
-def _build_locked(sources, out, verbose):
+def _build_locked(target, verbose):
+    sources, out, csrc = target.sources, target.out, _csrc(target)
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     extra_all = os.environ.get("LIDARGS_EXTRA_HIPCC_FLAGS", "").split()      # instrumented builds of the tools (e.g. -DLG_LANE_STATS), never the product's
 
     def compile_one(item):
         src, extra = item
         obj = os.path.join(OBJ, src.replace(".hip", ".o"))
-        cmd = [hipcc] + COMMON + extra + extra_all + ["-c", os.path.join(CSRC, src), "-o", obj]
+        cmd = [hipcc] + COMMON + extra + extra_all + ["-c", os.path.join(csrc, src), "-o", obj]
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)
