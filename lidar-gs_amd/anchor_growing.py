@@ -17,10 +17,11 @@ import ctypes as C
 
 import torch
 
+import lidargs_abi
 from diff_lidargs_rasterization import _C as _base
 
 _lib = _base._lib
-EXACT_DIVISION = 1     # LIDARGS_AG_EXACT_DIVISION
+EXACT_DIVISION = lidargs_abi.library_constants("hip")["LIDARGS_AG_EXACT_DIVISION"]
 
 
 def _f32c(t):

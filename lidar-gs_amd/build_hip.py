@@ -6,8 +6,8 @@ TARGETS below is the one description of what is built: per library its name, its
 flags, and the directory of the public headers that declare exactly what it exports.  `hip` is the main library (the rasterizers and
 everything include/ declares); every other entry is a single source with a header directory of its own, so that liblidargs_hip.so
 exports exactly what include/ declares.  Staleness (stale, deps), the build loop (build) and the content hash (build_id, build_id_files)
-are all derived from the table: a further library is one more entry.  PACKAGE_TARGETS is a second table of the same kind for the
-libraries of stand-in packages whose source lies in the package: built, checked for staleness and loaded like the others, outside the build id.
+are all derived from the table, and so is what the Python side loads (lidargs_abi.library takes a library's path, headers, version
+function and the name in its error messages from its entry): a further library is one more entry.
 
 Per-file flags: the per-Gaussian kernels (preprocess.hip) are HBM-bound, so they are built with
 -ffp-contract=off: every expression rounds as written, which keeps the unit vectors s = p/|p| that
@@ -42,44 +42,35 @@ SOURCES = {
     "knn.hip": ["-ffp-contract=off"],              # the 3-NN squared distances and the voxel quotients are compared bit for bit; the box bound prunes exactly only without contraction
     "metrics.hip": ["-ffp-contract=off"],          # the SSIM map and the float32 means round as scikit-image / torch write them
 }
-Target = collections.namedtuple("Target", "name out sources include")      # sources: {file of csrc/: [per-file flags]}; include: its header directory
+# sources: {file of csrc/: [per-file flags]}; include: its header directory; prefix: of its symbols (<prefix>_abi_version, <prefix>_last_error,
+# the macro <PREFIX>_ABI_VERSION); package: the importer that the loader's error messages name (lidargs_abi.library)
+Target = collections.namedtuple("Target", "name out sources include prefix package")
 TARGETS = {t.name: t for t in (
-    Target("hip", OUT, SOURCES, os.path.join(ROOT, "include")),
+    Target("hip", OUT, SOURCES, os.path.join(ROOT, "include"), "lidargs", "diff_lidargs_rasterization"),
     Target("optim", os.path.join(HERE, "lidargs_optim", "liblidargs_optim.so"), {
         "adam.hip": ["-ffp-contract=off"],         # torch's op-by-op roundings; the steps its device kernels fuse are written as fmaf
-    }, os.path.join(ROOT, "include_optim")),
+    }, os.path.join(ROOT, "include_optim"), "lidargs_optim", "lidargs_optim"),
     # the decode's two model options (use_feat_bank, appearance_dim > 0): entry points beside the decode's
     Target("decode_options", os.path.join(HERE, "liblidargs_decode_options.so"), {
         "decode_options.hip": [],
-    }, os.path.join(ROOT, "include_decode")),
+    }, os.path.join(ROOT, "include_decode"), "lidargs_ng_options", "neural_gaussians"),
     # the tinycudann stand-in (frequency encoding, fused MLP)
     Target("tcnn", os.path.join(HERE, "tinycudann", "liblidargs_tcnn.so"), {
         "raydrop_mlp.hip": [],
-    }, os.path.join(ROOT, "include_tcnn")),
+    }, os.path.join(ROOT, "include_tcnn"), "lidargs_tcnn", "tinycudann"),
     # the range-view conversion (point cloud -> range image and back)
     Target("rangeview", os.path.join(HERE, "liblidargs_rangeview.so"), {
         "range_view.hip": ["-ffp-contract=off"],   # the row and the column of a point are compared pixel for pixel with the reference's float32 evaluation
-    }, os.path.join(ROOT, "include_rangeview")),
-)}
-
-# Libraries of stand-in packages.  They are not entries of TARGETS because that table is pinned: tests/test_build_targets_cpu.py asserts its
-# five names, that every .hip directly in csrc/ belongs to one of them and that build_id_files() is csrc/, their headers and this file --
-# the id of what bench.py measures, which is nothing of these.  The same tuple plus the directory of the sources.
-PackageTarget = collections.namedtuple("PackageTarget", Target._fields + ("csrc",))
-PACKAGE_TARGETS = {t.name: t for t in (
+    }, os.path.join(ROOT, "include_rangeview"), "lidargs_rv", "range_view"),
     # the torch_scatter stand-in (scatter_max / scatter_min with the winning position)
-    PackageTarget("scatter", os.path.join(HERE, "torch_scatter", "liblidargs_scatter.so"), {
+    Target("scatter", os.path.join(HERE, "torch_scatter", "liblidargs_scatter.so"), {
         "scatter.hip": [],
-    }, os.path.join(ROOT, "include_scatter"), os.path.join(HERE, "torch_scatter", "csrc")),
+    }, os.path.join(ROOT, "include_scatter"), "lidargs_scatter", "torch_scatter"),
 )}
 
 
 def all_targets():
-    return list(TARGETS.values()) + list(PACKAGE_TARGETS.values())
-
-
-def _csrc(target):
-    return getattr(target, "csrc", CSRC)
+    return list(TARGETS.values())
 
 
 def _listed(d, keep=lambda f: True):
@@ -89,7 +80,7 @@ def _listed(d, keep=lambda f: True):
 def deps(target):
     """What a library is rebuilt for: its own sources, every shared file of csrc/ that is not a .hip (headers and .inc, whichever
     target includes them: more than needed, never less), every header of its include directory and this file."""
-    return ([os.path.join(_csrc(target), f) for f in target.sources] + _listed(CSRC, lambda f: not f.endswith(".hip"))
+    return ([os.path.join(CSRC, f) for f in target.sources] + _listed(CSRC, lambda f: not f.endswith(".hip"))
             + _listed(target.include) + [os.path.abspath(__file__)])
 
 
@@ -132,7 +123,7 @@ def build(force=False, verbose=False):
     """Up-to-date check and build under an exclusive file lock: the ranks of `bench.py --gpus N` (one process per GPU) all call this
     at start-up, and only the first may compile -- the others wait and then find the library up to date.  The link goes to a
     temporary name and is moved into place, so a process that loaded the library earlier never sees a half-written file.
-    Builds every library of TARGETS and PACKAGE_TARGETS that is stale; returns the main library's path."""
+    Builds every library of TARGETS that is stale; returns the main library's path."""
     if not force and not any(stale(t) for t in all_targets()):
         return OUT
     import fcntl
@@ -149,14 +140,14 @@ def build(force=False, verbose=False):
 
 
 def _build_locked(target, verbose):
-    sources, out, csrc = target.sources, target.out, _csrc(target)
+    sources, out = target.sources, target.out
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     extra_all = os.environ.get("LIDARGS_EXTRA_HIPCC_FLAGS", "").split()      # instrumented builds of the tools (e.g. -DLG_LANE_STATS), never the product's
 
     def compile_one(item):
         src, extra = item
         obj = os.path.join(OBJ, src.replace(".hip", ".o"))
-        cmd = [hipcc] + COMMON + extra + extra_all + ["-c", os.path.join(csrc, src), "-o", obj]
+        cmd = [hipcc] + COMMON + extra + extra_all + ["-c", os.path.join(CSRC, src), "-o", obj]
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)

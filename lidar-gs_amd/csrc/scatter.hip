@@ -18,8 +18,8 @@
 // The divisions that split i into (a, e, b) are 32-bit whenever every count fits (Idx = unsigned), 64-bit otherwise.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "../../../include_scatter/lidargs_scatter.h"
-#include "../../csrc/lidargs_status.h"
+#include "../../include_scatter/lidargs_scatter.h"
+#include "lidargs_status.h"
 
 namespace {
 

@@ -13,7 +13,6 @@ and the shared library must have been built (python lidar-gs_amd/build_hip.py, o
 __graft_entry__.build()); otherwise importing or calling this module fails loudly.
 """
 import ctypes as C
-import os
 
 import torch
 
@@ -21,7 +20,8 @@ import lidargs_abi
 
 NUM_CHANNELS = 2  # R3/cr/config.h:15
 # The one CDLL of the process, every lidargs_* function typed from the headers (restype and argtypes: lidargs_abi).
-_lib = lidargs_abi.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "liblidargs_hip.so"))
+_lib = lidargs_abi.library("hip")
+_ptr, _stream = lidargs_abi.ptr, lidargs_abi.stream
 _ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_size_t)
 
 
@@ -30,10 +30,9 @@ def _err():
 
 
 def _raise(code, what):
-    msg = _err()
     if code == -2:  # LIDARGS_ERR_NO_COLORS: the reference throws std::runtime_error here (R3/cr/rasterizer_impl.cu:249-252)
-        raise RuntimeError(msg)
-    raise RuntimeError(f"{what} failed with code {code}: {msg}")
+        raise RuntimeError(_err())
+    lidargs_abi.check(_lib, code, what)
 
 
 def _require_device(t, name):
@@ -50,19 +49,8 @@ def _f32(t, name):
     return t.contiguous()
 
 
-def _ptr(t):
-    """Device pointer, NULL for empty tensors (torch gives data_ptr()==0 for them, which is what the
-    reference relies on for `cov3D_precomp != nullptr`, R3/cr/forward.cu:307)."""
-    if t is None or t.numel() == 0:
-        return None
-    return C.c_void_p(t.data_ptr())
-
-
 _scratch_registry = {}
-# LIDARGS_POISON_SCRATCH=1 (tests): every scratch buffer handed to the library is filled with 0xFF bytes (NaN floats, huge
-# integers) first, so that a kernel reading scratch memory nobody wrote shows up deterministically instead of depending on what
-# the caching allocator happens to recycle.
-_POISON = os.environ.get("LIDARGS_POISON_SCRATCH", "0") == "1"
+_POISON = lidargs_abi.poison_scratch()     # read once, at import
 
 
 @_ALLOC_FN
@@ -105,10 +93,6 @@ class _Scratch:
 
     def __del__(self):
         _scratch_registry.pop(getattr(self, "key", None), None)
-
-
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,

@@ -14,17 +14,13 @@ There is NO CPU path: a parameter that is not on a HIP device is a RuntimeError.
 learning rates and step counts are launch arguments, a replayed capture would repeat the captured ones.
 """
 import ctypes as C
-import os
 
 import torch
 
 import lidargs_abi
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-INCLUDE = os.path.normpath(os.path.join(_HERE, "..", "..", "include_optim"))
-ABI_VERSION = 1     # LIDARGS_OPTIM_ABI_VERSION of include_optim/lidargs_optim.h
-_lib = lidargs_abi.load(os.path.join(_HERE, "liblidargs_optim.so"), include=INCLUDE, version_fn="lidargs_optim_abi_version",
-                        version=ABI_VERSION, package="lidargs_optim")
+_lib = lidargs_abi.library("optim")
+ABI_VERSION = lidargs_abi.library_constants("optim")["LIDARGS_OPTIM_ABI_VERSION"]
 MAX_TENSORS = _lib.lidargs_adam_max_tensors()
 
 
@@ -120,7 +116,7 @@ class Adam(torch.optim.Optimizer):
             for it in items:
                 calls.setdefault((it[6][0], it[6][1], it[7]), []).append(it)
             with torch.cuda.device(device):
-                stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+                stream = lidargs_abi.stream(device)
                 for (beta1, beta2, eps), its in calls.items():
                     for lo in range(0, len(its), MAX_TENSORS):
                         self._launch(its[lo:lo + MAX_TENSORS], beta1, beta2, eps, stream)
@@ -140,6 +136,4 @@ class Adam(torch.optim.Optimizer):
             e.param, e.grad, e.exp_avg, e.exp_avg_sq, e.n = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
             e.neg_step_size = -step_size
             e.inv_bias_correction2_sqrt = 1.0 / bias_correction2_sqrt      # torch's device kernel for tensor / python_float multiplies by this
-        rc = _lib.lidargs_adam_step(len(items), table, beta1, beta2, eps, stream)
-        if rc < 0:
-            raise RuntimeError(f"lidargs_optim.Adam: step failed with code {rc}: {_lib.lidargs_optim_last_error().decode(errors='replace')}")
+        lidargs_abi.check(_lib, _lib.lidargs_adam_step(len(items), table, beta1, beta2, eps, stream), "lidargs_optim.Adam: step")

@@ -24,9 +24,7 @@ import lidargs_abi
 from diff_lidargs_rasterization import _C as _base
 
 _lib = _base._lib
-_HERE = os.path.dirname(os.path.abspath(__file__))
-OPTIONS_INCLUDE = os.path.normpath(os.path.join(_HERE, "..", "include_decode"))
-OPTIONS_ABI_VERSION = 1     # LIDARGS_NG_OPTIONS_ABI_VERSION of include_decode/lidargs_decode_options.h
+OPTIONS_ABI_VERSION = lidargs_abi.library_constants("decode_options")["LIDARGS_NG_OPTIONS_ABI_VERSION"]
 _OPTIONS_LIB = None
 
 
@@ -34,8 +32,7 @@ def _options_lib():
     """liblidargs_decode_options.so, loaded and typed on the first use of an option: a model with both options off never needs it."""
     global _OPTIONS_LIB
     if _OPTIONS_LIB is None:
-        _OPTIONS_LIB = lidargs_abi.load(os.path.join(_HERE, "liblidargs_decode_options.so"), include=OPTIONS_INCLUDE,
-                                        version_fn="lidargs_ng_options_abi_version", version=OPTIONS_ABI_VERSION, package="neural_gaussians")
+        _OPTIONS_LIB = lidargs_abi.library("decode_options")
     return _OPTIONS_LIB
 MLP_ORDER = ("opacity", "cov", "color", "raydrop")
 
@@ -257,8 +254,7 @@ class _Decode(torch.autograd.Function):
 
 
 def _check_opt(rc, what):
-    if rc < 0:
-        raise RuntimeError(f"{what} failed with code {rc}: {_options_lib().lidargs_ng_options_last_error().decode(errors='replace')}")
+    lidargs_abi.check(_options_lib(), rc, what)
 
 
 class _FeatBank(torch.autograd.Function):

@@ -19,19 +19,15 @@ would be a read of its own): it goes through the native call like any other and 
 There is NO numpy path: what the native library cannot take is a RuntimeError or ValueError, never a fallback.
 """
 import ctypes as C
-import os
 
 import numpy as np
 import torch
 
 import lidargs_abi
+from lidargs_abi import ptr as _ptr, stream as _stream
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-INCLUDE = os.path.normpath(os.path.join(_HERE, "..", "include_rangeview"))
-ABI_VERSION = 1     # LIDARGS_RV_ABI_VERSION of include_rangeview/lidargs_range_view.h
-PIXEL_ROWS = 1      # LIDARGS_RV_PIXEL_ROWS
-_lib = lidargs_abi.load(os.path.join(_HERE, "liblidargs_rangeview.so"), include=INCLUDE, version_fn="lidargs_rv_abi_version",
-                        version=ABI_VERSION, package="range_view")
+_lib = lidargs_abi.library("rangeview")
+ABI_VERSION, PIXEL_ROWS = (lidargs_abi.library_constants("rangeview")["LIDARGS_RV_" + k] for k in ("ABI_VERSION", "PIXEL_ROWS"))
 
 
 def get_beam_inclinations(fov_up, fov, H):
@@ -40,17 +36,8 @@ def get_beam_inclinations(fov_up, fov, H):
     return ((fov_up - j / H * fov) / 180 * np.pi)[::-1]
 
 
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 def _check(rc, what):
-    if rc < 0:
-        raise RuntimeError(f"range_view.{what} failed with code {rc}: {_lib.lidargs_rv_last_error().decode(errors='replace')}")
+    lidargs_abi.check(_lib, rc, "range_view." + what)
 
 
 def _image(x, name, what):

@@ -15,43 +15,25 @@ Both are torch.nn.Modules with one flat float32 parameter `params` (empty for th
     width, composite encodings, NetworkWithInputEncoding and dtype=torch.half raise NotImplementedError.
 There is NO CPU path and no fallback to framework ops: an input that is not a float32 tensor on a HIP device is a RuntimeError.
 """
-import ctypes as C
 import math
-import os
 
 import torch
 
 import lidargs_abi
+from lidargs_abi import poison_scratch as _poison, ptr as _ptr, stream as _stream
 from . import _config
 from ._config import layer_shapes, parse_encoding, parse_network  # noqa: F401
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-INCLUDE = os.path.normpath(os.path.join(_HERE, "..", "..", "include_tcnn"))
-ABI_VERSION = 1     # LIDARGS_TCNN_ABI_VERSION of include_tcnn/lidargs_tcnn.h
-_lib = lidargs_abi.load(os.path.join(_HERE, "liblidargs_tcnn.so"), include=INCLUDE, version_fn="lidargs_tcnn_abi_version",
-                        version=ABI_VERSION, package="tinycudann")
+_lib = lidargs_abi.library("tcnn")
+ABI_VERSION = _config.CONSTANTS["LIDARGS_TCNN_ABI_VERSION"]
 FORWARD_ROW_TILE = _lib.lidargs_tcnn_forward_row_tile()
 BACKWARD_ROW_TILE = _lib.lidargs_tcnn_backward_row_tile()
 
 __all__ = ["Encoding", "Network", "NetworkWithInputEncoding"]
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
-
-
-def _stream(t):
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
 def _check(rc, what):
-    if rc < 0:
-        raise RuntimeError(f"tinycudann stand-in: {what} failed with code {rc}: {_lib.lidargs_tcnn_last_error().decode(errors='replace')}")
-
-
-def _poison():
-    """LIDARGS_POISON_SCRATCH=1 (tests): scratch is filled with 0xFF bytes before the library sees it."""
-    return os.environ.get("LIDARGS_POISON_SCRATCH", "0") == "1"
+    lidargs_abi.check(_lib, rc, "tinycudann stand-in: " + what)
 
 
 def _checked_input(x, width, who):

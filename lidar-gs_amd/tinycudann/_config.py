@@ -6,10 +6,10 @@ constructor that names each key and what is used in its place.
 """
 import warnings
 
-WIDTH = 128                      # LIDARGS_TCNN_WIDTH of include_tcnn/lidargs_tcnn.h
-MAX_HIDDEN_LAYERS = 8
-MAX_OUT = 16
-MAX_FREQUENCIES = 32
+import lidargs_abi
+
+CONSTANTS = lidargs_abi.library_constants("tcnn")      # the limits are those of include_tcnn/lidargs_tcnn.h
+WIDTH, MAX_HIDDEN_LAYERS, MAX_OUT, MAX_FREQUENCIES = (CONSTANTS["LIDARGS_TCNN_" + k] for k in ("WIDTH", "MAX_HIDDEN_LAYERS", "MAX_OUT", "MAX_FREQUENCIES"))
 DEFAULT_FREQUENCIES = 12         # tinycudann's documented default of the Frequency encoding
 OUTPUT_ACTIVATIONS = {"None": 0, "Sigmoid": 1}        # out_act of the C ABI
 NETWORK_OTYPES = ("FullyFusedMLP", "CutlassMLP")      # one native path for both

@@ -1,6 +1,6 @@
 """`torch_scatter` -- a native stand-in for the part of torch_scatter the reference uses (scene/gaussian_model.py:15 imports
 `scatter_max`, :742 calls it): with lidar-gs_amd/ on PYTHONPATH `import torch_scatter` resolves here and runs on the HIP kernels of
-include_scatter/lidargs_scatter.h (torch_scatter/csrc/scatter.hip, liblidargs_scatter.so).
+include_scatter/lidargs_scatter.h (csrc/scatter.hip, liblidargs_scatter.so; the entry `scatter` of build_hip.TARGETS).
 
     scatter_max(src, index, dim=-1, out=None, dim_size=None) -> (out, arg)
     scatter_min(src, index, dim=-1, out=None, dim_size=None) -> (out, arg)
@@ -17,21 +17,15 @@ The gradient goes to `src` only: grad_out at the `arg` positions, 0 elsewhere (t
 Everything else of torch_scatter (scatter_sum / add / mean / mul, the segment and composite ops) is NOT here: the name raises
 NotImplementedError, which names torch's own device op.  There is NO CPU path and no fallback to framework ops.
 """
-import ctypes as C
-import os
-
 import torch
 
 import lidargs_abi
+from lidargs_abi import poison_scratch as _poison, ptr as _ptr, stream as _stream
 
 __version__ = "2.1.2"   # the torch_scatter release whose signatures these are
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-INCLUDE = os.path.normpath(os.path.join(_HERE, "..", "..", "include_scatter"))
-ABI_VERSION = 1     # LIDARGS_SCATTER_ABI_VERSION of include_scatter/lidargs_scatter.h
-MAX, MIN = 0, 1     # LIDARGS_SCATTER_MAX, LIDARGS_SCATTER_MIN
-_lib = lidargs_abi.load(os.path.join(_HERE, "liblidargs_scatter.so"), include=INCLUDE, version_fn="lidargs_scatter_abi_version",
-                        version=ABI_VERSION, package="torch_scatter")
+_lib = lidargs_abi.library("scatter")
+ABI_VERSION, MAX, MIN = (lidargs_abi.library_constants("scatter")["LIDARGS_SCATTER_" + k] for k in ("ABI_VERSION", "MAX", "MIN"))
 
 __all__ = ["scatter_max", "scatter_min", "scatter"]
 
@@ -62,22 +56,8 @@ def __getattr__(name):
     raise AttributeError(f"module 'torch_scatter' has no attribute '{name}'")
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
-
-
-def _stream(t):
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
 def _check(rc, what):
-    if rc < 0:
-        raise RuntimeError(f"torch_scatter stand-in: {what} failed with code {rc}: {_lib.lidargs_scatter_last_error().decode(errors='replace')}")
-
-
-def _poison():
-    """LIDARGS_POISON_SCRATCH=1 (tests): scratch is filled with 0xFF bytes before the library sees it."""
-    return os.environ.get("LIDARGS_POISON_SCRATCH", "0") == "1"
+    lidargs_abi.check(_lib, rc, "torch_scatter stand-in: " + what)
 
 
 def _typed(t, name, dtype, who):

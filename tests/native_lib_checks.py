@@ -9,7 +9,7 @@ import lidargs_abi
 
 # target name -> "test module:its set of declared functions": the module whose test calls check_library() for that target
 SATELLITES = {"optim": "test_optim_cpu:DECLARED", "decode_options": "test_decode_options_cpu:NEW", "tcnn": "test_tcnn_cpu:DECLARED",
-              "rangeview": "test_range_view_cpu:DECLARED"}
+              "rangeview": "test_range_view_cpu:DECLARED", "scatter": "test_scatter_cpu:DECLARED"}
 
 
 def exports(so):

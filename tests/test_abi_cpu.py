@@ -106,6 +106,85 @@ def test_parser_refuses_what_it_cannot_map():
             lidargs_abi.parse_header(text)
 
 
+def test_constants_against_the_defines_read_by_eye(tmp_path):
+    """Every `#define LIDARGS_* <integer>` of each header directory, written out from the headers by hand."""
+    import build_hip
+    import lidargs_abi
+    by_eye = {
+        "hip": {"LIDARGS_ABI_VERSION": 2, "LIDARGS_NUM_CHANNELS": 2, "LIDARGS_MAX_STAGES": 24, "LIDARGS_AG_EXACT_DIVISION": 1},
+        "optim": {"LIDARGS_OPTIM_ABI_VERSION": 1, "LIDARGS_ADAM_MAX_TENSORS": 64},
+        "decode_options": {"LIDARGS_NG_OPTIONS_ABI_VERSION": 1, "LIDARGS_NG_OPTIONS_ERR_INVALID_ARGUMENT": -1, "LIDARGS_NG_OPTIONS_ERR_HIP": -4,
+                           "LIDARGS_NG_BANK_PARAMS": 259},
+        "tcnn": {"LIDARGS_TCNN_ABI_VERSION": 1, "LIDARGS_TCNN_WIDTH": 128, "LIDARGS_TCNN_MAX_HIDDEN_LAYERS": 8, "LIDARGS_TCNN_MAX_OUT": 16,
+                 "LIDARGS_TCNN_MAX_FREQUENCIES": 32},
+        "rangeview": {"LIDARGS_RV_ABI_VERSION": 1, "LIDARGS_RV_PIXEL_ROWS": 1},
+        "scatter": {"LIDARGS_SCATTER_ABI_VERSION": 1, "LIDARGS_SCATTER_MAX": 0, "LIDARGS_SCATTER_MIN": 1},
+    }
+    assert list(by_eye) == list(build_hip.TARGETS)
+    for name, want in by_eye.items():
+        assert lidargs_abi.constants(build_hip.TARGETS[name].include) == lidargs_abi.library_constants(name) == want, name
+        assert want[build_hip.TARGETS[name].prefix.upper() + "_ABI_VERSION"] >= 1
+    assert lidargs_abi.constants() == by_eye["hip"] and lidargs_abi.ABI_VERSION == 2
+    (tmp_path / "a.h").write_text(
+        "#ifndef LIDARGS_A_H\n#define LIDARGS_A_H\n"
+        "#define LIDARGS_A_VERSION 7 /* a comment that goes on\n#define LIDARGS_A_IN_A_COMMENT 5\n   over lines */\n"
+        "#define LIDARGS_A_LINE 3 // to the end of the line\n"
+        "  #  define LIDARGS_A_NEG (-12)   /* in parentheses */\n"
+        "#define LIDARGS_A_EXPR (1 << 4)\n#define LIDARGS_A_FLOAT 1.5\n#define LIDARGS_A_NAME lidargs_a\n#define LIDARGS_A_CALL(x) 1\n"
+        "#define LIDARGS_A_TRAILING 4 + 1\n#define OTHER_A 9\n#endif\n")
+    (tmp_path / "b.txt").write_text("#define LIDARGS_NOT_A_HEADER 1\n")
+    assert lidargs_abi.constants(str(tmp_path)) == {"LIDARGS_A_VERSION": 7, "LIDARGS_A_LINE": 3, "LIDARGS_A_NEG": -12}
+    with pytest.raises(ImportError, match="are missing"):
+        lidargs_abi.constants(str(tmp_path / "nowhere"))
+
+
+def test_library_loads_every_target_from_the_table(hip_lib_built, tmp_path, monkeypatch):
+    """library(name) is load() with the table's entry; the ImportErrors are load()'s own, for every package name."""
+    import build_hip
+    import lidargs_abi
+    for name, t in build_hip.TARGETS.items():
+        lib = lidargs_abi.library(name)
+        assert lib._name == t.out, name
+        version = getattr(lib, t.prefix + "_abi_version")()
+        assert version == lidargs_abi.library_constants(name)[t.prefix.upper() + "_ABI_VERSION"], name
+        assert isinstance(getattr(lib, t.prefix + "_last_error")(), bytes)
+        for fn, (restype, argtypes) in lidargs_abi.signatures(t.include).items():
+            assert getattr(lib, fn).restype is restype and tuple(getattr(lib, fn).argtypes) == argtypes, fn
+        so = os.path.basename(t.out)
+        with pytest.raises(ImportError, match=re.escape(f"{t.package}: {so} ABI version mismatch; rebuild it")):
+            lidargs_abi.load(t.out, include=t.include, version_fn=t.prefix + "_abi_version", version=version + 1, package=t.package)
+        missing = str(tmp_path / so)                                       # the same entry, pointing at a library that is not there
+        monkeypatch.setitem(build_hip.TARGETS, name, t._replace(out=missing))
+        with pytest.raises(ImportError) as e:
+            lidargs_abi.library(name)
+        assert str(e.value) == (f"{t.package}: native library {missing} is missing. Build it with "
+                                "`python lidar-gs_amd/build_hip.py` (hipcc --offload-arch=gfx950). There is no CPU fallback.")
+
+
+def test_the_call_helpers_are_stated_once(hip_lib_built, monkeypatch):
+    import lidargs_abi
+    from diff_lidargs_rasterization import _C
+    assert _C._ptr is lidargs_abi.ptr and _C._stream is lidargs_abi.stream
+    assert lidargs_abi.ptr(None) is None and lidargs_abi.ptr(torch.zeros(0)) is None and lidargs_abi.ptr(torch.zeros(3, 0)) is None
+    t = torch.zeros(4)
+    assert isinstance(lidargs_abi.ptr(t), ctypes.c_void_p) and lidargs_abi.ptr(t).value == t.data_ptr()
+    lib = _C._lib
+    assert lib.lidargs_mark_visible(-1, None, None, None, None, None) == -1
+    for rc in (0, 3):
+        lidargs_abi.check(lib, rc, "nothing")                              # only a negative code is an error
+    with pytest.raises(RuntimeError, match=r"^mark_visible failed with code -1: .*mark_visible"):
+        lidargs_abi.check(lib, -1, "mark_visible")
+    with pytest.raises(RuntimeError, match=r"^mark_visible failed with code -1: "):
+        _C._raise(-1, "mark_visible")
+    with pytest.raises(RuntimeError, match=r"^(?!.*failed with code)"):                    # -2: the library's message alone
+        _C._raise(-2, "mark_visible")
+    for value, want in (("1", True), ("0", False), ("", False), ("true", False)):
+        monkeypatch.setenv("LIDARGS_POISON_SCRATCH", value)
+        assert lidargs_abi.poison_scratch() is want
+    monkeypatch.delenv("LIDARGS_POISON_SCRATCH")
+    assert lidargs_abi.poison_scratch() is False
+
+
 def test_typed_calls_are_refused_before_the_library_is_entered(hip_lib_built):
     """Through the package's own _lib.  lidargs_mark_visible validates first (P = -1 never reaches the device), and a call ctypes
     refuses never reaches it: the thread's last error stays the one a different entry point left."""
@@ -222,7 +301,8 @@ def test_missing_library_is_a_loud_import_error(tmp_path, hip_lib_built):
     dst.mkdir()
     for fn in ("__init__.py", "_C.py"):
         shutil.copy(os.path.join(src, fn), dst / fn)
-    shutil.copy(os.path.join(ROOT, "lidar-gs_amd", "lidargs_abi.py"), tmp_path / "lidargs_abi.py")     # the loader _C.py imports
+    for fn in ("lidargs_abi.py", "build_hip.py"):                          # the loader _C.py imports, and the table the loader reads
+        shutil.copy(os.path.join(ROOT, "lidar-gs_amd", fn), tmp_path / fn)
     code = f"import sys; sys.path.insert(0, {str(tmp_path)!r}); import diff_lidargs_rasterization"
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True)
     assert r.returncode != 0 and "liblidargs_hip.so is missing" in (r.stderr + r.stdout).replace("\n", " ") or "is missing" in r.stderr
@@ -237,7 +317,8 @@ def test_missing_headers_are_a_loud_import_error(tmp_path, hip_lib_built):
     for fn in ("__init__.py", "_C.py"):
         shutil.copy(os.path.join(src, fn), dst / fn)
     os.symlink(hip_lib_built, dst / "liblidargs_hip.so")
-    shutil.copy(os.path.join(ROOT, "lidar-gs_amd", "lidargs_abi.py"), tmp_path / "tree" / "lidargs_abi.py")
+    for fn in ("lidargs_abi.py", "build_hip.py"):
+        shutil.copy(os.path.join(ROOT, "lidar-gs_amd", fn), tmp_path / "tree" / fn)
     code = f"import sys; sys.path.insert(0, {str(tmp_path / 'tree')!r}); import diff_lidargs_rasterization"
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True)
     assert r.returncode != 0 and "ImportError" in r.stderr and "headers" in r.stderr and "are missing" in r.stderr

@@ -16,7 +16,7 @@ def headers(t):
 
 
 def test_table_is_ordered_and_every_satellite_has_its_checks():
-    assert list(TARGETS) == ["hip", "optim", "decode_options", "tcnn", "rangeview"] and all(t.name == k for k, t in TARGETS.items())
+    assert list(TARGETS) == ["hip", "optim", "decode_options", "tcnn", "rangeview", "scatter"] and all(t.name == k for k, t in TARGETS.items())
     assert TARGETS["hip"].out == build_hip.OUT and TARGETS["hip"].sources is build_hip.SOURCES
     assert len({t.out for t in TARGETS.values()}) == len({t.include for t in TARGETS.values()}) == len(TARGETS)
     assert set(SATELLITES) == set(TARGETS) - {"hip"}, "a library of TARGETS without a registered declared set"

