@@ -33,6 +33,12 @@
  * buffer's address and the library keeps no per-forward host state, so the saved buffers may be
  * cloned, moved, offloaded and brought back before the backward runs, and a backward may run
  * more than once on them (the "gradient lines still zero" mark is a word inside the geometry buffer).
+ *
+ * LIDARGS_DETERMINISTIC=1 in the environment of lidargs_forward (read at every call) selects the deterministic
+ * mode: the geometry buffer is asked for 128 bytes per Gaussian longer and carries a mode word, and every
+ * lidargs_backward on those buffers -- which reads no environment -- returns gradients that are a pure function
+ * of its inputs (64-bit integer accumulation across workgroups instead of float atomics).  lidargs_forward_enqueue,
+ * the shell / wedge forwards and lidargs_surfel_forward return LIDARGS_ERR_INVALID_ARGUMENT while it is set.
  */
 #ifndef LIDARGS_RASTERIZER_H
 #define LIDARGS_RASTERIZER_H

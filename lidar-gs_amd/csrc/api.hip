@@ -20,6 +20,7 @@
 #include <string.h>
 #include <limits>
 #include <algorithm>
+#include <atomic>
 #include <mutex>
 
 namespace {
@@ -301,6 +302,24 @@ Profiler g_prof;   // process-wide: autograd runs backward on its own thread
 namespace lg {
 int api_fail(int code, const char* msg) { return fail(code, "%s", msg); }
 int api_check_launch(hipStream_t s, int debug, const char* what) { return check_launch(s, debug, what); }
+// LIDARGS_DETERMINISTIC=1: a supported mode, not a diagnostic -- lidargs_forward makes buffers on which every lidargs_backward is a
+// pure function of its inputs (lidargs_common.h "deterministic accumulation").  Read at EVERY call (a caller may flip it between two
+// frames of one process), and by forward entry points only: a backward takes the mode from the buffers.
+bool deterministic_env() {
+    const char* e = getenv("LIDARGS_DETERMINISTIC");
+    return e && *e && atoi(e) != 0;
+}
+// Has ANY forward of this process made deterministic buffers?  Until one has, no buffer a backward of this process can be handed is
+// deterministic, and backward_impl neither queues the second walk nor hands its kernels the mode word: the default mode then runs
+// exactly the launches it ran before the mode existed.  Not per-forward state (it is never cleared, names no buffer and decides no
+// result: with it set, the buffer's word decides as always) -- only the licence to skip a launch that would retire at once.
+std::atomic<bool> g_deterministic_seen{false};
+// The forwards the mode does not cover yet refuse it, before any device work: running their float-atomic backward under a switch that
+// promises the opposite would be worse than an error.
+int refuse_deterministic(const char* entry) {
+    if (!deterministic_env()) return 0;
+    return fail(LIDARGS_ERR_INVALID_ARGUMENT, "%s: LIDARGS_DETERMINISTIC=1 is not supported by this entry point (only lidargs_forward / lidargs_backward are); unset it for this call", entry);
+}
 int api_read_words_zero_behind(const uint32_t* dev, int n, uint32_t* out, void* zero, size_t zero_bytes, hipStream_t s) {
     hipError_t e = (hipError_t)read_words_begin(dev, n, s);
     if (e == hipSuccess && zero && zero_bytes) e = hipMemsetAsync(zero, 0, zero_bytes, s);
@@ -510,6 +529,9 @@ struct FrameMode {
     // device word, optional: the P rows are a capacity-sized selection of which only the first *n_valid exist (enqueue-only rank frames
     // of the sharded path): the preprocess culls the rest before reading them, everything behind it sees culled Gaussians.
     const uint32_t* n_valid = nullptr;
+    // lidargs_forward under LIDARGS_DETERMINISTIC=1: the geometry buffer is asked for with its 64-bit accumulator lines behind everything
+    // else and its mode word set (lidargs_common.h LG_TOTALS_MODE_WORD); every backward on these buffers then adds up in fixed point.
+    bool deterministic = false;
 };
 
 // The preprocess' parameters of a whole frame on `grid`: no column wedge, full span records, pruning on, every row valid.  The forward,
@@ -556,13 +578,17 @@ int forward_impl(lidargs_alloc_fn geometry_alloc, void* geometry_user, lidargs_a
     const lg::TileGrid grid4 = lg::make_grid(width, height, 4);        // the image buffer is laid out for the finest tiling
     lg::prof_begin(stream, 0);
 
-    char* geom_p = geometry_alloc(geometry_user, lg::geom_carve(nullptr, (size_t)P, lg::GAUSS_BUFFERS, nullptr));
+    char* geom_p = geometry_alloc(geometry_user, lg::geom_carve(nullptr, (size_t)P, lg::GAUSS_BUFFERS, nullptr, mode.deterministic));
     if (!geom_p) return fail(LIDARGS_ERR_ALLOC, "geometry allocator returned NULL%s");
     char* img_p = image_alloc(image_user, lg::img_carve(nullptr, width, height, grid4.num_tiles(), nullptr));
     if (!img_p) return fail(LIDARGS_ERR_ALLOC, "image allocator returned NULL%s");
     lg::GeomView geom; lg::geom_carve(geom_p, (size_t)P, lg::GAUSS_BUFFERS, &geom);
     lg::ImgView img; lg::img_carve(img_p, width, height, grid4.num_tiles(), &img);
     LG_HIP(hipMemsetAsync(geom.totals, 0, LG_TOTALS_WORDS * sizeof(uint32_t), stream));
+    if (mode.deterministic) {
+        lg::g_deterministic_seen.store(true, std::memory_order_relaxed);   // (before the buffer can reach any backward)
+        LG_HIP(hipMemsetD32Async((hipDeviceptr_t)(geom.totals + LG_TOTALS_MODE_WORD), 1, 1, stream));   // (0 = the default, from the line above)
+    }
 
     lg::PreprocessParams pp = preprocess_params(P, grid4, scale_modifier, near_f, far_f, shell_lo, shell_hi, viewmatrix);
     pp.compact = lg::compact_spans(grid4.tiles_x, height) ? 1 : 0;
@@ -661,6 +687,11 @@ int backward_impl(int P, int R, const float* background, int width, int height, 
         return fail(LIDARGS_ERR_INVALID_ARGUMENT, "backward: NULL required pointer%s");
 
     lg::GeomView geom; lg::geom_carve(geom_buffer, (size_t)P, lg::GAUSS_BUFFERS, &geom);
+    // The accumulation mode is the forward's and travels in the geometry buffer (LG_TOTALS_MODE_WORD); the host never reads it.  On a plain
+    // frame's buffers the kernels are handed the word and the place deterministic buffers keep their 64-bit lines at; shell and wedge
+    // forwards refuse the mode, so their backwards do not look -- and nobody looks in a process that never made a deterministic forward.
+    const bool may_be_det = !mode.is_shell && col_lo < 0 && lg::g_deterministic_seen.load(std::memory_order_relaxed);
+    const uint32_t* const det_mode = may_be_det ? geom.totals + LG_TOTALS_MODE_WORD : nullptr;
     // a column wedge's buffers: only its own patches were rendered
     if (col_lo >= 0 && (col_lo % LG_TILE_W || col_hi <= col_lo || col_hi > width)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "backward: bad column wedge%s");
     const lg::FrameLayout L = lg::frame_layout(R, width, height, col_lo, col_hi, mode.is_shell ? lg::FRAME_SHELL : lg::FRAME_GAUSS);   // (from the forward's num_rendered)
@@ -673,7 +704,7 @@ int backward_impl(int P, int R, const float* background, int width, int height, 
     lg::ZeroRows zr;
     zr.add(dL_dmean2D, 4); zr.add(dL_dconic, 4); zr.add(dL_dopacity, 1); zr.add(dL_dcolor, 2); zr.add(dL_ddepths, 1); zr.add(dL_dmean3D, 3);
     zr.add(dL_dsphere_means3D, 3); zr.add(dL_dbasis_u1, 3); zr.add(dL_dbasis_u2, 3); zr.add(dL_dcov3D, 6); zr.add(dL_dscale, 3); zr.add(dL_drot, 4);
-    lg::launch_zero_touched(geom.touched, reinterpret_cast<float4*>(geom.gacc), 4, (size_t)P, geom.tlist, geom.tcount, zr, stream);
+    lg::launch_zero_touched(geom.touched, reinterpret_cast<float4*>(geom.gacc), 4, (size_t)P, geom.tlist, geom.tcount, zr, stream, det_mode, geom.acc64);
     lg::prof_mark("bwd_zero", stream);
 
     lg::RenderBwdArgs rb;
@@ -686,6 +717,7 @@ int backward_impl(int P, int R, const float* background, int width, int height, 
     rb.T_final_global = mode.T_final_global; rb.behind = mode.behind;
     rb.dL_dpix = dL_dpix; rb.dL_ddepth = dL_dout_depth; rb.dL_docc = dL_dout_occ; rb.gacc = geom.gacc;
     if (L.work_list) rb.walk = lg::work_list(bin);
+    rb.det_mode = det_mode; rb.acc64 = geom.acc64;
     lg::launch_render_backward(rb, stream);
     LG_STAGE_CHECK("render backward");
     lg::prof_mark("render_bwd", stream);
@@ -699,6 +731,7 @@ int backward_impl(int P, int R, const float* background, int width, int height, 
     gb.dL_ddepths = dL_ddepths; gb.dL_dbasis_u1 = dL_dbasis_u1; gb.dL_dbasis_u2 = dL_dbasis_u2;
     gb.dL_dsphere = dL_dsphere_means3D; gb.dL_dmean3D = dL_dmean3D; gb.dL_dcov3D = dL_dcov3D; gb.dL_dscale = dL_dscale;
     gb.dL_drot = dL_drot;
+    gb.det_mode = det_mode; gb.acc64 = geom.acc64;
     lg::launch_gaussian_backward(gb, stream);
     LG_STAGE_CHECK("gaussian backward");
     lg::prof_mark("gaussian_bwd", stream);
@@ -721,10 +754,12 @@ int lidargs_forward(lidargs_alloc_fn geometry_alloc, void* geometry_user, lidarg
                     int* radii, int* radii_xy, int debug, void* stream) {
     (void)D; (void)M; (void)shs; (void)projmatrix; (void)cam_pos; (void)prefiltered;
     const float inf = std::numeric_limits<float>::infinity();
+    FrameMode mode;
+    mode.deterministic = lg::deterministic_env();
     return forward_impl(geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user, P, background, width,
                         height, means3D, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix,
                         beam_inclinations, (float)lidar_near, (float)lidar_far, -inf, inf, nullptr, 0, out_color, out_depth,
-                        out_occ, nullptr, radii, radii_xy, debug, (hipStream_t)stream, FrameMode());
+                        out_occ, nullptr, radii, radii_xy, debug, (hipStream_t)stream, mode);
 }
 
 int lidargs_forward_enqueue(lidargs_alloc_fn geometry_alloc, void* geometry_user, lidargs_alloc_fn binning_alloc, void* binning_user,
@@ -735,6 +770,7 @@ int lidargs_forward_enqueue(lidargs_alloc_fn geometry_alloc, void* geometry_user
                             int prefiltered, int lidar_far, int lidar_near, float* out_color, float* out_depth, float* out_occ,
                             int* radii, int* radii_xy, int debug, int instance_capacity, int tile_rows, unsigned* status_host, void* stream) {
     (void)D; (void)M; (void)shs; (void)projmatrix; (void)cam_pos; (void)prefiltered;
+    if (const int rc = lg::refuse_deterministic("lidargs_forward_enqueue")) return rc;
     if (instance_capacity <= 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward_enqueue: instance_capacity must be positive%s");
     const float inf = std::numeric_limits<float>::infinity();
     FrameMode mode;
@@ -1004,6 +1040,7 @@ int lidargs_forward_shell(lidargs_alloc_fn geometry_alloc, void* geometry_user, 
                           const float* beam_inclinations, int lidar_far, int lidar_near, float shell_lo, float shell_hi,
                           const float* T_in, int transmittance_pass, float* out_color, float* out_depth, float* out_occ,
                           float* T_out, int* radii, int* radii_xy, int debug, void* stream) {
+    if (const int rc = lg::refuse_deterministic("lidargs_forward_shell")) return rc;
     FrameMode mode;
     mode.is_shell = true;
     return forward_impl(geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user, P, background, width,
@@ -1020,6 +1057,7 @@ int lidargs_forward_shell_enqueue(lidargs_alloc_fn geometry_alloc, void* geometr
                                   const float* T_in, int transmittance_pass, float* out_color, float* out_depth, float* out_occ,
                                   float* T_out, int* radii, int* radii_xy, int debug, const unsigned* n_valid, int instance_capacity,
                                   int tile_rows, unsigned* status_host, void* stream) {
+    if (const int rc = lg::refuse_deterministic("lidargs_forward_shell_enqueue")) return rc;
     if (instance_capacity <= 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward_shell_enqueue: instance_capacity must be positive%s");
     FrameMode mode;
     mode.is_shell = true; mode.n_valid = n_valid;
@@ -1037,6 +1075,7 @@ int lidargs_forward_wedge(lidargs_alloc_fn geometry_alloc, void* geometry_user, 
                           float scale_modifier, const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
                           const float* beam_inclinations, int lidar_far, int lidar_near, int col_lo, int col_hi, float* out_color,
                           float* out_depth, float* out_occ, int* radii, int* radii_xy, int debug, void* stream) {
+    if (const int rc = lg::refuse_deterministic("lidargs_forward_wedge")) return rc;
     if (col_lo < 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward_wedge: col_lo < 0%s");
     // lidargs_wedge_select_count bounds a Gaussian's reach from its scales and rotation; a precomputed covariance has no such bound
     // there, and a wedge rendered from an under-selected set would silently miss its boundary Gaussians
@@ -1057,6 +1096,7 @@ int lidargs_forward_wedge_enqueue(lidargs_alloc_fn geometry_alloc, void* geometr
                                   const float* beam_inclinations, int lidar_far, int lidar_near, int col_lo, int col_hi, float* out_color,
                                   float* out_depth, float* out_occ, int* radii, int* radii_xy, int debug, const unsigned* n_valid,
                                   int instance_capacity, int tile_rows, unsigned* status_host, void* stream) {
+    if (const int rc = lg::refuse_deterministic("lidargs_forward_wedge_enqueue")) return rc;
     if (col_lo < 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward_wedge: col_lo < 0%s");
     if (cov3D_precomp) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward_wedge: cov3D_precomp is not supported on the column-wedge path (give scales + rotations)%s");
     if (instance_capacity <= 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward_wedge_enqueue: instance_capacity must be positive%s");

@@ -104,6 +104,10 @@ __device__ __forceinline__ uint2 span_unpack(uint32_t w) {            // -> (xsp
 #define LG_INST_SLOTS 64
 #define LG_TOTALS_SLOT_WORD 8
 // (word 4 of the totals was rounds 2-4's "gradient lines dirty" mark: every backward now clears the touched Gaussians' lines itself)
+// Word 4 now carries the forward's accumulation mode to every backward on the buffer: 0 (the forward's memset) = float atomics,
+// 1 = deterministic (LIDARGS_DETERMINISTIC=1 at the forward: the geometry buffer then ends in GeomView::acc64).  The backward's
+// KERNELS read it; the host never does, so a cloned or offloaded buffer carries its mode along and no backward waits for a read.
+#define LG_TOTALS_MODE_WORD 4
 // behind the status words: LG_INST_SLOTS slots of (~smallest, largest) range key of the frame's visible Gaussians (atomicMax of the
 // preprocess blocks, spread over the slots like the instance totals; all start at 0, so an empty frame reads kmin = 0xFFFFFFFF,
 // kmax = 0).  The host folds them after its one read: the range sort then works on key - kmin and needs only as many passes as the
@@ -133,6 +137,8 @@ struct GeomView {
                                         //     in the region (tlist[region * LG_REGION + j], j < tcount[region]); written by k_zero_touched
     uint32_t* scratch;                  // sort + scan scratch
     size_t scratch_words;
+    long long* acc64;                   // [16P] deterministic mode only (behind everything else, so that the default buffer is byte for byte
+                                        //     what it was): the 64-bit fixed-point twin of a Gaussian's gacc line (det_encode / det_decode)
 };
 
 // What the two rasterizers' buffers differ in: float4s of splat record and floats of gradient line per Gaussian, 64-float planes per
@@ -141,7 +147,9 @@ struct BufferWidths { int rec_f4, gacc_floats, seg_planes; bool work_list; };
 constexpr BufferWidths GAUSS_BUFFERS = {4, 16, LG_SEG_PLANES, true};
 constexpr BufferWidths SURFEL_BUFFERS = {5, 32, 16, false};     // (16: surfel.hip SF_SEG_PLANES, checked there)
 
-inline size_t geom_carve(char* base, size_t P, const BufferWidths& w, GeomView* v) {
+// det: carve GeomView::acc64 as well.  The forward asks for it only in deterministic mode; a backward always computes the address (it does
+// not know the mode) and hands it to kernels that use it only where the buffer's mode word says it is there.
+inline size_t geom_carve(char* base, size_t P, const BufferWidths& w, GeomView* v, bool det = false) {
     Carver c(base);
     GeomView g;
     g.rec = c.take<float4>((size_t)w.rec_f4 * P);
@@ -157,8 +165,10 @@ inline size_t geom_carve(char* base, size_t P, const BufferWidths& w, GeomView* 
     g.tlist = c.take<uint8_t>(P + LG_REGION); g.tcount = c.take<uint16_t>(P / LG_REGION + 64);
     g.scratch_words = sort_scratch_words(P, SORT_MAX_RADIX_BITS) + scan_scratch_words(P);
     g.scratch = c.take<uint32_t>(g.scratch_words);
+    const size_t plain = (size_t)(c.p - base) + 128;
+    g.acc64 = c.take<long long>(16 * P);
     if (v) *v = g;
-    return (size_t)(c.p - base) + 128;
+    return det ? (size_t)(c.p - base) + 128 : plain;
 }
 
 struct BinView {
@@ -321,6 +331,8 @@ void lane_stats_read(unsigned long long* out, int reset);              // render
 // helpers exported by api.hip for the other entry-point files
 int api_fail(int code, const char* msg);
 int api_check_launch(hipStream_t s, int debug, const char* what);
+bool deterministic_env();                       // LIDARGS_DETERMINISTIC=1, read at every call
+int refuse_deterministic(const char* entry);    // 0, or LIDARGS_ERR_INVALID_ARGUMENT (message set) when the switch is on: entry points the mode does not cover
 // Device -> host read of `n` (<= 1024) words with `zero_bytes` at `zero` cleared BEHIND the copy on the same stream: the host waits
 // for the copy only.  Returns a hipError_t.
 int api_read_words_zero_behind(const uint32_t* dev, int n, uint32_t* out, void* zero, size_t zero_bytes, hipStream_t s);
@@ -362,7 +374,9 @@ int bin_frame(const BinSpec& spec, const GeomView& geom, uint2* ranges, size_t P
 // lists the touched Gaussians per region (tlist / tcount of the geometry view) and zeroes every row of the caller's gradient arrays.
 struct ZeroRows { static constexpr int MAX = 12; float* p[MAX]; int w[MAX]; int n = 0;   // arrays of P rows of w floats (w = 1, 2, 3, 4, 6 or 9)
                   void add(float* q, int width) { if (q && n < MAX) { p[n] = q; w[n] = width; n++; } } };
-void launch_zero_touched(const uint8_t* touched, float4* acc, int line_f4, size_t P, uint8_t* tlist, uint16_t* tcount, const ZeroRows& zr, hipStream_t s);
+// det_mode / acc64 (optional): where *det_mode != 0 the touched Gaussians' 128-byte fixed-point lines are cleared as well
+void launch_zero_touched(const uint8_t* touched, float4* acc, int line_f4, size_t P, uint8_t* tlist, uint16_t* tcount, const ZeroRows& zr, hipStream_t s,
+                         const uint32_t* det_mode = nullptr, long long* acc64 = nullptr);
 // touched[i] = 1 for all P (frames whose forward writes no contribution flags: every listed entry is walked, so every visible Gaussian counts)
 void launch_touch_all(uint8_t* touched, const int* radii, size_t P, hipStream_t s);   // marks the Gaussians with radii > 0
 
@@ -530,7 +544,12 @@ struct RenderBwdArgs {
     float* gacc;                   // [16P], zeroed: slots 0-2 mean2D.xyz, 3-5 conic A,B,C, 6 opacity, 7-8 colour,
                                    //               9 range, 10-12 G1 = sum gx delta, 13-15 G2 = sum gy delta (moments of dL/du1, dL/du2)
     WorkList walk;                 // the list k_render_combine filled; cnt == nullptr: the slot grid
+    const uint32_t* det_mode = nullptr;   // the buffer's mode word (LG_TOTALS_MODE_WORD), nullptr = float atomics whatever it says
+    long long* acc64 = nullptr;           // [16P] GeomView::acc64, touched only where *det_mode != 0
 };
+// det_mode == nullptr: one launch, float atomics.  Otherwise the walk is launched in the form that asks the mode word, and a second
+// launch follows, which retires on one scalar load unless the buffer is a deterministic forward's: there the first walk leaves
+// max |term| per (Gaussian, slot) in gacc, the second adds the terms up as 64-bit integers on the grid that maximum fixes (det_encode).
 void launch_render_backward(const RenderBwdArgs& a, hipStream_t s);
 void launch_count_backward_entries(const RenderBwdArgs& a, unsigned long long* out, hipStream_t s);   // diagnostics: adds the list entries k_render_backward gathers to *out
 // diagnostics of a forward (lidargs_last_counters): host-side counters; with lidargs_counters_enable(1) also queues the counting launches.
@@ -546,6 +565,7 @@ struct GaussBwdArgs {
     float* dL_dmean2D; float* dL_dconic; float* dL_dopacity; float* dL_dcolor; float* dL_ddepths;
     float* dL_dbasis_u1; float* dL_dbasis_u2;
     float* dL_dsphere; float* dL_dmean3D; float* dL_dcov3D; float* dL_dscale; float* dL_drot;
+    const uint32_t* det_mode = nullptr; const long long* acc64 = nullptr;   // as in RenderBwdArgs: where *det_mode != 0 a line is det_decode(gacc, acc64)
 };
 void launch_gaussian_backward(const GaussBwdArgs& a, hipStream_t s);
 
@@ -573,6 +593,36 @@ __device__ __forceinline__ float4 get4(const float* p, size_t i) { const float f
 __device__ __forceinline__ float3 get3(const float* p, size_t i) { const row3 v = *reinterpret_cast<const row3*>(p + 3 * i); return make_float3(v.x, v.y, v.z); }
 __device__ __forceinline__ float4 get4(const float* p, size_t i) { const row4 v = *reinterpret_cast<const row4*>(p + 4 * i); return make_float4(v.x, v.y, v.z, v.w); }
 #endif
+
+// ---- deterministic accumulation across workgroups (LIDARGS_DETERMINISTIC=1; DESIGN.md "Deterministic backward") ------
+// A (Gaussian, slot) sum is formed by two walks over the same wave-reduced terms t.
+//   walk 1: top = max |t| as a bit pattern, with an integer atomicMax into the slot of the float line (order-independent);
+//   walk 2: q = t / unit rounded to the nearest integer, unit = 2^(e - 165), e = max(biased exponent of top, 1), added with a 64-bit
+//           integer atomic (associative, so order-independent).  |t| < 2^(e - 126) makes |q| < 2^39: 2^23 (8.4 M) terms stay below 2^62.
+//           A term up to 15 binades below the largest is carried exactly (24 + 15 = 39 bits), a smaller one to 2^-39 of the largest.
+//   k_gaussian_backward reads the sum back as float(acc * unit): one rounding of an otherwise exact sum.
+// A non-finite term makes top >= 0x7f800000; the 64-bit slot then collects three class bits with atomicOr (1 = +inf, 2 = -inf, 4 = NaN
+// seen) and decodes to what a float sum of those terms gives in any order.
+__device__ __forceinline__ bool det_finite(uint32_t top) { return top < 0x7f800000u; }
+__device__ __forceinline__ double det_unit(uint32_t top, bool inverse) {
+    const int e = max((int)(top >> 23), 1);                            // (top carries no sign bit)
+    const int k = inverse ? 165 - e : e - 165;                         // -164 .. 164: a normal double
+    return __longlong_as_double((long long)(1023 + k) << 52);
+}
+__device__ __forceinline__ unsigned long long det_encode(float t, uint32_t top) {
+    if (det_finite(top)) return (unsigned long long)__double2ll_rn((double)t * det_unit(top, true));   // (the product is exact)
+    return t != t ? 4ull : (t == INFINITY ? 1ull : (t == -INFINITY ? 2ull : 0ull));
+}
+__device__ __forceinline__ void det_add(long long* dst, float t, uint32_t top) {
+    const unsigned long long q = det_encode(t, top);
+    if (det_finite(top)) atomicAdd(reinterpret_cast<unsigned long long*>(dst), q);
+    else if (q) atomicOr(reinterpret_cast<unsigned long long*>(dst), q);
+}
+__device__ __forceinline__ float det_decode(uint32_t top, long long acc) {
+    if (det_finite(top)) return (float)((double)acc * det_unit(top, false));
+    if ((acc & 4) || (acc & 3) == 3) return __uint_as_float(0x7fc00000u);
+    return (acc & 1) ? INFINITY : -INFINITY;
+}
 
 // LDS reads that stay where they are written (see walk_flagged in render.hip)
 typedef float v4f __attribute__((ext_vector_type(4)));

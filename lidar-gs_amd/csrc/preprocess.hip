@@ -455,8 +455,19 @@ __device__ __forceinline__ void gb_row(const GaussBwdArgs& a, const int idx) {
     const float ff = (float)(idx & 255);
     const float4 q0 = make_float4(ff, 1.f, 2.f, ff), q1 = q0, q2 = q0, q3 = q0;
 #else
-    const float4 q0 = acc[0], q1 = acc[1], q2 = acc[2], q3 = acc[3];
+    float4 q0 = acc[0], q1 = acc[1], q2 = acc[2], q3 = acc[3];
 #endif
+    if (a.det_mode && *a.det_mode != 0u) {
+        // deterministic buffers (lidargs_common.h "deterministic accumulation"): the float line holds each slot's largest term, the
+        // sums are the 64-bit line's, read on the grid that term fixes
+        const longlong2* w = reinterpret_cast<const longlong2*>(a.acc64 + 16 * (size_t)idx);
+        auto line = [&](float4& q, int k) {
+            const longlong2 lo = w[2 * k], hi = w[2 * k + 1];
+            q = make_float4(det_decode(__float_as_uint(q.x), lo.x), det_decode(__float_as_uint(q.y), lo.y),
+                            det_decode(__float_as_uint(q.z), hi.x), det_decode(__float_as_uint(q.w), hi.y));
+        };
+        line(q0, 0); line(q1, 1); line(q2, 2); line(q3, 3);
+    }
     const bool have_sr = (a.cov3D_precomp == nullptr);
     float3 s_in = f3(0, 0, 0); float4 q = make_float4(1, 0, 0, 0);
     float3 cv0 = f3(0, 0, 0), cv1 = f3(0, 0, 0);
@@ -627,7 +638,8 @@ __global__ void __launch_bounds__(256) k_gaussian_backward(const GaussBwdArgs a)
 //     written lines behind for the touched rows to complete later: 95 us against 75 in the micro-benchmark.)
 template <int LINE>
 __global__ void __launch_bounds__(LG_REGION) k_zero_touched(const uint8_t* __restrict__ touched, float4* __restrict__ acc, size_t P,
-                                                           uint8_t* __restrict__ tlist, uint16_t* __restrict__ tcount, const ZeroRows zr) {
+                                                           uint8_t* __restrict__ tlist, uint16_t* __restrict__ tcount, const ZeroRows zr,
+                                                           const uint32_t* __restrict__ det_mode, long long* __restrict__ acc64) {
     __shared__ uint32_t s_wcnt[LG_REGION / 64];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const size_t base = (size_t)blockIdx.x * LG_REGION;
@@ -655,6 +667,11 @@ __global__ void __launch_bounds__(LG_REGION) k_zero_touched(const uint8_t* __res
             if (mine >= 0) acc[(wbase + (size_t)mine) * LINE + part] = z;
         }
     }
+    if (det_mode && *det_mode != 0u && mark) {                         // deterministic buffers: the marked Gaussians' 128-byte fixed-point lines too
+        float4* const w = reinterpret_cast<float4*>(acc64 + 16 * i);
+#pragma unroll
+        for (int k = 0; k < 8; k++) w[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
     if (i < P) {
         for (int k = 0; k < zr.n; k++) {                               // (wave-uniform: the pointers and widths are scalar loads from the arguments)
             float* q = zr.p[k];
@@ -675,11 +692,12 @@ __global__ void __launch_bounds__(LG_REGION) k_zero_touched(const uint8_t* __res
     if (mark) tlist[base + off + (uint32_t)__popcll(m0 & ((1ull << lane) - 1ull))] = (uint8_t)tid;
     if (tid == 0) tcount[blockIdx.x] = (uint16_t)total;
 }
-void launch_zero_touched(const uint8_t* touched, float4* acc, int line_f4, size_t P, uint8_t* tlist, uint16_t* tcount, const ZeroRows& zr, hipStream_t s) {
+void launch_zero_touched(const uint8_t* touched, float4* acc, int line_f4, size_t P, uint8_t* tlist, uint16_t* tcount, const ZeroRows& zr, hipStream_t s,
+                         const uint32_t* det_mode, long long* acc64) {
     const unsigned blocks = (unsigned)((P + LG_REGION - 1) / LG_REGION);
     if (!blocks) return;
-    if (line_f4 == 8) hipLaunchKernelGGL(k_zero_touched<8>, dim3(blocks), dim3(LG_REGION), 0, s, touched, acc, P, tlist, tcount, zr);
-    else hipLaunchKernelGGL(k_zero_touched<4>, dim3(blocks), dim3(LG_REGION), 0, s, touched, acc, P, tlist, tcount, zr);
+    if (line_f4 == 8) hipLaunchKernelGGL(k_zero_touched<8>, dim3(blocks), dim3(LG_REGION), 0, s, touched, acc, P, tlist, tcount, zr, det_mode, acc64);
+    else hipLaunchKernelGGL(k_zero_touched<4>, dim3(blocks), dim3(LG_REGION), 0, s, touched, acc, P, tlist, tcount, zr, det_mode, acc64);
 }
 // the one-segment plan has no contribution flags: every VISIBLE Gaussian may be added to.  The culled ones stay unmarked -- their rows
 // must be the exact zeros the reference's torch::zeros leaves (the chain on zero sums would turn a huge or non-finite scale into 0 * inf)

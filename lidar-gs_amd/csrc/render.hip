@@ -1006,32 +1006,45 @@ __device__ __forceinline__ float reduce_scatter16(float (&v)[16], int lane) {
 // slot cnt-1 (or cnt, a zero record, when cnt is odd) down in pairs: a counted loop, the entry's position and Gaussian id riding in LDS
 // -- no find-last-set / clear / compare / clamp on a 64-bit scalar mask per entry (~10 scalar instructions of the ~45 a visited entry
 // that contributes nothing costs).  The arithmetic per entry is the first form's, in the same order.
-template <bool V2>
-#ifdef LG_BWD_WAVES      /* experiment (tools/waves_ab.sh): force the register budget of N waves per SIMD */
-__attribute__((amdgpu_waves_per_eu(LG_BWD_WAVES, LG_BWD_WAVES)))
-#endif
-__global__ void __launch_bounds__(64) k_render_backward(const RenderBwdArgs a) {
+//
+// The walk of workgroup slot `bid`.  What happens to an entry's sixteen wave-reduced sums depends on the mode of the forward that made the
+// buffers (lidargs_common.h LG_TOTALS_MODE_WORD, "deterministic accumulation"):
+//   BWD_PLAIN                float atomicAdd into the Gaussian's line: the default, and the only form a process launches until one of its
+//                            forwards has made deterministic buffers (api.hip g_deterministic_seen)
+//   BWD_FIRST, det = false   the same, the mode word having said so
+//   BWD_FIRST, det = true    integer atomicMax of |sum|'s bits into the same slot: the line ends as the largest term per slot
+//   BWD_SECOND               the second walk of the deterministic mode: the sums go onto the grid the largest term fixes and are
+//                            added to the 64-bit line (det_add).  A chunk's sixteen maxima per entry are fetched into LDS behind its
+//                            records (4 KB beside s_rec / s_oprow: 16 workgroups per CU still fit), so that no entry waits for memory.
+// The arithmetic in front of the atomic is the same text in all of them, and every (patch, segment) walk is one wave: the second walk's
+// terms are the same numbers in whatever order the workgroups run.
+enum { BWD_PLAIN = 0, BWD_FIRST = 1, BWD_SECOND = 2 };
+template <bool V2, int MODE>
+__device__ __forceinline__ void backward_walk(const RenderBwdArgs& a, const unsigned bid, const bool det) {
+    constexpr bool SECOND = MODE == BWD_SECOND;
     constexpr int OFS = V2 ? 2 : 0;                                    // slack slots below slot 0 (V2's look-ahead reads)
     __shared__ float4 s_rec_[4 * (LG_CHUNK + OFS)];
     __shared__ float4 s_oprow_[LG_CHUNK + OFS];                        // opacity per pixel row of the patch, 0 outside the entry's row span
     __shared__ uint32_t s_gid_[LG_CHUNK + OFS];
+    __shared__ uint32_t s_top_[SECOND ? 16 * (LG_CHUNK + OFS) : 1];    // SECOND: max |term| per (parked entry, slot), as bits
     constexpr int CS = LG_CHUNK + OFS;                                 // component stride of s_rec
     float4* const s_rec = s_rec_ + OFS;
     float4* const s_oprow = s_oprow_ + OFS;
     uint32_t* const s_gid = s_gid_ + OFS;
+    uint32_t* const s_top = s_top_ + (SECOND ? 16 * OFS : 0);
     const int lane = threadIdx.x;
     const int S = a.S;
     const int wpt = a.grid.waves_per_tile;
     int patch, seg;
     if (a.walk.cnt) {
-        // item blockIdx / R of region blockIdx % R of the list k_render_combine filled (lidargs_common.h WorkList); the workgroups behind a
+        // item bid / R of region bid % R of the list k_render_combine filled (lidargs_common.h WorkList); the workgroups behind a
         // region's count -- the tail of the grid -- leave on one scalar load
-        const unsigned r = blockIdx.x % LG_WORK_REGIONS, i = blockIdx.x / LG_WORK_REGIONS;
+        const unsigned r = bid % LG_WORK_REGIONS, i = bid / LG_WORK_REGIONS;
         if (i >= a.walk.cnt[r * LG_WORK_CNT_STRIDE]) return;
         const uint32_t it = a.walk.items[(size_t)r * a.walk.cap + i];
         patch = (int)(it >> 8); seg = (int)(it & 255u);
     } else {
-        if (!block_patch_segment(blockIdx.x, a.grid.window_patches(), S, patch, seg)) return;
+        if (!block_patch_segment(bid, a.grid.window_patches(), S, patch, seg)) return;
         patch = a.grid.global_patch(patch);
     }
     const int tile = patch / wpt, sub = patch - tile * wpt;
@@ -1098,7 +1111,8 @@ __global__ void __launch_bounds__(64) k_render_backward(const RenderBwdArgs a) {
     }
     float last_alpha = 0.f;
     v2f lc01 = v2f{0.f, 0.f}, ldo = v2f{0.f, 1.f};                    // last entry's (colour0, colour1) | (range, 1)
-    float* const gacc_slot = a.gacc + (8 * ((lane >> 5) & 1) + 4 * ((lane >> 4) & 1) + 2 * (lane & 1) + ((lane >> 1) & 1));   // this lane's slot of a Gaussian's packed line (reduce_scatter16)
+    const int top_slot = 8 * ((lane >> 5) & 1) + 4 * ((lane >> 4) & 1) + 2 * (lane & 1) + ((lane >> 1) & 1);
+    float* const gacc_slot = a.gacc + top_slot;                       // this lane's slot of a Gaussian's packed line (reduce_scatter16)
 
     const int y0 = (tile / a.grid.tiles_x) * a.grid.TH + sub * LG_WAVE_ROWS;       // first pixel row of the patch
     const float* oprow = reinterpret_cast<const float*>(s_oprow) + (lane >> 4);
@@ -1132,11 +1146,21 @@ __global__ void __launch_bounds__(64) k_render_backward(const RenderBwdArgs a) {
         __syncthreads();
         if (c > 0) gather(c - 1, st, gid, have);
         if (todo == 0ull) continue;
+        if (SECOND) {
+            // the parked entries' lines of maxima, a 64-byte line per sixteen lanes (an unflagged slot parks Gaussian 0: a valid line, never used)
+#pragma unroll 4
+            for (int k = 0; k < LG_CHUNK / 4; k++) {
+                const int jj = 4 * k + (lane >> 4);
+                s_top[16 * jj + (lane & 15)] = __float_as_uint(a.gacc[16 * (size_t)s_gid[jj] + (lane & 15)]);
+            }
+            __syncthreads();
+        }
         // back to front, software-pipelined like the forward walk (walk_flagged): two register sets, unconditional look-ahead reads
-        struct Rec { float4 r0, r1, r2, r3; float op; uint32_t gid; };
+        struct Rec { float4 r0, r1, r2, r3; float op; uint32_t gid; uint32_t top; };
         auto read = [&](int jj) {
             Rec r;
-            r.gid = lds_ahead(&s_gid[jj]);                             // with the look-ahead reads: fetched where the atomic needs it, the owners waited out an LDS round trip per entry
+            r.top = SECOND ? lds_ahead(&s_top[16 * jj + top_slot]) : 0u;
+            r.gid = lds_ahead(&s_gid[jj]);                            // with the look-ahead reads: fetched where the atomic needs it, the owners waited out an LDS round trip per entry
             const float* f3 = reinterpret_cast<const float*>(&s_rec[3 * CS + jj]);
             const float4 s0 = lds_ahead(&s_rec[jj]);                   // s.xyz | B  (park_record)
             r.r1 = lds_ahead(&s_rec[CS + jj]); r.r2 = lds_ahead(&s_rec[2 * CS + jj]);
@@ -1218,7 +1242,11 @@ __global__ void __launch_bounds__(64) k_render_backward(const RenderBwdArgs a) {
                 // (the slot's address before the reduction, in every lane: independent work for the wait states between its dependent DPP steps)
                 float* const dst = gacc_slot + 16 * (size_t)r.gid;
                 const float mine = reduce_scatter16(v, lane);
-                if ((lane & 12) == 0) atomicAdd(dst, mine);             // one owner per slot
+                if (SECOND) {
+                    if ((lane & 12) == 0) det_add(a.acc64 + (dst - a.gacc), mine, r.top);
+                } else if (MODE == BWD_FIRST && det) {                 // (wave-uniform, a scalar of the launch)
+                    if ((lane & 12) == 0) atomicMax(reinterpret_cast<uint32_t*>(dst), __float_as_uint(mine) & 0x7fffffffu);
+                } else if ((lane & 12) == 0) atomicAdd(dst, mine);      // one owner per slot
             }
         };
         if (V2) {
@@ -1251,6 +1279,30 @@ __global__ void __launch_bounds__(64) k_render_backward(const RenderBwdArgs a) {
             if (!more_a) break;
         }
     }
+}
+
+template <bool V2>
+#ifdef LG_BWD_WAVES      /* experiment (tools/waves_ab.sh): force the register budget of N waves per SIMD */
+__attribute__((amdgpu_waves_per_eu(LG_BWD_WAVES, LG_BWD_WAVES)))
+#endif
+__global__ void __launch_bounds__(64) k_render_backward(const RenderBwdArgs a) {
+    backward_walk<V2, BWD_PLAIN>(a, blockIdx.x, false);
+}
+// the first walk on buffers that may be deterministic: their mode word decides what the sums are combined with
+template <bool V2>
+__global__ void __launch_bounds__(64) k_render_backward_first(const RenderBwdArgs a) {
+    const bool det = *a.det_mode != 0u;                                // (a scalar load, needed at the first entry's atomic)
+    backward_walk<V2, BWD_FIRST>(a, blockIdx.x, det);
+}
+
+// The deterministic mode's second walk.  The host does not know the buffers' mode (it travels in them), so this is launched behind every
+// first walk that passes a mode word: a fixed, small grid whose workgroups retire on one scalar load in the default mode and otherwise
+// take the `slots` workgroup slots of the first launch in strides.  Which workgroup walks which slot, and when, does not matter to the sums.
+#define LG_DET_GRID 4096                 // 16 single-wave workgroups per CU (what the 9.7 KB of LDS admit) on 256 CUs
+template <bool V2>
+__global__ void __launch_bounds__(64) k_render_backward_det(const RenderBwdArgs a, const unsigned slots) {
+    if (*a.det_mode == 0u) return;
+    for (unsigned bid = blockIdx.x; bid < slots; bid += gridDim.x) backward_walk<V2, BWD_SECOND>(a, bid, true);
 }
 
 // Diagnostics (lidargs_counters_enable + lidargs_last_counters, outside any timed region): the list entries k_render_backward gathers for a frame -- per (patch,
@@ -1286,8 +1338,17 @@ void launch_count_backward_entries(const RenderBwdArgs& a, unsigned long long* o
 
 void launch_render_backward(const RenderBwdArgs& a, hipStream_t s) {
     const unsigned blocks = a.walk.cnt ? (unsigned)LG_WORK_REGIONS * a.walk.cap : segment_grid(a.grid.window_patches(), a.S);
-    if (walk2() & 4) hipLaunchKernelGGL(k_render_backward<true>, dim3(blocks), dim3(64), 0, s, a);
-    else hipLaunchKernelGGL(k_render_backward<false>, dim3(blocks), dim3(64), 0, s, a);
+    if (!a.det_mode) {
+        if (walk2() & 4) hipLaunchKernelGGL(k_render_backward<true>, dim3(blocks), dim3(64), 0, s, a);
+        else hipLaunchKernelGGL(k_render_backward<false>, dim3(blocks), dim3(64), 0, s, a);
+        return;
+    }
+    if (!blocks) return;
+    if (walk2() & 4) hipLaunchKernelGGL(k_render_backward_first<true>, dim3(blocks), dim3(64), 0, s, a);
+    else hipLaunchKernelGGL(k_render_backward_first<false>, dim3(blocks), dim3(64), 0, s, a);
+    const unsigned grid = blocks < (unsigned)LG_DET_GRID ? blocks : (unsigned)LG_DET_GRID;
+    if (walk2() & 4) hipLaunchKernelGGL(k_render_backward_det<true>, dim3(grid), dim3(64), 0, s, a, blocks);
+    else hipLaunchKernelGGL(k_render_backward_det<false>, dim3(grid), dim3(64), 0, s, a, blocks);
 }
 
 }  // namespace lg
