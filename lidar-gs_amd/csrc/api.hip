@@ -16,7 +16,6 @@
 
 #include <math.h>
 #include <stdio.h>
-#include <stdlib.h>
 #include <string.h>
 #include <limits>
 #include <algorithm>
@@ -112,23 +111,13 @@ int check_launch(hipStream_t s, int debug, const char* what) {
         if (rc_) return rc_;                                  \
     } while (0)
 
-// LIDARGS_TILE_ROWS forces the list-tile height (4, 8, 16 or 32 pixel rows); unset = chosen per frame (choose_tile_rows).
-int forced_tile_rows() {
-    static int th = [] {
-        const char* e = getenv("LIDARGS_TILE_ROWS");
-        const int v = e ? atoi(e) : 0;
-        return (v == 4 || v == 8 || v == 16 || v == 32) ? v : 0;
-    }();
-    return th;
-}
-
 // Tile height from the instance totals the preprocess accumulated for heights 4 / 8 / 16 / 32.  The blend costs the same for every
 // height (per-lane row test + contribution flags), the binning costs ~18 ns per 1000 instances, and a taller tile makes pass 1
 // visit entries that do not reach a patch's rows.  Measured: street scenes (instances shrink 1.27x / 1.46x at 8 / 16 rows) are
 // fastest at 4 rows, an 8 M-Gaussian shell scene with tall footprints (1.74x / 2.77x) at 16 (4.5 -> 3.0 ms) and, its instances
 // shrinking another 1.5x, at 32 (2.52 -> 2.33 ms: binning 0.53 -> 0.34 ms against 0.05 ms more in pass 1).
 int choose_tile_rows(const unsigned long long (&inst)[4], int height) {
-    if (const int f = forced_tile_rows()) return f;
+    if (const int f = lg::switches().tile_rows) return f;
     const double r4 = (double)inst[0];
     if (inst[2] > 0 && r4 / (double)inst[2] >= 2.2) {
         if (height >= 64 && inst[3] > 0 && (double)inst[2] / (double)inst[3] >= 1.4) return 32;
@@ -175,23 +164,8 @@ thread_local HostRead t_host_read;
 //   blend latency-bound at ~2 waves per SIMD (SQ_WAVE_CYCLES), so the lists are cut finer: 64-entry segments, 45 slots, a first
 //   round of 5 segments (cfg3 0.99 -> 0.93 ms).  Frames with plenty of segments (8 M Gaussians at 128x4096) lose 10 % that way
 //   and keep 128 / 33 / 3.  The surfel blend does twice the arithmetic per entry and sits in between: 96 / 45 / 6.
-//   LIDARGS_SEG_LEN, LIDARGS_MAX_SEGMENTS, LIDARGS_ROUNDS ("3,9") override.
 SegPlan plan_segments(size_t R, int waves_per_tile, int surfel, size_t patches = 0) {
-    static const int env_len = [] { const char* e = getenv("LIDARGS_SEG_LEN"); return e ? std::max(64, atoi(e)) : 0; }();
-    static const int env_max = [] { const char* e = getenv("LIDARGS_MAX_SEGMENTS"); return e ? std::min(63, std::max(1, atoi(e))) | 1 : 0; }();
-    static int env_rounds[8];
-    static const int env_nrounds = [] {
-        const char* e = getenv("LIDARGS_ROUNDS");
-        if (!e) return -1;
-        int n = 0, prev = 0;
-        while (*e && n < 8) {
-            const int v = atoi(e);
-            if (v > prev && v < 255) { env_rounds[n++] = v; prev = v; }
-            while (*e && *e != ',') e++;
-            if (*e == ',') e++;
-        }
-        return n;
-    }();
+    const lg::Switches& env = lg::switches();
     SegPlan p;
     const bool fine = (unsigned long long)R * (unsigned)waves_per_tile / 128ull < 150000ull;
     p.seg_len = fine ? 64 : LG_SEG_LEN_DEFAULT;   // (the surfel variant took 96 until its walks got a fifth cheaper: round 4's end, 64 / 8 segments beat 96 / 6 by 1.5 %)
@@ -208,22 +182,21 @@ SegPlan plan_segments(size_t R, int waves_per_tile, int surfel, size_t patches =
     // the 64x2650 frames a workgroup per patch walking 5 segments in a row is 2.6 waves per SIMD of serial work: 2 M Gaussians lose
     // 0.09 ms, 0.5 M are even; heads of 1 or 2 segments there lose 0.03-0.04 ms to the extra launches (r02 measurements).
     p.head = (fine || surfel) ? 0 : 1;
-    { static const int env_head = [] { const char* e = getenv("LIDARGS_HEAD"); return e ? atoi(e) : -1; }(); if (env_head >= 0 && !surfel) p.head = env_head ? 1 : 0; }
+    if (env.head >= 0 && !surfel) p.head = env.head ? 1 : 0;
     // Small frames (<= 1 M instances: per-rank sub-frames of a sharded scene, small scenes) run the fine plan's forward blend as ONE
     // launch, a workgroup of 8 waves per patch walking the list in rounds of 8 segments (render.hip k_render_fused): the records are
     // gathered once instead of 2-3 times, there are no workgroups that only read a range and retire, and five launches become one.
     // Measured (r03): 0.17 M instances 0.095 -> 0.057 ms, 0.7 M 0.137 -> 0.114 ms; at 1.3 M (0.165 -> 0.196 ms) and 5.7 M
     // (0.195 -> 0.252 ms) the few long unsaturated lists, walked round after round by one workgroup, are a tail the multi-launch
     // form does not have.  The two forms produce bit-identical images.  LIDARGS_FUSED = 0 / 1 forces one of them.
-    { static const int env_fused = [] { const char* e = getenv("LIDARGS_FUSED"); return e ? atoi(e) : -1; }();
-      // ... and short lists (<= 600 instances per patch the launch covers on average): a column wedge of a sharded frame has few
-      // instances but the single-GPU frame's long lists, and its 300-odd patches leave nothing to hide the long ones' rounds behind
-      // (8 wedges of the 2 M frame: kernel stages 0.41 -> 0.47 ms per rank with the fused form, r03 replay)
-      p.fused = (fine && !surfel && R <= (size_t)1000000 && (patches == 0 || R <= 600 * patches)) ? 1 : 0;
-      if (env_fused >= 0 && !surfel) p.fused = env_fused ? 1 : 0; }
-    if (env_len) p.seg_len = env_len;
-    if (env_max) p.max_segments = env_max;
-    if (env_nrounds >= 0) { p.n_rounds = env_nrounds; for (int k = 0; k < env_nrounds; k++) p.rounds[k] = env_rounds[k]; }
+    // ... and short lists (<= 600 instances per patch the launch covers on average): a column wedge of a sharded frame has few
+    // instances but the single-GPU frame's long lists, and its 300-odd patches leave nothing to hide the long ones' rounds behind
+    // (8 wedges of the 2 M frame: kernel stages 0.41 -> 0.47 ms per rank with the fused form, r03 replay)
+    p.fused = (fine && !surfel && R <= (size_t)1000000 && (patches == 0 || R <= 600 * patches)) ? 1 : 0;
+    if (env.fused >= 0 && !surfel) p.fused = env.fused ? 1 : 0;
+    if (env.seg_len) p.seg_len = env.seg_len;
+    if (env.max_segments) p.max_segments = env.max_segments;
+    if (env.n_rounds >= 0) { p.n_rounds = env.n_rounds; for (int k = 0; k < env.n_rounds; k++) p.rounds[k] = env.rounds[k]; }
     return p;
 }
 
@@ -258,11 +231,6 @@ void run_pass1_rounds(lg::RenderFwdArgs& ra, const SegPlan& plan, uint8_t* alive
     ra.seg_lo = 0; ra.seg_hi = S;
 }
 
-// digit width of the range sort of the P Gaussians: LIDARGS_RANGE_SORT_BITS = 8 (4 passes over the 31 key bits) .. 11 (3 passes)
-int range_sort_bits() {
-    static const int b = [] { const char* e = getenv("LIDARGS_RANGE_SORT_BITS"); const int v = e ? atoi(e) : 8; return (v >= 8 && v <= lg::SORT_MAX_RADIX_BITS) ? v : 8; }();
-    return b;
-}
 int ceil_log2(uint32_t n) {
     int b = 0;
     while ((1u << b) < n && b < 31) b++;
@@ -302,13 +270,6 @@ Profiler g_prof;   // process-wide: autograd runs backward on its own thread
 namespace lg {
 int api_fail(int code, const char* msg) { return fail(code, "%s", msg); }
 int api_check_launch(hipStream_t s, int debug, const char* what) { return check_launch(s, debug, what); }
-// LIDARGS_DETERMINISTIC=1: a supported mode, not a diagnostic -- lidargs_forward makes buffers on which every lidargs_backward is a
-// pure function of its inputs (lidargs_common.h "deterministic accumulation").  Read at EVERY call (a caller may flip it between two
-// frames of one process), and by forward entry points only: a backward takes the mode from the buffers.
-bool deterministic_env() {
-    const char* e = getenv("LIDARGS_DETERMINISTIC");
-    return e && *e && atoi(e) != 0;
-}
 // Has ANY forward of this process made deterministic buffers?  Until one has, no buffer a backward of this process can be handed is
 // deterministic, and backward_impl neither queues the second walk nor hands its kernels the mode word: the default mode then runs
 // exactly the launches it ran before the mode existed.  Not per-forward state (it is never cleared, names no buffer and decides no
@@ -317,7 +278,7 @@ std::atomic<bool> g_deterministic_seen{false};
 // The forwards the mode does not cover yet refuse it, before any device work: running their float-atomic backward under a switch that
 // promises the opposite would be worse than an error.
 int refuse_deterministic(const char* entry) {
-    if (!deterministic_env()) return 0;
+    if (!deterministic_requested()) return 0;
     return fail(LIDARGS_ERR_INVALID_ARGUMENT, "%s: LIDARGS_DETERMINISTIC=1 is not supported by this entry point (only lidargs_forward / lidargs_backward are); unset it for this call", entry);
 }
 int api_read_words_zero_behind(const uint32_t* dev, int n, uint32_t* out, void* zero, size_t zero_bytes, hipStream_t s) {
@@ -325,13 +286,8 @@ int api_read_words_zero_behind(const uint32_t* dev, int n, uint32_t* out, void* 
     if (e == hipSuccess && zero && zero_bytes) e = hipMemsetAsync(zero, 0, zero_bytes, s);
     return e == hipSuccess ? read_words_end(n, out) : (int)e;
 }
-// LIDARGS_NO_PRUNE=1 switches the conservative footprint pruning of the preprocess off (every tile / row of the reference rect is binned):
-// a diagnostic and a test instrument -- pruned entries are exactly those no pixel can take, so the results must not change.
-bool prune_footprints() {
-    static const bool on = [] { const char* e = getenv("LIDARGS_NO_PRUNE"); return !(e && atoi(e) != 0); }();
-    return on;
-}
-int tile_rows() { return forced_tile_rows() ? forced_tile_rows() : 4; }      // what non-adaptive callers (surfel variant) use
+bool prune_footprints() { return !switches().no_prune; }
+int tile_rows() { return switches().tile_rows ? switches().tile_rows : 4; }      // what non-adaptive callers (surfel variant) use
 
 FrameLayout frame_layout(int num_rendered, int W, int H, int col_lo, int col_hi, FrameVariant variant) {
     const bool surfel = variant == FRAME_SURFEL, shell = variant == FRAME_SHELL;
@@ -348,8 +304,7 @@ FrameLayout frame_layout(int num_rendered, int W, int H, int col_lo, int col_hi,
     L.flags = L.fused || L.S > 1 || shell || surfel;      // a shell's backward always reads the flags; the surfel forward always runs pass 1
     // The backward blend walks the work list k_render_combine filled (lidargs_common.h WorkList) on every plain or column-wedge frame that
     // runs the segmented launches (a shell's backward keeps the slot grid).  LIDARGS_WORK_LISTS=0: the slot grid again (A/B, tests).
-    static const bool lists = [] { const char* e = getenv("LIDARGS_WORK_LISTS"); return !e || atoi(e) != 0; }();
-    L.work_list = lists && !surfel && !shell && work_lists_fit(L.patches, L.S) && !L.fused && L.S > 1;
+    L.work_list = switches().work_lists && !surfel && !shell && work_lists_fit(L.patches, L.S) && !L.fused && L.S > 1;
     L.buf = surfel ? SURFEL_BUFFERS : GAUSS_BUFFERS;
     return L;
 }
@@ -400,7 +355,7 @@ int bin_frame(const BinSpec& spec, const GeomView& geom, uint2* ranges, size_t P
         LG_STAGE_CHECK("range sort");
     } else if (enqueue_only) {                                         // no host read: all 31 bits of the raw key
         const int side = launch_radix_sort_pairs(geom.key_a, geom.key_b, geom.id_a, geom.id_b, P, 31, geom.scratch, stream,
-                                                 range_sort_bits(), nullptr, SORT_MAX_RADIX_BITS, true, span_tail);   // (scratch carved for 11-bit digits; ids = positions)
+                                                 switches().range_sort_bits, nullptr, SORT_MAX_RADIX_BITS, true, span_tail);   // (scratch carved for 11-bit digits; ids = positions)
         ids_sorted = side ? geom.id_b : geom.id_a;
         LG_STAGE_CHECK("range sort");
     } else {
@@ -425,7 +380,7 @@ int bin_frame(const BinSpec& spec, const GeomView& geom, uint2* ranges, size_t P
             const RangeSortRest rest = range_sort_rest(kinv, kmax);
             KeyBias kb = rest.bias;
             int bits = rest.end_bit;
-            static const int env_full = [] { const char* e = getenv("LIDARGS_RANGE_SORT_FULL"); return e ? atoi(e) : 0; }();   // 1: always 31 bits (A/B)
+            const bool env_full = switches().range_sort_full;              // LIDARGS_RANGE_SORT_FULL=1: always 31 bits (A/B)
             if (env_full && !surfel) { bits = 32; kb.kmin = 0u; kb.cull = 0xFFFFFFFFu; }
             uint32_t* const k_in = first_side ? geom.key_b : geom.key_a; uint32_t* const k_out = first_side ? geom.key_a : geom.key_b;
             uint32_t* const v_in = first_side ? geom.id_b : geom.id_a; uint32_t* const v_out = first_side ? geom.id_a : geom.id_b;
@@ -476,9 +431,8 @@ int bin_frame(const BinSpec& spec, const GeomView& geom, uint2* ranges, size_t P
     L.bin_carve(bin_p, &bin);
 
     // 3. emit instances in range order, bin them by tile (stable); 16-bit tile keys whenever the tile ids fit (LIDARGS_TILE_KEY32=1: A/B)
-    static const bool key32 = [] { const char* e = getenv("LIDARGS_TILE_KEY32"); return e && atoi(e) != 0; }();
     const int tiles = L.grid.num_tiles();
-    const bool key16 = tiles <= 65536 && (surfel || !key32);
+    const bool key16 = tiles <= 65536 && (surfel || !switches().tile_key32);
     if (R) {
         // the sorted lists are wanted on the a side (the backward finds them there whatever the pass count was): a sort that will end on
         // the other side -- an odd number of passes: images of at most 256 list tiles -- gets its input there, instead of two copies behind it
@@ -755,7 +709,7 @@ int lidargs_forward(lidargs_alloc_fn geometry_alloc, void* geometry_user, lidarg
     (void)D; (void)M; (void)shs; (void)projmatrix; (void)cam_pos; (void)prefiltered;
     const float inf = std::numeric_limits<float>::infinity();
     FrameMode mode;
-    mode.deterministic = lg::deterministic_env();
+    mode.deterministic = lg::deterministic_requested();
     return forward_impl(geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user, P, background, width,
                         height, means3D, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix,
                         beam_inclinations, (float)lidar_near, (float)lidar_far, -inf, inf, nullptr, 0, out_color, out_depth,

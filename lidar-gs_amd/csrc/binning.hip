@@ -14,7 +14,6 @@
 // Ranks inside a wave come from ballot-matching the digit bits (wave-wide match-any), so every pass is
 // stable by construction; blocks sort locally in LDS and write whole digit runs.
 #include "lidargs_common.h"
-#include <stdlib.h>
 
 namespace lg {
 
@@ -489,11 +488,7 @@ static void radix_pass_items_aux(const uint32_t* kin, const uint32_t* vin, uint3
 // group's keys (and values) in flight while this one is ranked, with plain unconditional loads the compiler can count (the first forms
 // -- all rounds in registers behind workgroup-scope atomic loads, then one round ahead -- waited for every load: 30 us per pass).
 constexpr int SMALL_SORT_WAVES = 16;
-constexpr size_t SMALL_SORT_MAX = 16384;                               // pairs (a size choice: 16 rounds per wave)
-// ... and up to where it is used (LIDARGS_SMALL_SORT_MAX): one CU ranks ~0.5 pairs per ns (16 waves x ~100 instructions per 64 pairs and
-// phase on four SIMDs: issue-bound, tools/micro/small_sort_bench.cpp), so at 14 k pairs a pass takes 25-30 us against ~15 us for the
-// three launches of the general form; below ~4 k pairs the single launch wins (4000 pairs: 12 us per pass)
-constexpr size_t SMALL_SORT_DEFAULT = 4096;
+// (SMALL_SORT_MAX, and SMALL_SORT_DEFAULT up to where the form is used unless LIDARGS_SMALL_SORT_MAX says otherwise: switches.h)
 constexpr int SMALL_SORT_GROUP = 4;                                    // rounds ranked per set of loads in flight
 __device__ __forceinline__ uint32_t load_l2(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 
@@ -669,7 +664,7 @@ __global__ void __launch_bounds__(64 * SMALL_SORT_WAVES) k_radix_sort_small(KT* 
 template <int BITS, typename KT>
 static void radix_pass(const KT* kin, const uint32_t* vin, KT* kout, uint32_t* vout, size_t n, const uint32_t* n_dev, int shift,
                        uint32_t* scratch, hipStream_t s, int scratch_bits, const RadixTail& tail, const KeyBias* bias) {
-    static const int env = [] { const char* e = getenv("LIDARGS_SORT_ITEMS"); return e ? atoi(e) : 0; }();   // 8 / 16 forces the block size
+    const int env = switches().sort_items;                       // LIDARGS_SORT_ITEMS = 8 / 16 forces the block size
     const bool room = BITS + 1 <= scratch_bits;                  // twice the blocks x BINS <= the histogram area (and the chunk sums likewise)
     const bool half = room && (env ? env == 8 : n <= ((size_t)4 << 20));
     if constexpr (BITS <= 10) {
@@ -684,10 +679,7 @@ static int radix_sort_pairs_t(KT* key_a, KT* key_b, uint32_t* val_a, uint32_t* v
                             RadixTail tail, int begin_bit, const KeyBias* bias) {
     if (n == 0 || end_bit <= begin_bit) return 0;
     if (max_bits < 1 || max_bits > SORT_MAX_RADIX_BITS) max_bits = SORT_RADIX_BITS;
-    static const int small_off = [] { const char* e = getenv("LIDARGS_NO_SMALL_SORT"); return e ? atoi(e) : 0; }();
-    static const size_t small_max = [] { const char* e = getenv("LIDARGS_SMALL_SORT_MAX"); const long v = e ? atol(e) : (long)SMALL_SORT_DEFAULT;
-                                         return (size_t)(v < 0 ? 0 : (v > (long)SMALL_SORT_MAX ? (long)SMALL_SORT_MAX : v)); }();
-    if (n <= small_max && !small_off) {                                // the whole sort in one launch (k_radix_sort_small)
+    if (uses_small_sort(n)) {                                          // the whole sort in one launch (k_radix_sort_small)
         const int mb = max_bits > 8 ? 8 : max_bits;
         int passes = 0;
         for (int sh = begin_bit; sh < end_bit;) { const int left = end_bit - sh, pl = (left + mb - 1) / mb; sh += (left + pl - 1) / pl; passes++; }
@@ -732,10 +724,7 @@ static int radix_sort_pairs_t(KT* key_a, KT* key_b, uint32_t* val_a, uint32_t* v
 // on a given side produces the input on the other one when this says 1 (api.hip: the emit of a one-pass tile sort writes to the b side).
 int radix_sort_result_side(size_t n, int end_bit) {
     if (n == 0 || end_bit <= 0) return 0;
-    static const int small_off = [] { const char* e = getenv("LIDARGS_NO_SMALL_SORT"); return e ? atoi(e) : 0; }();
-    static const size_t small_max = [] { const char* e = getenv("LIDARGS_SMALL_SORT_MAX"); const long v = e ? atol(e) : (long)SMALL_SORT_DEFAULT;
-                                         return (size_t)(v < 0 ? 0 : (v > (long)SMALL_SORT_MAX ? (long)SMALL_SORT_MAX : v)); }();
-    if (n <= small_max && !small_off) return 0;
+    if (uses_small_sort(n)) return 0;
     return ((end_bit + SORT_RADIX_BITS - 1) / SORT_RADIX_BITS) & 1;
 }
 int launch_radix_sort_pairs(uint32_t* key_a, uint32_t* key_b, uint32_t* val_a, uint32_t* val_b, size_t n, int end_bit,
@@ -1080,14 +1069,8 @@ __global__ void __launch_bounds__(64 * BSORT_WAVES) __attribute__((amdgpu_waves_
 }
 
 // LIDARGS_RANGE_SORT_BUCKETS=0: the LSD passes again (A/B, tests).  LIDARGS_RANGE_SORT_BUCKET_BITS=11: the 2048-interval form at any size
-// (tests: the CPU checker cannot run frames above 4 M Gaussians; read per call, the suite switches it inside one process).
-static int forced_bucket_bits() { const char* e = getenv("LIDARGS_RANGE_SORT_BUCKET_BITS"); const int v = e ? atoi(e) : 0; return (v == BUCKET_BITS || v == BUCKET_BITS_BIG) ? v : 0; }
 bool range_sort_buckets_ok(size_t P) {
-    static const bool on = [] { const char* e = getenv("LIDARGS_RANGE_SORT_BUCKETS"); return !e || atoi(e) != 0; }();
-    static const size_t small_max = [] { const char* e = getenv("LIDARGS_SMALL_SORT_MAX"); const long v = e ? atol(e) : (long)SMALL_SORT_DEFAULT;
-                                         return (size_t)(v < 0 ? 0 : (v > (long)SMALL_SORT_MAX ? (long)SMALL_SORT_MAX : v)); }();
-    static const int small_off = [] { const char* e = getenv("LIDARGS_NO_SMALL_SORT"); return e ? atoi(e) : 0; }();
-    return on && (P <= BUCKET_SORT_MAX || forced_bucket_bits() == BUCKET_BITS_BIG) && (small_off || P > small_max);
+    return switches().range_sort_buckets && (P <= BUCKET_SORT_MAX || forced_bucket_bits(BUCKET_BITS, BUCKET_BITS_BIG) == BUCKET_BITS_BIG) && !uses_small_sort(P);
 }
 // (key_a, positions) -> ids in range order in id_a, tail.dst = the records of tail.src in range order.  key_b / id_b hold the bucketed
 // pairs; `scratch` as for launch_radix_sort_pairs with scratch_bits = SORT_MAX_RADIX_BITS.  key_span: GeomView totals + LG_TOTALS_KEYSPAN_WORD.
@@ -1095,8 +1078,7 @@ template <int BB>
 static void range_sort_buckets_t(uint32_t* key_a, uint32_t* key_b, uint32_t* id_a, uint32_t* id_b, size_t P, uint32_t* scratch, const KeyBias* kb, RadixTail tail, hipStream_t s) {
     const uint32_t* tot = scratch + ((size_t)1 << SORT_MAX_RADIX_BITS) * sort_blocks(P);       // where the pass leaves the digit totals (radix_pass_items)
     const unsigned cull_blocks = (unsigned)((P + BSORT_CULL_SLICE - 1) / BSORT_CULL_SLICE);     // (as many as a frame of culled Gaussians only would need: the others leave at once)
-    static const bool packed_on = [] { const char* e = getenv("LIDARGS_RANGE_SORT_PACKED"); return !e || atoi(e) != 0; }();   // 0: round 5's form (A/B)
-    if (tail.mode == 1 && packed_on) {
+    if (tail.mode == 1 && switches().range_sort_packed) {               // LIDARGS_RANGE_SORT_PACKED=0: round 5's form (A/B)
         // 4-byte span records: they ride along with the pairs (the second half of the span_sorted allocation -- u32x2[P], of which the
         // compact form uses the first P words -- holds them between the two launches)
         uint32_t* aux_b = static_cast<uint32_t*>(tail.dst) + P;
@@ -1114,7 +1096,7 @@ void launch_range_sort_buckets(uint32_t* key_a, uint32_t* key_b, uint32_t* id_a,
                                RadixTail tail, hipStream_t s) {
     if (P == 0) return;
     KeyBias kb; kb.kmin = 0u; kb.cull = 0xFFFFFFFFu; kb.lin_span = key_span;
-    const int forced = forced_bucket_bits();
+    const int forced = forced_bucket_bits(BUCKET_BITS, BUCKET_BITS_BIG);
     if (forced ? forced == BUCKET_BITS_BIG : P > BUCKET_SORT_MAX) range_sort_buckets_t<BUCKET_BITS_BIG>(key_a, key_b, id_a, id_b, P, scratch, &kb, tail, s);
     else range_sort_buckets_t<BUCKET_BITS>(key_a, key_b, id_a, id_b, P, scratch, &kb, tail, s);
 }

@@ -295,7 +295,7 @@ namespace {
 // then cover the capacities n, m and every kernel clamps to the real sizes)
 int chamfer_forward_impl(int B, int n, int m, const float* xyz1, const float* xyz2, float* dist1, float* dist2, int* idx1, int* idx2,
                          char* scratch, const uint32_t* nm_dev, hipStream_t stream) {
-    static const bool brute_only = [] { const char* e = getenv("LIDARGS_CHAMFER_BRUTE"); return e && atoi(e) != 0; }();   // A/B, tests: the round-3 path
+    const bool brute_only = lg::switches().chamfer_brute;              // LIDARGS_CHAMFER_BRUTE=1 (A/B, tests: the round-3 path)
     ChWork w; ch_carve(scratch, n, m, &w);
     const int per = CH_BLOCK * CH_Q;
     hipError_t e = hipSuccess;

@@ -28,6 +28,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include "switches.h"     // every LIDARGS_* environment switch; SORT_MAX_RADIX_BITS
 
 #define LG_TILE_W 16          // = the reference's BLOCK_X (R3/cr/config.h:16); rect x-units are shared
 #define LG_WAVE_ROWS 4        // one wave64 = 16 columns x 4 rows of pixels
@@ -63,7 +64,6 @@ constexpr int SORT_ITEMS = 16;                  // rounds of 64 keys per wave
 constexpr int SORT_WAVES = 4;                   // waves per sort block
 constexpr int SORT_CHUNK = 64 * SORT_ITEMS * SORT_WAVES;   // keys per block (4096)
 constexpr int SORT_RADIX_BITS = 8;               // default digit width (tile binning: short digit runs must stay whole lines)
-constexpr int SORT_MAX_RADIX_BITS = 11;          // the range sort of the P Gaussians: 31 key bits in 3 passes (11 + 10 + 10)
 constexpr int SORT_MAX_BINS = 1 << SORT_MAX_RADIX_BITS;
 constexpr int SCAN_BLOCK = 1024;                // elements per scan block (256 threads x 4)
 
@@ -331,7 +331,6 @@ void lane_stats_read(unsigned long long* out, int reset);              // render
 // helpers exported by api.hip for the other entry-point files
 int api_fail(int code, const char* msg);
 int api_check_launch(hipStream_t s, int debug, const char* what);
-bool deterministic_env();                       // LIDARGS_DETERMINISTIC=1, read at every call
 int refuse_deterministic(const char* entry);    // 0, or LIDARGS_ERR_INVALID_ARGUMENT (message set) when the switch is on: entry points the mode does not cover
 // Device -> host read of `n` (<= 1024) words with `zero_bytes` at `zero` cleared BEHIND the copy on the same stream: the host waits
 // for the copy only.  Returns a hipError_t.

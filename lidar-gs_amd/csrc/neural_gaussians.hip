@@ -1004,18 +1004,9 @@ int ng_cus() {
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
     return cus;
 }
-// LIDARGS_NG_PER_LANE_DECODE=1 (read once per process): the one-anchor-per-lane forward, which a model without W2T gets in any case
-bool ng_per_lane() {
-    static const bool on = [] { const char* e = getenv("LIDARGS_NG_PER_LANE_DECODE"); return e && atoi(e) != 0; }();
-    return on;
-}
 // k <= 6: the forward's two MLP launches on 16x16x4 tiles (k_ng_opacity_t16 / k_ng_decode_t16: persistent workgroups of twelve waves, weights in
 // LDS); k = 8, 10 and LIDARGS_NG_FORWARD_T16=0 (A/B, test variant): the 32x32x2 kernels, one wave per workgroup
-bool ng_forward_t16(int k) {
-    if (k > 6) return false;
-    const char* e = getenv("LIDARGS_NG_FORWARD_T16");
-    return !(e && e[0] == '0');
-}
+bool ng_forward_t16(int k) { return k <= 6 && lg::ng_forward_t16_allowed(); }
 int ng_forward_grid(int N) {
     const int cus = ng_cus(), need = ((N + 31) / 32 + NGF_WAVES - 1) / NGF_WAVES;
     return need < cus ? (need > 0 ? need : 1) : cus;
@@ -1049,7 +1040,7 @@ static int ng_forward_select(int N, const lidargs_ng_model* model, const uint8_t
     auto launch = [&](auto kernel, int grid, int block) {
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, stream, N, m, c.cam, anchor_feat, anchor, s.vis_flags, s.vis_idx, neural_opacity, mask, s.sel_flags);
     };
-    if (ng_per_lane() || !m.W2T[0]) { NG_DISPATCH(m.k, launch(lg::k_ng_opacity<K>, (N + 63) / 64, 64)); }
+    if (lg::switches().ng_per_lane_decode || !m.W2T[0]) { NG_DISPATCH(m.k, launch(lg::k_ng_opacity<K>, (N + 63) / 64, 64)); }
     else if (ng_forward_t16(m.k)) { NG_DISPATCH_T16(m.k, launch(lg::k_ng_opacity_t16<K>, ng_forward_grid(N), 64 * NGF_WAVES)); }
     else { NG_DISPATCH(m.k, launch(lg::k_ng_opacity_mfma<K>, (N + 63) / 64, 64)); }
     lg::launch_exclusive_scan(s.sel_flags, s.slot, (size_t)N * m.k, s.totals + 1, s.scan, stream);
@@ -1087,7 +1078,7 @@ int lidargs_ng_forward_decode(int N, const lidargs_ng_model* model, const float*
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, stream, N, m, c.cam, anchor_feat, anchor, offset, scaling, s.vis_flags, s.vis_idx, s.sel_flags, s.slot,
                            neural_opacity, out_xyz, out_color, out_opacity, out_scaling, out_rot);
     };
-    if (ng_per_lane() || !m.W2T[0] || !m.W2T[1] || !m.W2T[2] || !m.W2T[3]) {     // the matrix-pipe decode reads the transposed second-layer weights
+    if (lg::switches().ng_per_lane_decode || !m.W2T[0] || !m.W2T[1] || !m.W2T[2] || !m.W2T[3]) {     // the matrix-pipe decode reads the transposed second-layer weights
         NG_DISPATCH(m.k, launch(lg::k_ng_decode<K>, (N + 63) / 64, 64));
     } else if (ng_forward_t16(m.k)) { NG_DISPATCH_T16(m.k, launch(lg::k_ng_decode_t16<K>, ng_forward_grid(N), 64 * NGF_WAVES)); }
     else { NG_DISPATCH(m.k, launch(lg::k_ng_decode_mfma<K>, (N + 63) / 64, 64)); }
@@ -1115,18 +1106,12 @@ int lidargs_ng_backward(int N, int n_visible, const lidargs_ng_model* model, con
 
 // k <= 6: k_ng_backward_t16 (16x16x4 tiles, one workgroup of eight waves per CU, one partial row per workgroup); k = 8, 10 (its LDS does
 // not hold their delta2 rows for eight waves) and LIDARGS_NG_BACKWARD_T16=0 (A/B, test variant): k_ng_backward_mfma, one wave per SIMD
-static bool ng_use_t16(int k) {
-    if (k > 6) return false;
-    const char* e = getenv("LIDARGS_NG_BACKWARD_T16");
-    return !(e && e[0] == '0');
-}
-// LIDARGS_NG_T16_PASSES=1: the four MLPs in one launch (A/B); default two launches (see k_ng_backward_t16)
-static bool ng_t16_two_pass() { const char* e = getenv("LIDARGS_NG_T16_PASSES"); return !(e && e[0] == '1'); }
+static bool ng_use_t16(int k) { return k <= 6 && lg::ng_backward_t16_allowed(); }
 // The variant is chosen by environment switches read per call (the suite selects variants in one process), and the backward takes no
 // capacity argument: what lidargs_ng_backward_partials last told this thread for k is remembered, and a backward whose variant would now
 // write a different number of partial rows refuses instead of overflowing the caller's buffer (round-5 advisor finding).
 static thread_local int t_ng_rows_reported[16] = {0};
-static int ng_partial_rows(int k) { return ng_use_t16(k) ? (ng_t16_two_pass() ? 2 : 1) * ng_cus() : 4 * ng_cus(); }
+static int ng_partial_rows(int k) { return ng_use_t16(k) ? (lg::ng_t16_two_pass() ? 2 : 1) * ng_cus() : 4 * ng_cus(); }
 int lidargs_ng_backward_partials(int n_offsets, int* waves, int* floats_per_wave) {
     const int k = n_offsets;
     if (!lg::ng_valid_k(k) || !waves || !floats_per_wave) return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "ng_backward_partials: bad argument");
@@ -1154,9 +1139,8 @@ int lidargs_ng_backward_mfma(int N, const lidargs_ng_model* model, const float* 
                            dL_dxyz, dL_dcolor, dL_dopacity, dL_dscaling, dL_drot, dL_dneural_opacity, dL_danchor_feat, dL_danchor, dL_doffset, dL_dscaling_in, partials, tail...);
     };
     if (ng_use_t16(m.k)) {
-        const char* sg = getenv("LIDARGS_NG_T16_STAGGER");
-        const int stagger = sg ? atoi(sg) : 0, grid = ng_cus(), block = 64 * NGT_WAVES;
-        if (ng_t16_two_pass()) { NG_DISPATCH_T16(m.k, launch(lg::k_ng_backward_t16<K, 2>, grid, block, stagger); launch(lg::k_ng_backward_t16<K, 1>, grid, block, stagger)); }
+        const int stagger = lg::ng_t16_stagger(), grid = ng_cus(), block = 64 * NGT_WAVES;
+        if (lg::ng_t16_two_pass()) { NG_DISPATCH_T16(m.k, launch(lg::k_ng_backward_t16<K, 2>, grid, block, stagger); launch(lg::k_ng_backward_t16<K, 1>, grid, block, stagger)); }
         else { NG_DISPATCH_T16(m.k, launch(lg::k_ng_backward_t16<K, 0>, grid, block, stagger)); }
     } else { NG_DISPATCH(m.k, launch(lg::k_ng_backward_mfma<K>, waves, 64)); }
     NG_HIP(hipGetLastError());

@@ -41,7 +41,6 @@
 #else
 #define LG_EXPF(x) __expf(x)
 #endif
-#include <stdlib.h>
 
 namespace lg {
 
@@ -905,18 +904,13 @@ __global__ void __launch_bounds__(64) k_render_combine(const RenderFwdArgs a) {
     a.out_occ[pix] = 1.f - T_final;
 }
 
-// LIDARGS_WALK2 (bits; default all): 1 = the second form of the T-only walk, 2 = of the full walk, 4 = of the backward walk; 0 = the first forms (A/B)
-static int walk2() {
-    static const int m = [] { const char* e = getenv("LIDARGS_WALK2"); return e ? atoi(e) : 7; }();
-    return m;
-}
-// waves per workgroup of the fused forward blend: LIDARGS_FUSED_WAVES = 4, 8 (default) or 16
+static int walk2() { return switches().walk2; }     // LIDARGS_WALK2: bits 1 / 2 / 4 = the second form of the T-only / full / backward walk
 void launch_render_fused(const RenderFwdArgs& a_, hipStream_t s) {
     RenderFwdArgs a = a_; a.walk2 = walk2() & 1;
-    static const int env = [] { const char* e = getenv("LIDARGS_FUSED_WAVES"); return e ? atoi(e) : 0; }();
+    const int waves = switches().fused_waves;           // LIDARGS_FUSED_WAVES
     const unsigned patches = (unsigned)a.grid.window_patches();
-    if (env == 4) hipLaunchKernelGGL(k_render_fused<4>, dim3(patches), dim3(256), 0, s, a);
-    else if (env == 16) hipLaunchKernelGGL(k_render_fused<16>, dim3(patches), dim3(1024), 0, s, a);
+    if (waves == 4) hipLaunchKernelGGL(k_render_fused<4>, dim3(patches), dim3(256), 0, s, a);
+    else if (waves == 16) hipLaunchKernelGGL(k_render_fused<16>, dim3(patches), dim3(1024), 0, s, a);
     else hipLaunchKernelGGL(k_render_fused<8>, dim3(patches), dim3(512), 0, s, a);
 }
 void launch_render_alive(const RenderFwdArgs& a, hipStream_t s) {
@@ -933,8 +927,7 @@ void launch_render_pass1(const RenderFwdArgs& a, hipStream_t s) {
 // long), so it stays at 1 = one workgroup per (patch, segment); on the 128-entry plan of the big frames 8 wins (cfg4 0.104 ->
 // 0.077 ms).  LIDARGS_P2_GROUP overrides.
 static int pass2_group(int seg_len) {
-    static const int env = [] { const char* e = getenv("LIDARGS_P2_GROUP"); const int v = e ? atoi(e) : 0; return v < 0 ? 0 : (v > 64 ? 64 : v); }();
-    return env ? env : (seg_len >= LG_SEG_LEN_DEFAULT ? 8 : 1);
+    return switches().p2_group ? switches().p2_group : (seg_len >= LG_SEG_LEN_DEFAULT ? 8 : 1);
 }
 void launch_render_pass2(const RenderFwdArgs& a, hipStream_t s) {
     const int G = pass2_group(a.seg_len);

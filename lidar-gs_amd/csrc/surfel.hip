@@ -731,8 +731,7 @@ __global__ void __launch_bounds__(64) k_sf_combine(const SfFwdArgs a) {
 }
 
 void launch_sf_render_pass1(const SfFwdArgs& a, hipStream_t s) {
-    static const bool walk2 = [] { const char* e = getenv("LIDARGS_WALK2"); return !e || (atoi(e) & 1) != 0; }();   // render.hip walk2()
-    if (walk2) hipLaunchKernelGGL((k_sf_render_forward<true, true>), dim3(segment_grid(a.grid.num_tiles() * a.grid.waves_per_tile, a.seg_hi - a.seg_lo)), dim3(64), 0, s, a);
+    if (switches().walk2 & 1) hipLaunchKernelGGL((k_sf_render_forward<true, true>), dim3(segment_grid(a.grid.num_tiles() * a.grid.waves_per_tile, a.seg_hi - a.seg_lo)), dim3(64), 0, s, a);
     else hipLaunchKernelGGL((k_sf_render_forward<true, false>), dim3(segment_grid(a.grid.num_tiles() * a.grid.waves_per_tile, a.seg_hi - a.seg_lo)), dim3(64), 0, s, a);
 }
 void launch_sf_render_pass2(const SfFwdArgs& a, hipStream_t s) {

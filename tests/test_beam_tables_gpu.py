@@ -19,7 +19,7 @@ import numpy as np
 import pytest
 
 import lidargs_scenes as sc
-from util import GRAD_KEYS_SR, hip_forward_backward, oracle_forward_backward, parity
+from util import GRAD_KEYS_SR, hip_forward_backward, oracle_forward_backward, parity, run_child
 
 pytestmark = pytest.mark.gpu
 
@@ -161,25 +161,22 @@ def test_pruning_is_invisible(table, hip_lib_built):
     """LIDARGS_NO_PRUNE=1 bins every tile / row of the reference rect (what the reference does); the default drops those no pixel
     can take.  Same image and gradients either way (up to the summation grouping: the lists are cut into segments by length), and
     the pruned run must bin strictly fewer instances on this scene -- i.e. the knob really switches something."""
-    import json, os, subprocess, sys, tempfile
+    import os, tempfile
     code = r"""
 import sys, json, numpy as np
-sys.path[:0] = [%r, %r, %r]
 from test_beam_tables_gpu import _stress_scene
 from util import hip_forward_backward, GRAD_KEYS_SR
 from diff_lidargs_rasterization import _C
 scene, W, H, grads = _stress_scene(%r)
 hip = hip_forward_backward(scene, W, H, grads)
 np.savez(sys.argv[1], instances=_C.last_counters()["instances"], **{k: hip[k] for k in ("color", "depth", "occ", "radii") + GRAD_KEYS_SR})
-"""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = code % (root, os.path.join(root, "lidar-gs_amd"), os.path.join(root, "tests"), table)
+print("OK")
+""" % table
     res = {}
     with tempfile.TemporaryDirectory() as tmp:
         for name, env in (("pruned", {}), ("unpruned", {"LIDARGS_NO_PRUNE": "1"})):
             out = os.path.join(tmp, name + ".npz")
-            r = subprocess.run([sys.executable, "-c", code, out], env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
-            assert r.returncode == 0, r.stderr[-3000:]
+            run_child(code, env, (out,))
             res[name] = dict(np.load(out))
     a, b = res["pruned"], res["unpruned"]
     print(f"[prune] instances binned: {int(a['instances'])} pruned, {int(b['instances'])} unpruned")

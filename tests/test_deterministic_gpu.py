@@ -19,14 +19,13 @@ four child processes (two scenes x {work list, slot grid}), started together; LI
 is flipped inside one process everywhere else.
 """
 import os
-import subprocess
-import sys
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
 
 import lidargs_scenes as sc
-from util import GRAD_KEYS_SR, hip_forward_backward, oracle_forward_backward, parity
+from util import GRAD_KEYS_SR, hip_forward_backward, oracle_forward_backward, parity, run_child
 
 pytestmark = pytest.mark.gpu
 
@@ -89,29 +88,15 @@ def child_main(name, out):
 @pytest.fixture(scope="module")
 def runs(hip_lib_built, tmp_path_factory):
     """{(scene, "lists" | "grid"): arrays of child_main}, the four children running side by side."""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = "import sys; sys.path[:0] = [%r, %r, %r]; import test_deterministic_gpu as t; t.child_main(sys.argv[1], sys.argv[2])" % (
-        root, os.path.join(root, "lidar-gs_amd"), os.path.join(root, "tests"))
+    code = f"import os\nos.environ.pop({SWITCH!r}, None)\nimport test_deterministic_gpu as t\nt.child_main(sys.argv[1], sys.argv[2])"
     d = tmp_path_factory.mktemp("deterministic")
-    base = {k: v for k, v in os.environ.items() if k != SWITCH}
-    procs = {}
-    for name, (_, _, _, plan) in SCENES.items():
-        for order, lists in (("lists", "1"), ("grid", "0")):
-            out = str(d / f"{name}_{order}.npz")
-            env = dict(base, LIDARGS_WORK_LISTS=lists, **plan)
-            procs[name, order] = (out, subprocess.Popen([sys.executable, "-c", code, name, out], env=env, stdout=subprocess.PIPE,
-                                                        stderr=subprocess.STDOUT, text=True))
-    got = {}
-    for key, (out, p) in procs.items():
-        try:
-            text, _ = p.communicate(timeout=300)
-        except subprocess.TimeoutExpired:
-            p.kill()
-            text, _ = p.communicate()
-        print(key, text[-3000:])
-        assert p.returncode == 0 and "OK" in text, key
-        got[key] = dict(np.load(out))
-    return got
+    outs = {(name, order): str(d / f"{name}_{order}.npz") for name in SCENES for order in ("lists", "grid")}
+    with ThreadPoolExecutor(len(outs)) as pool:
+        runs = [pool.submit(run_child, code, dict(SCENES[name][3], LIDARGS_WORK_LISTS="1" if order == "lists" else "0"), (name, out), 300)
+                for (name, order), out in outs.items()]
+        for r in runs:
+            r.result()
+    return {key: dict(np.load(out)) for key, out in outs.items()}
 
 
 @pytest.mark.parametrize("name", list(SCENES))

@@ -2,20 +2,15 @@
 negative, NaN and +-inf.  Every other rasterizer test draws its opacities from U(0.1, 1) times a scale; the kernels' decisions that hang
 on the opacity -- the cull `op * 255 < 1`, both footprint prunings (their reach follows tau = ln(255 op)), the blend's
 fminf(0.99, op G) and its 1/255 test -- are pinned here against the oracle, entry by entry where a budget could hide a dropped pixel."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import lidargs_scenes as sc
 from util import (FLOOR, GRAD_KEYS_SR, GRAD_KEYS_SURFEL, SOFT_MAX, hip_forward_backward, hip_surfel_forward_backward, oracle_forward_backward,
-                  oracle_surfel_forward_backward, parity, placed_scene, surfel_scene, surfel_upstream_grads)
+                  oracle_surfel_forward_backward, parity, placed_scene, run_child, surfel_scene, surfel_upstream_grads)
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OTHERS = ("depth", "alpha", "normal_x", "normal_y", "normal_z")          # the surfel planes compared pixel by pixel (not the median / distortion)
 
 
@@ -241,11 +236,7 @@ def test_nonfinite_opacity(variant):
 
 def test_nonfinite_opacity_on_the_five_launch_forward_and_work_list_backward():
     """The 3-D variant's other forward (five launches) and the backward over the work list the combine fills (its default there)."""
-    code = "import sys; sys.path[:0] = [%r, %r, %r]\nimport test_opacity_domain_gpu as t\nt._nonfinite_case('3d')\nprint('OK')" % (
-        ROOT, os.path.join(ROOT, "lidar-gs_amd"), os.path.join(ROOT, "tests"))
-    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, LIDARGS_FUSED="0"), capture_output=True, text=True, timeout=600)
-    print(r.stdout[-3000:], r.stderr[-3000:])
-    assert r.returncode == 0 and "OK" in r.stdout
+    run_child("import test_opacity_domain_gpu as t\nt._nonfinite_case('3d')\nprint('OK')", {"LIDARGS_FUSED": "0"})
 
 
 @pytest.mark.parametrize("variant", ["3d", "surfel"])

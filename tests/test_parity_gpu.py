@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import lidargs_scenes as sc
-from util import GRAD_KEYS_SR, hip_forward_backward, oracle_forward_backward, parity
+from util import GRAD_KEYS_SR, hip_forward_backward, oracle_forward_backward, parity, run_child
 
 pytestmark = pytest.mark.gpu
 
@@ -183,10 +183,8 @@ def test_argument_errors(hip_lib_built):
 @pytest.mark.parametrize("tile_rows", [8, 16, 32])
 def test_tile_height_variants(tile_rows, hip_lib_built):
     """The list-tile height (LIDARGS_TILE_ROWS) is an internal choice: results must not depend on it."""
-    import os, subprocess, sys, json, tempfile
-    code = r"""
-import sys, json, numpy as np
-sys.path[:0] = [%r, %r, %r]
+    run_child(r"""
+import json, numpy as np
 import lidargs_scenes as sc
 from util import hip_forward_backward, oracle_forward_backward, parity, GRAD_KEYS_SR
 scene = sc.make_scene("street", 30000, 32, 10, random_view=True)
@@ -196,13 +194,7 @@ hip = hip_forward_backward(scene, 800, 32, grads)
 for k in ("color", "depth", "occ") + GRAD_KEYS_SR:
     parity(k, hip[k], ref[k])
 print("OK")
-"""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = code % (root, os.path.join(root, "lidar-gs_amd"), os.path.join(root, "tests"))
-    env = dict(os.environ, LIDARGS_TILE_ROWS=str(tile_rows))
-    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
-    print(r.stdout[-3000:], r.stderr[-3000:])
-    assert r.returncode == 0 and "OK" in r.stdout
+""", {"LIDARGS_TILE_ROWS": str(tile_rows)})
 
 
 @pytest.mark.parametrize("env", [{"LIDARGS_HEAD": "1"}, {"LIDARGS_HEAD": "1", "LIDARGS_ROUNDS": "2,6"}, {"LIDARGS_HEAD": "0", "LIDARGS_SEG_LEN": "128"},
@@ -225,10 +217,8 @@ def test_plan_variants_are_invisible(env, hip_lib_built):
     go through it too), the range sort on the key span against all 31 bits (the third scene sits closer than 2 m to the sensor in places,
     so that the key span is not the usual 26 bits); the backward blend over
     the slot grid against the work list the combine fills (the default whenever the five-launch forward runs: `five_launch_forward`)."""
-    import os, subprocess, sys
-    code = r"""
-import sys, numpy as np
-sys.path[:0] = [%r, %r, %r]
+    run_child(r"""
+import numpy as np
 import lidargs_scenes as sc
 from util import hip_forward_backward, oracle_forward_backward, parity, GRAD_KEYS_SR
 for kind, P, H, W, seed in (("street", 60000, 32, 800, 11), ("shell", 20000, 16, 512, 12), ("near", 9000, 16, 400, 13)):
@@ -250,12 +240,7 @@ for kind, P, H, W, seed in (("street", 60000, 32, 800, 11), ("shell", 20000, 16,
     for k in ("color", "depth", "occ") + GRAD_KEYS_SR:
         parity(kind + "." + k, hip[k], ref[k])
 print("OK")
-"""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = code % (root, os.path.join(root, "lidar-gs_amd"), os.path.join(root, "tests"))
-    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
-    print(r.stdout[-3000:], r.stderr[-3000:])
-    assert r.returncode == 0 and "OK" in r.stdout
+""", env)
 
 
 @pytest.mark.parametrize("env", [{"LIDARGS_HEAD": "1"}, {"LIDARGS_HEAD": "0", "LIDARGS_SEG_LEN": "128"}, {"LIDARGS_FUSED": "0"},
@@ -265,10 +250,8 @@ def test_plan_variants_are_invisible_on_bimodal_opacities(env, hip_lib_built):
     """test_plan_variants_are_invisible on a trained model's opacities (lidargs_scenes.make_scene opacity="bimodal": 70 % U(0.01, 0.1), 30 %
     U(0.7, 1)): saturating and nearly transparent lists share every patch, so the gated rounds close some pixels of a patch early while
     the others walk their whole lists -- the regime the head, the segment plans and the two backward schedules are tuned for least."""
-    import os, subprocess, sys
-    code = r"""
-import sys, numpy as np
-sys.path[:0] = [%r, %r, %r]
+    run_child(r"""
+import numpy as np
 import lidargs_scenes as sc
 from util import hip_forward_backward, oracle_forward_backward, parity, GRAD_KEYS_SR
 P, H, W, seed = 60000, 32, 800, 11
@@ -280,12 +263,7 @@ assert int((hip["radii"] != ref["radii"]).sum()) <= 1
 for k in ("color", "depth", "occ") + GRAD_KEYS_SR:
     parity("bimodal." + k, hip[k], ref[k])
 print("OK")
-"""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = code % (root, os.path.join(root, "lidar-gs_amd"), os.path.join(root, "tests"))
-    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
-    print(r.stdout[-3000:], r.stderr[-3000:])
-    assert r.returncode == 0 and "OK" in r.stdout
+""", env)
 
 
 @pytest.mark.parametrize("H,W", [(16, 4128), (272, 512)], ids=["258_tile_columns", "272_rows"])
@@ -649,10 +627,8 @@ def test_hip_graph_capture_of_forward_and_backward(hip_lib_built):
     eager image bit for bit and the eager gradients within the summation-order band (the backward's float atomics).  Runs in a
     process of its own: a capture is invalidated by unrelated runtime calls made while it records (another test's pinned host
     memory being released, an event query), and a broken capture must fail this test, not take the session down."""
-    import os, subprocess, sys
-    code = r"""
-import sys, gc
-sys.path[:0] = [%r, %r, %r]
+    run_child(r"""
+import gc
 import numpy as np, torch
 import lidargs_scenes as sc
 from test_parity_gpu import _enqueue_setup
@@ -696,9 +672,4 @@ for outs, gs in replays:
     for a, b in zip(g_ref, gs):
         parity("graph replay backward", b.cpu().numpy(), a.cpu().numpy(), verbose=False)
 print("GRAPH-OK")
-"""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = code % (root, os.path.join(root, "lidar-gs_amd"), os.path.join(root, "tests"))
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600)
-    print(r.stdout[-2000:], r.stderr[-3000:])
-    assert r.returncode == 0 and "GRAPH-OK" in r.stdout
+""")

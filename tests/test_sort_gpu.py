@@ -15,12 +15,11 @@ field f = (km(key) >> begin_bit) & ((1 << (end_bit - begin_bit)) - 1), km the id
 perm = the stable argsort of f: raw keys and values on the returned side are key[perm] and val[perm].  Every array the hooks see lies
 between 64 guard words that must come back untouched; the b sides and the tail's destination start out as 0xFF bytes."""
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
+
+from util import run_child
 
 pytestmark = pytest.mark.gpu
 
@@ -509,13 +508,4 @@ CHILDREN = {"no_single_launch_sort": ({"LIDARGS_NO_SMALL_SORT": "1"}, _child_no_
 
 @pytest.mark.parametrize("name", list(CHILDREN))
 def test_forms_selected_by_the_environment(name, hip_lib_built):
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), name], env=dict(os.environ, **CHILDREN[name][0]), capture_output=True, text=True, timeout=300)
-    print(r.stdout[-3000:], r.stderr[-3000:])
-    assert r.returncode == 0 and r.stdout.strip().endswith("OK")
-
-
-if __name__ == "__main__":
-    _root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    sys.path[:0] = [_root, os.path.join(_root, "lidar-gs_amd"), os.path.join(_root, "tests")]
-    CHILDREN[sys.argv[1]][1]()
-    print("OK")
+    run_child("import test_sort_gpu as t\nt.CHILDREN[sys.argv[1]][1]()\nprint('OK')", CHILDREN[name][0], (name,), timeout=300)

@@ -4,7 +4,7 @@ drop-in package `diff_lidargs_surfel_rasterization` and the C ABI (lidargs_surfe
 import numpy as np
 import pytest
 
-from util import (GRAD_KEYS_SURFEL, hip_surfel_forward_backward, oracle_surfel_forward_backward, parity, surfel_scene,
+from util import (GRAD_KEYS_SURFEL, hip_surfel_forward_backward, oracle_surfel_forward_backward, parity, run_child, surfel_scene,
                   surfel_upstream_grads)
 
 pytestmark = pytest.mark.gpu
@@ -121,10 +121,9 @@ def test_surfel_pruning_is_invisible(case):
     """LIDARGS_NO_PRUNE=1 bins every tile / row of the reference rect (what the reference does); the default drops those no pixel can
     take (surfel.hip sf_prune).  Same images and gradients either way (up to the summation grouping: the lists are cut into segments by
     length), strictly fewer instances binned."""
-    import os, subprocess, sys, tempfile
+    import os, tempfile
     code = r"""
 import sys, numpy as np
-sys.path[:0] = [%r, %r, %r]
 from test_surfel_gpu import _seam_scene
 from util import hip_surfel_forward_backward, surfel_scene, surfel_upstream_grads, GRAD_KEYS_SURFEL
 from diff_lidargs_rasterization import _C
@@ -135,15 +134,13 @@ if case == "thin":
     scene["opacities"] = (scene["opacities"] * np.float32(0.1)).astype(np.float32)
 hip = hip_surfel_forward_backward(scene, W, H, surfel_upstream_grads(H, W, 5))
 np.savez(sys.argv[1], instances=_C.last_counters()["instances"], **{k: hip[k] for k in ("color", "others", "radii") + GRAD_KEYS_SURFEL})
-"""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = code % (root, os.path.join(root, "lidar-gs_amd"), os.path.join(root, "tests"), case)
+print("OK")
+""" % case
     res = {}
     with tempfile.TemporaryDirectory() as tmp:
         for name, env in (("pruned", {}), ("unpruned", {"LIDARGS_NO_PRUNE": "1"})):
             out = os.path.join(tmp, name + ".npz")
-            r = subprocess.run([sys.executable, "-c", code, out], env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
-            assert r.returncode == 0, r.stderr[-3000:]
+            run_child(code, env, (out,))
             res[name] = dict(np.load(out))
     a, b = res["pruned"], res["unpruned"]
     print(f"[surfel prune, {case}] instances binned: {int(a['instances'])} pruned, {int(b['instances'])} unpruned")

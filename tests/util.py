@@ -68,6 +68,19 @@ def parity(name, hip, ref, rtol=RTOL, floor=FLOOR, verbose=True, scale=None, sof
     return stats
 
 
+def run_child(body, env=None, args=(), timeout=600):
+    """`body` in an interpreter of its own that finds the tree as the tests do, with `env` on top of this process' environment (most
+    switches are read once per process: csrc/switches.h) and `args` as sys.argv[1:].  The tails of both streams are printed; the child
+    must exit with 0 AND end its stdout with the marker OK.  -> the completed process."""
+    import os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = "import sys\nsys.path[:0] = [%r, %r, %r]\n" % (root, os.path.join(root, "lidar-gs_amd"), os.path.join(root, "tests")) + body
+    r = subprocess.run([sys.executable, "-c", code, *args], env=dict(os.environ, **(env or {})), capture_output=True, text=True, timeout=timeout)
+    print(r.stdout[-3000:], r.stderr[-3000:])
+    assert r.returncode == 0 and r.stdout.rstrip().endswith("OK"), (r.returncode, r.stdout[-200:])
+    return r
+
+
 def to_torch(scene, device="cuda"):
     import torch
     return {k: torch.from_numpy(np.ascontiguousarray(v)).to(device) for k, v in scene.items()}
