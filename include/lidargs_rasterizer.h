@@ -646,6 +646,47 @@ int lidargs_debug_gaussian_backward(int P, int line_f4, int stage, const unsigne
                                     float* dL_ddepths, float* dL_dmean3D, float* dL_dsphere_means3D, float* dL_dbasis_u1, float* dL_dbasis_u2,
                                     float* dL_dcov3D, float* dL_dscale, float* dL_drot, unsigned char* tlist, unsigned short* tcount, void* stream);
 
+/* Test hooks of the surfel variant's two per-surfel stages (no reference counterpart as entry points; never called by the binding): the
+ * library's own launchers of the surfel preprocess and of the surfel backward's first and last launches on caller-supplied arrays, so that
+ * tests/ can hold every array they write against a float64 restatement (tests/surfel_ref.py).  Device pointers; nothing waits for the
+ * stream; no dispatch is decided and no environment switch is read here.  Each returns 0 or a negative LIDARGS_ERR_*, the latter before
+ * any device work.
+ *
+ * lidargs_debug_surfel_preprocess: the surfel preprocess of a width x height frame of P surfels with the parameters lidargs_surfel_forward
+ * derives from the same image size.  Inputs as lidargs_surfel_forward's: means3D f32[3 P], colors f32[2 P], opacities f32[P], scales
+ * f32[2 P], rotations f32[4 P], transMat_precomp f32[9 P] (nullable: the rows the blend uses; allowed only next to scales and rotations),
+ * viewmatrix f32[16], beams f32[height]; near_f / far_f the range limits as floats; tile_rows: the tile height the instance total is
+ * counted at (4, 8, 16 or 32); compact: 4-byte span records; prune: the conservative footprint pruning on (an argument, not
+ * LIDARGS_NO_PRUNE: one process can ask for both); filter_only: the visible filter's form of the kernel, which writes radii and radii_xy
+ * alone (every other output and colors / opacities may then be NULL and none is written).
+ *   rec f32[20 P]: the surfel records (written for binned surfels alone); rowspan u32[P] (the same): the reference rect's rows; spans
+ *   u32[P] (compact) or u32[4 P]; key u32[P]: the float bits of the range, 0xFFFFFFFF for surfels binned nowhere; touched u8[P]: cleared;
+ *   totals u32[LG_TOTALS_WORDS = 920]: cleared by the hook, then the 64 slots of block sums (words 8..: one u64 instance total, at
+ *   tile_rows, in the first of four u64 per slot; words 536..: (~smallest, largest) binned key per slot; words 664..: two u64 per slot,
+ *   visible surfels and the reference's tiles_touched); radii i32[P]; radii_xy i32[2 P].
+ *   Refused: P < 0, width <= 0, height < 2 or > 65535; tile_rows not 4, 8, 16 or 32; compact where the image has more than 256 tile
+ *   columns or rows; transMat_precomp without scales or rotations; a NULL required pointer.  P = 0: returns 0, nothing is launched or
+ *   written.
+ *
+ * lidargs_debug_surfel_gaussian_backward: the surfel backward's first launch (the touched lists, the cleared 128-byte lines, the zeroed
+ * rows, with the row widths of lidargs_surfel_backward) on touched u8[P] and gacc f32[32 P], and its last launch, the per-surfel chain on
+ * the listed surfels' lines.  `stage` picks the launches: 1 = the first alone; 2 = the chain alone, on gacc as the caller filled it and on
+ * tlist / tcount as a stage-1 call left them; 0 = both (the chain then reads the zeros the first launch left in the marked lines).
+ * means3D, scales f32[2 P], rotations, transMat_precomp (nullable), viewmatrix, beams f32[height], radii i32[P] as lidargs_surfel_backward's;
+ * the nine gradient arrays and depth f32[P] are lidargs_surfel_backward's, with the same three optional (dL_dnormal, dL_dtransMat,
+ * dL_dtransMat_2dtemp); a stage-1 call needs none of them and skips NULL ones.  tlist u8[P + 256], tcount u16[P / 256 + 64].
+ *   Refused: P < 0, width <= 0, height < 2; stage not 0, 1, 2; a NULL required pointer.  P = 0: returns 0. */
+int lidargs_debug_surfel_preprocess(int P, int width, int height, const float* means3D, const float* colors, const float* opacities,
+                                    const float* scales, float scale_modifier, const float* rotations, const float* transMat_precomp,
+                                    const float* viewmatrix, const float* beams, float near_f, float far_f, int tile_rows, int compact, int prune,
+                                    int filter_only, float* rec, unsigned* rowspan, unsigned* spans, unsigned* key, unsigned char* touched,
+                                    unsigned* totals, int* radii, int* radii_xy, void* stream);
+int lidargs_debug_surfel_gaussian_backward(int P, int width, int height, int stage, const unsigned char* touched, float* gacc, const float* means3D,
+                                           const float* scales, const float* rotations, const float* transMat_precomp, const float* viewmatrix,
+                                           const float* beams, const int* radii, float* dL_dmean2D, float* dL_dnormal, float* dL_dopacity,
+                                           float* dL_dcolor, float* dL_dmean3D, float* dL_dtransMat, float* dL_dtransMat_2dtemp, float* dL_dscale,
+                                           float* dL_drot, float* depth, unsigned char* tlist, unsigned short* tcount, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

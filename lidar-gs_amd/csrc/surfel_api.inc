@@ -18,6 +18,37 @@ static size_t sf_img_carve(char* base, int W, int H, int tiles, SfImgView* v) {
     return (size_t)(c.p - base) + 128;
 }
 
+// The surfel preprocess' parameters of a whole width x height frame at tile height TH: everything but the arrays it writes.  The forward,
+// the visible filter and the test hook (lidargs_debug_surfel_preprocess) all start from here, so the column step is the same value for each.
+static SfPreArgs sf_pre_params(int P, const TileGrid& grid, float scale_modifier, float near_f, float far_f, const float* viewmatrix,
+                               const float* means3D, const float* scales, const float* rotations, const float* beams, int* radii, int* radii_xy) {
+    SfPreArgs pa = SfPreArgs();
+    pa.P = P; pa.W = grid.W; pa.H = grid.H; pa.TH = grid.TH; pa.tiles_x = grid.tiles_x;
+    pa.scale_modifier = scale_modifier; pa.near_f = near_f; pa.far_f = far_f;
+    pa.col_step = 2 * 3.14159265358979323846f / (float)grid.W;
+    pa.view = viewmatrix; pa.means3D = means3D; pa.scales = scales; pa.rotations = rotations; pa.beams = beams;
+    pa.radii = radii; pa.radii_xy = radii_xy;
+    return pa;
+}
+// ... and what the full preprocess reads and writes on top (K2 has none of it)
+static void sf_pre_outputs(SfPreArgs& pa, const float* opacities, const float* colors, const float* transMat, const GeomView& geom, int compact, int prune) {
+    pa.opacities = opacities; pa.colors = colors; pa.transMat = transMat;
+    pa.rec = geom.rec; pa.rowspan = geom.rowspan; pa.spans = geom.spans; pa.dkey = geom.key_a; pa.ids = geom.id_a;
+    pa.inst_slots = reinterpret_cast<unsigned long long*>(geom.totals + LG_TOTALS_SLOT_WORD);
+    pa.diag_slots = reinterpret_cast<unsigned long long*>(geom.totals + LG_TOTALS_DIAG_WORD);
+    pa.key_span = geom.totals + LG_TOTALS_KEYSPAN_WORD;
+    pa.compact = compact; pa.touched = geom.touched; pa.prune = prune;
+}
+
+// The rows the backward's first launch zeroes, with their widths (depth is written for every surfel by k_sf_gaussian_backward)
+static ZeroRows sf_zero_rows(float* dL_dmean2D, float* dL_dnormal, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dtransMat,
+                             float* dL_dtransMat_2dtemp, float* dL_dscale, float* dL_drot) {
+    ZeroRows zr;
+    zr.add(dL_dmean2D, 4); zr.add(dL_dnormal, 3); zr.add(dL_dopacity, 1); zr.add(dL_dcolor, 2); zr.add(dL_dmean3D, 3); zr.add(dL_dtransMat, 9);
+    zr.add(dL_dtransMat_2dtemp, 3); zr.add(dL_dscale, 2); zr.add(dL_drot, 4);
+    return zr;
+}
+
 }  // namespace lg
 
 #define SF_CHECK(what) do { int rc_ = lg::api_check_launch(stream, debug, what); if (rc_) return rc_; } while (0)
@@ -49,7 +80,6 @@ int lidargs_surfel_forward(lidargs_alloc_fn geometry_alloc, void* geometry_user,
     if (P == 0) return 0;
     const int TH = lg::tile_rows();
     const lg::TileGrid grid = lg::make_grid(width, height, TH);
-    lg::SfPreArgs pa = lg::SfPreArgs();
     char* geom_p = geometry_alloc(geometry_user, lg::geom_carve(nullptr, (size_t)P, lg::SURFEL_BUFFERS, nullptr));
     char* img_p = image_alloc(image_user, lg::sf_img_carve(nullptr, width, height, grid.num_tiles(), nullptr));
     if (!geom_p || !img_p) return lg::api_fail(LIDARGS_ERR_ALLOC, "surfel forward: allocator returned NULL");
@@ -59,17 +89,10 @@ int lidargs_surfel_forward(lidargs_alloc_fn geometry_alloc, void* geometry_user,
     lg::prof_begin(stream, 0);
     lg::ImgView tabs = lg::ImgView(); tabs.coltab = img.coltab; tabs.rowtab = img.rowtab;
     lg::launch_setup_tables(beam_inclinations, width, height, tabs, stream);
-    pa.P = P; pa.W = width; pa.H = height; pa.TH = TH; pa.tiles_x = grid.tiles_x;
-    pa.scale_modifier = scale_modifier; pa.near_f = (float)lidar_near; pa.far_f = (float)lidar_far;
-    pa.col_step = 2 * 3.14159265358979323846f / (float)width;
-    pa.view = viewmatrix; pa.means3D = means3D; pa.scales = scales; pa.rotations = rotations; pa.opacities = opacities;
-    pa.colors = colors_precomp; pa.beams = beam_inclinations; pa.radii = radii; pa.radii_xy = radii_xy; pa.transMat = transMat_precomp;
-    pa.rec = geom.rec; pa.rowspan = geom.rowspan; pa.spans = geom.spans; pa.dkey = geom.key_a; pa.ids = geom.id_a;
-    pa.inst_slots = reinterpret_cast<unsigned long long*>(geom.totals + LG_TOTALS_SLOT_WORD);
-    pa.diag_slots = reinterpret_cast<unsigned long long*>(geom.totals + LG_TOTALS_DIAG_WORD);
-    pa.key_span = geom.totals + LG_TOTALS_KEYSPAN_WORD;
-    pa.compact = lg::compact_spans(grid.tiles_x, height) ? 1 : 0;
-    pa.touched = geom.touched; pa.prune = lg::prune_footprints() ? 1 : 0;
+    lg::SfPreArgs pa = lg::sf_pre_params(P, grid, scale_modifier, (float)lidar_near, (float)lidar_far, viewmatrix, means3D, scales, rotations,
+                                         beam_inclinations, radii, radii_xy);
+    lg::sf_pre_outputs(pa, opacities, colors_precomp, transMat_precomp, geom, lg::compact_spans(grid.tiles_x, height) ? 1 : 0,
+                       lg::prune_footprints() ? 1 : 0);
     SF_HIP(hipMemsetAsync(geom.totals, 0, LG_TOTALS_WORDS * sizeof(uint32_t), stream));
     lg::launch_sf_preprocess(pa, false, stream);
     SF_CHECK("surfel preprocess");
@@ -141,9 +164,7 @@ int lidargs_surfel_backward(int P, int D, int M, int R, const float* background,
     lg::BinView bin; L.bin_carve(binning_buffer, &bin);
     lg::SfImgView img; lg::sf_img_carve(image_buffer, width, height, L.grid.num_tiles(), &img);
     lg::prof_begin(stream, 1);
-    lg::ZeroRows zr;                                                   // (depth is written for every surfel by k_sf_gaussian_backward)
-    zr.add(dL_dmean2D, 4); zr.add(dL_dnormal, 3); zr.add(dL_dopacity, 1); zr.add(dL_dcolor, 2); zr.add(dL_dmean3D, 3); zr.add(dL_dtransMat, 9);
-    zr.add(dL_dtransMat_2dtemp, 3); zr.add(dL_dscale, 2); zr.add(dL_drot, 4);
+    const lg::ZeroRows zr = lg::sf_zero_rows(dL_dmean2D, dL_dnormal, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dtransMat, dL_dtransMat_2dtemp, dL_dscale, dL_drot);
     lg::launch_zero_touched(geom.touched, reinterpret_cast<float4*>(geom.gacc), 8, (size_t)P, geom.tlist, geom.tcount, zr, stream);   // the touched surfels' lines + lists, every backward
     lg::prof_mark("bwd_zero", stream);
     lg::SfBwdArgs ba;
@@ -179,14 +200,76 @@ int lidargs_surfel_visible_filter(lidargs_alloc_fn geometry_alloc, void* geometr
     if (!means3D || !scales || !rotations || !viewmatrix || !beam_inclinations || !radii || !radii_xy)
         return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "surfel visible_filter: NULL required pointer");
     const lg::TileGrid grid = lg::make_grid(width, height, lg::tile_rows());
-    lg::SfPreArgs pa = lg::SfPreArgs();
-    pa.P = P; pa.W = width; pa.H = height; pa.TH = grid.TH; pa.tiles_x = grid.tiles_x;
-    pa.scale_modifier = scale_modifier; pa.near_f = (float)lidar_near; pa.far_f = (float)lidar_far;
-    pa.col_step = 2 * 3.14159265358979323846f / (float)width;
-    pa.view = viewmatrix; pa.means3D = means3D; pa.scales = scales; pa.rotations = rotations; pa.beams = beam_inclinations;
-    pa.radii = radii; pa.radii_xy = radii_xy;
+    const lg::SfPreArgs pa = lg::sf_pre_params(P, grid, scale_modifier, (float)lidar_near, (float)lidar_far, viewmatrix, means3D, scales, rotations,
+                                               beam_inclinations, radii, radii_xy);
     lg::launch_sf_preprocess(pa, true, stream);
     SF_CHECK("surfel filter preprocess");
+    return 0;
+}
+
+// Test hooks of the surfel variant's two per-surfel stages: the product's own launchers on caller-supplied arrays; no dispatch is decided here.
+int lidargs_debug_surfel_preprocess(int P, int width, int height, const float* means3D, const float* colors, const float* opacities,
+                                    const float* scales, float scale_modifier, const float* rotations, const float* transMat_precomp,
+                                    const float* viewmatrix, const float* beams, float near_f, float far_f, int tile_rows, int compact, int prune,
+                                    int filter_only, float* rec, unsigned* rowspan, unsigned* spans, unsigned* key, unsigned char* touched,
+                                    unsigned* totals, int* radii, int* radii_xy, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const int debug = 0;
+    if (P < 0 || width <= 0 || height < 2 || height > 65535) return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_surfel_preprocess: bad sizes");
+    if (tile_rows != 4 && tile_rows != 8 && tile_rows != 16 && tile_rows != 32)
+        return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_surfel_preprocess: tile_rows must be 4, 8, 16 or 32");
+    const lg::TileGrid grid = lg::make_grid(width, height, tile_rows);
+    if (compact && !lg::compact_spans(grid.tiles_x, height))
+        return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_surfel_preprocess: compact span records do not hold this image");
+    if (transMat_precomp != nullptr && (!scales || !rotations))
+        return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_surfel_preprocess: transMat_precomp without scales and rotations");
+    if (!means3D || !scales || !rotations || !viewmatrix || !beams || !radii || !radii_xy)
+        return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_surfel_preprocess: NULL required pointer");
+    if (!filter_only && (!colors || !opacities || !rec || !rowspan || !spans || !key || !touched || !totals))
+        return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_surfel_preprocess: NULL required pointer");
+    if (P == 0) return 0;
+    lg::SfPreArgs pa = lg::sf_pre_params(P, grid, scale_modifier, near_f, far_f, viewmatrix, means3D, scales, rotations, beams, radii, radii_xy);
+    if (!filter_only) {
+        lg::GeomView geom; memset(&geom, 0, sizeof geom);
+        geom.rec = reinterpret_cast<float4*>(rec); geom.rowspan = rowspan; geom.spans = reinterpret_cast<uint4*>(spans); geom.key_a = key;
+        geom.touched = touched; geom.totals = totals;
+        lg::sf_pre_outputs(pa, opacities, colors, transMat_precomp, geom, compact ? 1 : 0, prune ? 1 : 0);
+        SF_HIP(hipMemsetAsync(totals, 0, LG_TOTALS_WORDS * sizeof(uint32_t), stream));     // as lidargs_surfel_forward does
+    }
+    lg::launch_sf_preprocess(pa, filter_only != 0, stream);
+    SF_CHECK("debug surfel preprocess");
+    return 0;
+}
+
+int lidargs_debug_surfel_gaussian_backward(int P, int width, int height, int stage, const unsigned char* touched, float* gacc, const float* means3D,
+                                           const float* scales, const float* rotations, const float* transMat_precomp, const float* viewmatrix,
+                                           const float* beams, const int* radii, float* dL_dmean2D, float* dL_dnormal, float* dL_dopacity,
+                                           float* dL_dcolor, float* dL_dmean3D, float* dL_dtransMat, float* dL_dtransMat_2dtemp, float* dL_dscale,
+                                           float* dL_drot, float* depth, unsigned char* tlist, unsigned short* tcount, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const int debug = 0;
+    if (P < 0 || width <= 0 || height < 2) return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_surfel_gaussian_backward: bad sizes");
+    if (stage < 0 || stage > 2) return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_surfel_gaussian_backward: stage must be 0, 1 or 2");
+    if (!touched || !gacc || !tlist || !tcount) return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_surfel_gaussian_backward: NULL required pointer");
+    const bool chain = stage != 1;
+    // the chain's rows, as lidargs_surfel_backward requires them (dL_dnormal, dL_dtransMat, dL_dtransMat_2dtemp stay optional)
+    if (chain && (!means3D || !scales || !rotations || !viewmatrix || !beams || !radii || !dL_dmean2D || !dL_dopacity || !dL_dcolor || !dL_dmean3D ||
+                  !dL_dscale || !dL_drot || !depth))
+        return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_surfel_gaussian_backward: NULL required pointer");
+    if (P == 0) return 0;
+    if (stage != 2) {
+        const lg::ZeroRows zr = lg::sf_zero_rows(dL_dmean2D, dL_dnormal, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dtransMat, dL_dtransMat_2dtemp, dL_dscale, dL_drot);
+        lg::launch_zero_touched(touched, reinterpret_cast<float4*>(gacc), 8, (size_t)P, tlist, tcount, zr, stream);
+        SF_CHECK("debug surfel zero touched");
+    }
+    if (!chain) return 0;
+    lg::SfGaussBwdArgs ga;
+    ga.P = P; ga.W = width; ga.H = height; ga.view = viewmatrix; ga.means3D = means3D; ga.scales = scales; ga.rotations = rotations;
+    ga.beams = beams; ga.radii = radii; ga.transMat = transMat_precomp; ga.gacc = gacc; ga.tlist = tlist; ga.tcount = tcount;
+    ga.dL_dmean2D = dL_dmean2D; ga.dL_dnormal = dL_dnormal; ga.dL_dopacity = dL_dopacity; ga.dL_dcolor = dL_dcolor; ga.dL_dmean3D = dL_dmean3D;
+    ga.dL_dtransMat = dL_dtransMat; ga.dL_dtransMat_2dtemp = dL_dtransMat_2dtemp; ga.dL_dscale = dL_dscale; ga.dL_drot = dL_drot; ga.depth = depth;
+    lg::launch_sf_gaussian_backward(ga, stream);
+    SF_CHECK("debug surfel gaussian backward");
     return 0;
 }
 

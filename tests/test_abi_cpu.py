@@ -69,7 +69,7 @@ def test_parser_against_prototypes_read_by_eye():
     import lidargs_abi
     i, f, d, z, p = ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_size_t, ctypes.c_void_p
     sigs = lidargs_abi.signatures(INCLUDE)
-    assert len(sigs) == 86
+    assert len(sigs) == 88
     ret, args = sigs["lidargs_forward"]
     assert ret is i and len(args) == 34
     assert args[:6] == (p,) * 6                                           # three (allocator, user) pairs
