@@ -281,6 +281,14 @@ int refuse_deterministic(const char* entry) {
     if (!deterministic_requested()) return 0;
     return fail(LIDARGS_ERR_INVALID_ARGUMENT, "%s: LIDARGS_DETERMINISTIC=1 is not supported by this entry point (only lidargs_forward / lidargs_backward are); unset it for this call", entry);
 }
+// LIDARGS_DEPTH=median, the same way: set by the first median forward, never cleared.  Until then a backward launches exactly what it
+// launched before the mode existed; from then on the first blend walk asks the buffer's mode word and k_median_backward is queued
+// (it retires on one load on a default buffer).  The buffer's word decides every result, not this flag.
+std::atomic<bool> g_median_seen{false};
+int refuse_median_depth(const char* entry) {
+    if (!median_depth_requested()) return 0;
+    return fail(LIDARGS_ERR_INVALID_ARGUMENT, "%s: LIDARGS_DEPTH=median is not supported by this entry point (only lidargs_forward / lidargs_backward are); unset it for this call", entry);
+}
 int api_read_words_zero_behind(const uint32_t* dev, int n, uint32_t* out, void* zero, size_t zero_bytes, hipStream_t s) {
     hipError_t e = (hipError_t)read_words_begin(dev, n, s);
     if (e == hipSuccess && zero && zero_bytes) e = hipMemsetAsync(zero, 0, zero_bytes, s);
@@ -486,6 +494,9 @@ struct FrameMode {
     // lidargs_forward under LIDARGS_DETERMINISTIC=1: the geometry buffer is asked for with its 64-bit accumulator lines behind everything
     // else and its mode word set (lidargs_common.h LG_TOTALS_MODE_WORD); every backward on these buffers then adds up in fixed point.
     bool deterministic = false;
+    // lidargs_forward under LIDARGS_DEPTH=median: the image buffer is asked for with the median_id plane behind everything else, the mode
+    // word gets LG_MODE_MEDIAN, and k_render_median overwrites out_depth behind the blend (never together with `deterministic`)
+    bool median = false;
 };
 
 // The preprocess' parameters of a whole frame on `grid`: no column wedge, full span records, pruning on, every row valid.  The forward,
@@ -534,14 +545,18 @@ int forward_impl(lidargs_alloc_fn geometry_alloc, void* geometry_user, lidargs_a
 
     char* geom_p = geometry_alloc(geometry_user, lg::geom_carve(nullptr, (size_t)P, lg::GAUSS_BUFFERS, nullptr, mode.deterministic));
     if (!geom_p) return fail(LIDARGS_ERR_ALLOC, "geometry allocator returned NULL%s");
-    char* img_p = image_alloc(image_user, lg::img_carve(nullptr, width, height, grid4.num_tiles(), nullptr));
+    char* img_p = image_alloc(image_user, lg::img_carve(nullptr, width, height, grid4.num_tiles(), nullptr, mode.median));
     if (!img_p) return fail(LIDARGS_ERR_ALLOC, "image allocator returned NULL%s");
     lg::GeomView geom; lg::geom_carve(geom_p, (size_t)P, lg::GAUSS_BUFFERS, &geom);
     lg::ImgView img; lg::img_carve(img_p, width, height, grid4.num_tiles(), &img);
     LG_HIP(hipMemsetAsync(geom.totals, 0, LG_TOTALS_WORDS * sizeof(uint32_t), stream));
     if (mode.deterministic) {
         lg::g_deterministic_seen.store(true, std::memory_order_relaxed);   // (before the buffer can reach any backward)
-        LG_HIP(hipMemsetD32Async((hipDeviceptr_t)(geom.totals + LG_TOTALS_MODE_WORD), 1, 1, stream));   // (0 = the default, from the line above)
+        LG_HIP(hipMemsetD32Async((hipDeviceptr_t)(geom.totals + LG_TOTALS_MODE_WORD), (int)lg::LG_MODE_DETERMINISTIC, 1, stream));   // (0 = the default, from the line above)
+    }
+    if (mode.median) {
+        lg::g_median_seen.store(true, std::memory_order_relaxed);          // (before the buffer can reach any backward)
+        LG_HIP(hipMemsetD32Async((hipDeviceptr_t)(geom.totals + LG_TOTALS_MODE_WORD), (int)lg::LG_MODE_MEDIAN, 1, stream));
     }
 
     lg::PreprocessParams pp = preprocess_params(P, grid4, scale_modifier, near_f, far_f, shell_lo, shell_hi, viewmatrix);
@@ -605,6 +620,14 @@ int forward_impl(lidargs_alloc_fn geometry_alloc, void* geometry_user, lidargs_a
     LG_STAGE_CHECK("render combine");
     lg::prof_mark("render_combine", stream);
     }
+    if (mode.median) {   // behind either form of the blend: out_depth becomes the median range, the image buffer's last plane names its Gaussian
+        lg::MedianFwdArgs ma;
+        ma.grid = L.grid; ma.ranges = img.ranges; ma.point_list = bin.val_a; ma.rec = geom.rec; ma.rowspan = geom.rowspan;
+        ma.coltab = img.coltab; ma.rowtab = img.rowtab; ma.out_depth = out_depth; ma.median_id = img.median_id;
+        lg::launch_render_median(ma, stream);
+        LG_STAGE_CHECK("render median");
+        lg::prof_mark("render_median", stream);
+    }
 
     // the selection a backward on these buffers will make (backward_impl builds the same view): counted now, while the buffers are certainly alive
     lg::RenderBwdArgs v = lg::RenderBwdArgs();
@@ -646,6 +669,9 @@ int backward_impl(int P, int R, const float* background, int width, int height, 
     // forwards refuse the mode, so their backwards do not look -- and nobody looks in a process that never made a deterministic forward.
     const bool may_be_det = !mode.is_shell && col_lo < 0 && lg::g_deterministic_seen.load(std::memory_order_relaxed);
     const uint32_t* const det_mode = may_be_det ? geom.totals + LG_TOTALS_MODE_WORD : nullptr;
+    // The depth mode travels in the same word (LG_MODE_MEDIAN), under the same rules: only lidargs_forward makes median buffers, and
+    // nobody looks before this process has made one.
+    const bool may_be_median = !mode.is_shell && col_lo < 0 && lg::g_median_seen.load(std::memory_order_relaxed);
     // a column wedge's buffers: only its own patches were rendered
     if (col_lo >= 0 && (col_lo % LG_TILE_W || col_hi <= col_lo || col_hi > width)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "backward: bad column wedge%s");
     const lg::FrameLayout L = lg::frame_layout(R, width, height, col_lo, col_hi, mode.is_shell ? lg::FRAME_SHELL : lg::FRAME_GAUSS);   // (from the forward's num_rendered)
@@ -671,10 +697,20 @@ int backward_impl(int P, int R, const float* background, int width, int height, 
     rb.T_final_global = mode.T_final_global; rb.behind = mode.behind;
     rb.dL_dpix = dL_dpix; rb.dL_ddepth = dL_dout_depth; rb.dL_docc = dL_dout_occ; rb.gacc = geom.gacc;
     if (L.work_list) rb.walk = lg::work_list(bin);
-    rb.det_mode = det_mode; rb.acc64 = geom.acc64;
+    rb.det_mode = (may_be_det || may_be_median) ? geom.totals + LG_TOTALS_MODE_WORD : nullptr;
+    rb.acc64 = may_be_det ? geom.acc64 : nullptr;
     lg::launch_render_backward(rb, stream);
     LG_STAGE_CHECK("render backward");
     lg::prof_mark("render_bwd", stream);
+    if (may_be_median) {
+        // (img.median_id is computed from the default size of the image buffer: on a default buffer it points behind it and is never read)
+        lg::MedianBwdArgs mb;
+        mb.mode = geom.totals + LG_TOTALS_MODE_WORD; mb.median_id = img.median_id; mb.dL_ddepth = dL_dout_depth; mb.gacc = geom.gacc;
+        mb.N = (size_t)width * height; mb.P = (uint32_t)P;
+        lg::launch_median_backward(mb, stream);
+        LG_STAGE_CHECK("median backward");
+        lg::prof_mark("median_bwd", stream);
+    }
 
     lg::GaussBwdArgs gb;
     gb.P = P; gb.scale_modifier = scale_modifier;
@@ -710,6 +746,9 @@ int lidargs_forward(lidargs_alloc_fn geometry_alloc, void* geometry_user, lidarg
     const float inf = std::numeric_limits<float>::infinity();
     FrameMode mode;
     mode.deterministic = lg::deterministic_requested();
+    mode.median = lg::median_depth_requested();
+    if (mode.deterministic && mode.median)   // (the median mode's depth gradient is added with a float atomic: not what the other switch promises)
+        return fail(LIDARGS_ERR_INVALID_ARGUMENT, "%s: LIDARGS_DEPTH=median is not supported together with LIDARGS_DETERMINISTIC=1; unset one of them for this call", "lidargs_forward");
     return forward_impl(geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user, P, background, width,
                         height, means3D, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix,
                         beam_inclinations, (float)lidar_near, (float)lidar_far, -inf, inf, nullptr, 0, out_color, out_depth,
@@ -725,6 +764,7 @@ int lidargs_forward_enqueue(lidargs_alloc_fn geometry_alloc, void* geometry_user
                             int* radii, int* radii_xy, int debug, int instance_capacity, int tile_rows, unsigned* status_host, void* stream) {
     (void)D; (void)M; (void)shs; (void)projmatrix; (void)cam_pos; (void)prefiltered;
     if (const int rc = lg::refuse_deterministic("lidargs_forward_enqueue")) return rc;
+    if (const int rc = lg::refuse_median_depth("lidargs_forward_enqueue")) return rc;
     if (instance_capacity <= 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward_enqueue: instance_capacity must be positive%s");
     const float inf = std::numeric_limits<float>::infinity();
     FrameMode mode;
@@ -995,6 +1035,7 @@ int lidargs_forward_shell(lidargs_alloc_fn geometry_alloc, void* geometry_user, 
                           const float* T_in, int transmittance_pass, float* out_color, float* out_depth, float* out_occ,
                           float* T_out, int* radii, int* radii_xy, int debug, void* stream) {
     if (const int rc = lg::refuse_deterministic("lidargs_forward_shell")) return rc;
+    if (const int rc = lg::refuse_median_depth("lidargs_forward_shell")) return rc;
     FrameMode mode;
     mode.is_shell = true;
     return forward_impl(geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user, P, background, width,
@@ -1012,6 +1053,7 @@ int lidargs_forward_shell_enqueue(lidargs_alloc_fn geometry_alloc, void* geometr
                                   float* T_out, int* radii, int* radii_xy, int debug, const unsigned* n_valid, int instance_capacity,
                                   int tile_rows, unsigned* status_host, void* stream) {
     if (const int rc = lg::refuse_deterministic("lidargs_forward_shell_enqueue")) return rc;
+    if (const int rc = lg::refuse_median_depth("lidargs_forward_shell_enqueue")) return rc;
     if (instance_capacity <= 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward_shell_enqueue: instance_capacity must be positive%s");
     FrameMode mode;
     mode.is_shell = true; mode.n_valid = n_valid;
@@ -1030,6 +1072,7 @@ int lidargs_forward_wedge(lidargs_alloc_fn geometry_alloc, void* geometry_user, 
                           const float* beam_inclinations, int lidar_far, int lidar_near, int col_lo, int col_hi, float* out_color,
                           float* out_depth, float* out_occ, int* radii, int* radii_xy, int debug, void* stream) {
     if (const int rc = lg::refuse_deterministic("lidargs_forward_wedge")) return rc;
+    if (const int rc = lg::refuse_median_depth("lidargs_forward_wedge")) return rc;
     if (col_lo < 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward_wedge: col_lo < 0%s");
     // lidargs_wedge_select_count bounds a Gaussian's reach from its scales and rotation; a precomputed covariance has no such bound
     // there, and a wedge rendered from an under-selected set would silently miss its boundary Gaussians
@@ -1051,6 +1094,7 @@ int lidargs_forward_wedge_enqueue(lidargs_alloc_fn geometry_alloc, void* geometr
                                   float* out_depth, float* out_occ, int* radii, int* radii_xy, int debug, const unsigned* n_valid,
                                   int instance_capacity, int tile_rows, unsigned* status_host, void* stream) {
     if (const int rc = lg::refuse_deterministic("lidargs_forward_wedge_enqueue")) return rc;
+    if (const int rc = lg::refuse_median_depth("lidargs_forward_wedge_enqueue")) return rc;
     if (col_lo < 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward_wedge: col_lo < 0%s");
     if (cov3D_precomp) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward_wedge: cov3D_precomp is not supported on the column-wedge path (give scales + rotations)%s");
     if (instance_capacity <= 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward_wedge_enqueue: instance_capacity must be positive%s");

@@ -107,7 +107,11 @@ __device__ __forceinline__ uint2 span_unpack(uint32_t w) {            // -> (xsp
 // Word 4 now carries the forward's accumulation mode to every backward on the buffer: 0 (the forward's memset) = float atomics,
 // 1 = deterministic (LIDARGS_DETERMINISTIC=1 at the forward: the geometry buffer then ends in GeomView::acc64).  The backward's
 // KERNELS read it; the host never does, so a cloned or offloaded buffer carries its mode along and no backward waits for a read.
+// Bit 1 (LIDARGS_DEPTH=median at the forward): out_depth is the median range and the image buffer ends in ImgView::median_id; the
+// backward's blend then treats dL/ddepth as zero and k_median_backward sends it to the one Gaussian each pixel names.  The two modes
+// exclude each other (lidargs_forward refuses both at once: the median add is a float atomic), so the word is 0, 1 or 2.
 #define LG_TOTALS_MODE_WORD 4
+constexpr uint32_t LG_MODE_DETERMINISTIC = 1u, LG_MODE_MEDIAN = 2u;
 // behind the status words: LG_INST_SLOTS slots of (~smallest, largest) range key of the frame's visible Gaussians (atomicMax of the
 // preprocess blocks, spread over the slots like the instance totals; all start at 0, so an empty frame reads kmin = 0xFFFFFFFF,
 // kmax = 0).  The host folds them after its one read: the range sort then works on key - kmin and needs only as many passes as the
@@ -263,9 +267,13 @@ struct ImgView {
     uint2* ranges;        // [tiles]
     float2* coltab;       // [W]  (cos beta, sin beta)
     float2* rowtab;       // [H]  (cos alpha, sin alpha) of pixel row y
+    uint32_t* median_id;  // [N] median mode only (behind everything else, as GeomView::acc64 is: the default buffer is byte for byte what it
+                          //     was): the Gaussian whose range the pixel returned, 0xFFFFFFFF = none (render.hip k_render_median)
 };
 
-inline size_t img_carve(char* base, int W, int H, int tiles, ImgView* v) {
+// median: carve ImgView::median_id as well.  The forward asks for it only under LIDARGS_DEPTH=median; a backward always computes the
+// address (it does not know the mode) and hands it to a kernel that reads it only where the buffer's mode word says it is there.
+inline size_t img_carve(char* base, int W, int H, int tiles, ImgView* v, bool median = false) {
     Carver c(base);
     ImgView m;
     size_t N = (size_t)W * H;
@@ -274,8 +282,10 @@ inline size_t img_carve(char* base, int W, int H, int tiles, ImgView* v) {
     m.ranges = c.take<uint2>(tiles);
     m.coltab = c.take<float2>(W);
     m.rowtab = c.take<float2>(H);
+    const size_t plain = (size_t)(c.p - base) + 128;
+    m.median_id = c.take<uint32_t>(N);
     if (v) *v = m;
-    return (size_t)(c.p - base) + 128;
+    return median ? (size_t)(c.p - base) + 128 : plain;
 }
 
 // Tile grid: 16 columns x TH rows (TH multiple of 4); each tile is rendered by TH/4 waves.
@@ -332,6 +342,7 @@ void lane_stats_read(unsigned long long* out, int reset);              // render
 int api_fail(int code, const char* msg);
 int api_check_launch(hipStream_t s, int debug, const char* what);
 int refuse_deterministic(const char* entry);    // 0, or LIDARGS_ERR_INVALID_ARGUMENT (message set) when the switch is on: entry points the mode does not cover
+int refuse_median_depth(const char* entry);     // the same for LIDARGS_DEPTH=median
 // Device -> host read of `n` (<= 1024) words with `zero_bytes` at `zero` cleared BEHIND the copy on the same stream: the host waits
 // for the copy only.  Returns a hipError_t.
 int api_read_words_zero_behind(const uint32_t* dev, int n, uint32_t* out, void* zero, size_t zero_bytes, hipStream_t s);
@@ -373,7 +384,7 @@ int bin_frame(const BinSpec& spec, const GeomView& geom, uint2* ranges, size_t P
 // lists the touched Gaussians per region (tlist / tcount of the geometry view) and zeroes every row of the caller's gradient arrays.
 struct ZeroRows { static constexpr int MAX = 12; float* p[MAX]; int w[MAX]; int n = 0;   // arrays of P rows of w floats (w = 1, 2, 3, 4, 6 or 9)
                   void add(float* q, int width) { if (q && n < MAX) { p[n] = q; w[n] = width; n++; } } };
-// det_mode / acc64 (optional): where *det_mode != 0 the touched Gaussians' 128-byte fixed-point lines are cleared as well
+// det_mode / acc64 (optional): where *det_mode has LG_MODE_DETERMINISTIC the touched Gaussians' 128-byte fixed-point lines are cleared as well
 void launch_zero_touched(const uint8_t* touched, float4* acc, int line_f4, size_t P, uint8_t* tlist, uint16_t* tcount, const ZeroRows& zr, hipStream_t s,
                          const uint32_t* det_mode = nullptr, long long* acc64 = nullptr);
 // touched[i] = 1 for all P (frames whose forward writes no contribution flags: every listed entry is walked, so every visible Gaussian counts)
@@ -543,13 +554,29 @@ struct RenderBwdArgs {
     float* gacc;                   // [16P], zeroed: slots 0-2 mean2D.xyz, 3-5 conic A,B,C, 6 opacity, 7-8 colour,
                                    //               9 range, 10-12 G1 = sum gx delta, 13-15 G2 = sum gy delta (moments of dL/du1, dL/du2)
     WorkList walk;                 // the list k_render_combine filled; cnt == nullptr: the slot grid
-    const uint32_t* det_mode = nullptr;   // the buffer's mode word (LG_TOTALS_MODE_WORD), nullptr = float atomics whatever it says
-    long long* acc64 = nullptr;           // [16P] GeomView::acc64, touched only where *det_mode != 0
+    const uint32_t* det_mode = nullptr;   // the buffer's mode word (LG_TOTALS_MODE_WORD), nullptr = float atomics and the expected range whatever it says
+    long long* acc64 = nullptr;           // [16P] GeomView::acc64, touched only where *det_mode has LG_MODE_DETERMINISTIC; nullptr = no forward of
+                                          //       this process has made deterministic buffers (the mode word is then looked at for the median bit alone)
 };
-// det_mode == nullptr: one launch, float atomics.  Otherwise the walk is launched in the form that asks the mode word, and a second
+// det_mode == nullptr: one launch, float atomics.  Otherwise the walk is launched in the form that asks the mode word (on a median
+// buffer it takes dL/ddepth as zero: k_median_backward delivers it), and -- with acc64 -- a second
 // launch follows, which retires on one scalar load unless the buffer is a deterministic forward's: there the first walk leaves
 // max |term| per (Gaussian, slot) in gacc, the second adds the terms up as 64-bit integers on the grid that maximum fixes (det_encode).
 void launch_render_backward(const RenderBwdArgs& a, hipStream_t s);
+
+// LIDARGS_DEPTH=median (DESIGN.md "Median-range depth").  Forward: behind the blend, one wave per 16 x 4 patch walks the tile's list from
+// T = 1 until every pixel's transmittance has fallen to one half, overwrites out_depth with the range of the last entry taken above one
+// half and names that Gaussian in median_id.  Backward: dL_ddepth[pixel] is added (weight 1) to the range slot of that Gaussian's packed
+// line; a fixed small grid that retires on one load unless the buffer's mode word has LG_MODE_MEDIAN.
+struct MedianFwdArgs {
+    TileGrid grid;
+    const uint2* ranges; const uint32_t* point_list; const float4* rec; const uint32_t* rowspan;
+    const float2* coltab; const float2* rowtab;
+    float* out_depth; uint32_t* median_id;
+};
+void launch_render_median(const MedianFwdArgs& a, hipStream_t s);
+struct MedianBwdArgs { const uint32_t* mode; const uint32_t* median_id; const float* dL_ddepth; float* gacc; size_t N; uint32_t P; };
+void launch_median_backward(const MedianBwdArgs& a, hipStream_t s);
 void launch_count_backward_entries(const RenderBwdArgs& a, unsigned long long* out, hipStream_t s);   // diagnostics: adds the list entries k_render_backward gathers to *out
 // diagnostics of a forward (lidargs_last_counters): host-side counters; with lidargs_counters_enable(1) also queues the counting launches.
 // view: the selection a backward on these buffers will make, or NULL
@@ -564,7 +591,7 @@ struct GaussBwdArgs {
     float* dL_dmean2D; float* dL_dconic; float* dL_dopacity; float* dL_dcolor; float* dL_ddepths;
     float* dL_dbasis_u1; float* dL_dbasis_u2;
     float* dL_dsphere; float* dL_dmean3D; float* dL_dcov3D; float* dL_dscale; float* dL_drot;
-    const uint32_t* det_mode = nullptr; const long long* acc64 = nullptr;   // as in RenderBwdArgs: where *det_mode != 0 a line is det_decode(gacc, acc64)
+    const uint32_t* det_mode = nullptr; const long long* acc64 = nullptr;   // as in RenderBwdArgs: where *det_mode has LG_MODE_DETERMINISTIC a line is det_decode(gacc, acc64)
 };
 void launch_gaussian_backward(const GaussBwdArgs& a, hipStream_t s);
 

@@ -457,7 +457,7 @@ __device__ __forceinline__ void gb_row(const GaussBwdArgs& a, const int idx) {
 #else
     float4 q0 = acc[0], q1 = acc[1], q2 = acc[2], q3 = acc[3];
 #endif
-    if (a.det_mode && *a.det_mode != 0u) {
+    if (a.det_mode && (*a.det_mode & LG_MODE_DETERMINISTIC) != 0u) {
         // deterministic buffers (lidargs_common.h "deterministic accumulation"): the float line holds each slot's largest term, the
         // sums are the 64-bit line's, read on the grid that term fixes
         const longlong2* w = reinterpret_cast<const longlong2*>(a.acc64 + 16 * (size_t)idx);
@@ -667,7 +667,7 @@ __global__ void __launch_bounds__(LG_REGION) k_zero_touched(const uint8_t* __res
             if (mine >= 0) acc[(wbase + (size_t)mine) * LINE + part] = z;
         }
     }
-    if (det_mode && *det_mode != 0u && mark) {                         // deterministic buffers: the marked Gaussians' 128-byte fixed-point lines too
+    if (det_mode && (*det_mode & LG_MODE_DETERMINISTIC) != 0u && mark) {                         // deterministic buffers: the marked Gaussians' 128-byte fixed-point lines too
         float4* const w = reinterpret_cast<float4*>(acc64 + 16 * i);
 #pragma unroll
         for (int k = 0; k < 8; k++) w[k] = make_float4(0.f, 0.f, 0.f, 0.f);

@@ -312,6 +312,20 @@ __device__ __forceinline__ void walk_T_only_v2(const int cnt, const float4* s_re
 // An entry a live pixel does not take has alpha_eff = 0: test = Tw exactly, blended with weight 0.  The same products and sums in
 // the same order as the first form.  T_break (only ever compared with 1e-4 by its consumers -- the combine's stop test, the shells'
 // compose) is T while the pixel is live and 0 once its walk has tripped here.
+// alpha of one parked entry (park_record / park_compact: r0 = s.xyz | B, r1, r2) for the pixel looking along (qxy, qz), `op` being the
+// entry's opacity on the pixel's row (0 outside its row span: the rect's row test); 0 where the pixel does not take the entry.  The
+// one text of the expression for the full walk below and the median walk (k_render_median), which must take exactly the same entries.
+__device__ __forceinline__ float entry_alpha(const float4& r0, const float4& r1, const float4& r2, const float op, const v2f qxy, const float qz) {
+    const v2f exy = v2f{r0.x, r0.y} - qxy;
+    const float ez = r0.z - qz;
+    const v2f d = exy.x * v2f{r1.x, r1.y} + exy.y * v2f{r1.z, r1.w} + ez * v2f{r2.x, r2.y};
+    const v2f qd = v2f{r2.z, r2.w} * d * d;
+    const float power = -0.5f * (qd.x + qd.y) - r0.w * d.x * d.y;   // :601
+    const float pw = (power <= 0.0f) ? power : -INFINITY;             // :602
+    const float alpha = fminf(0.99f, op * LG_EXPF(pw));
+    return (alpha >= 1.0f / 255.0f) ? alpha : 0.f;                    // :605
+}
+
 template <bool TRACK>
 __device__ __forceinline__ void walk_full_v2(const int cnt, const float4* s_rec, const float* oprow, const v2f qxy, const float qz, WalkState& w) {
     struct Rec { float4 r0, r1, r2, r3; float op; };
@@ -323,16 +337,7 @@ __device__ __forceinline__ void walk_full_v2(const int cnt, const float4* s_rec,
         r.op = lds_ahead(&oprow[4 * jj]);
         return r;
     };
-    auto alpha_eff = [&](const Rec& r) {
-        const v2f exy = v2f{r.r0.x, r.r0.y} - qxy;
-        const float ez = r.r0.z - qz;
-        const v2f d = exy.x * v2f{r.r1.x, r.r1.y} + exy.y * v2f{r.r1.z, r.r1.w} + ez * v2f{r.r2.x, r.r2.y};
-        const v2f qd = v2f{r.r2.z, r.r2.w} * d * d;
-        const float power = -0.5f * (qd.x + qd.y) - r.r0.w * d.x * d.y;   // :601
-        const float pw = (power <= 0.0f) ? power : -INFINITY;             // :602
-        const float alpha = fminf(0.99f, r.op * LG_EXPF(pw));
-        return (alpha >= 1.0f / 255.0f) ? alpha : 0.f;                    // :605
-    };
+    auto alpha_eff = [&](const Rec& r) { return entry_alpha(r.r0, r.r1, r.r2, r.op, qxy, qz); };
     const bool was_done = w.done;
     float Tw = was_done ? -w.T : w.T;
     v2f C01 = w.C01; float D = w.D; uint32_t last = w.last;
@@ -953,6 +958,60 @@ void launch_render_combine(const RenderFwdArgs& a, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// LIDARGS_DEPTH=median: the median range of every pixel, in a launch of its own behind the blend (whichever form that took).
+// One wave64 per 16 x 4 patch walks its tile's list in list order from T = 1, 64 records at a time through LDS.  Per pixel, for every
+// entry it takes (entry_alpha: the full walk's membership, skips and alpha):
+//     if T > 0.5:  median = the entry's range, median_id = its Gaussian;      then  T *= 1 - alpha
+// so the pixel ends with the entry at which T falls through one half -- or its last taker, if T never gets there; no taker: range 0,
+// id 0xFFFFFFFF.  The blend's T < 1e-4 stop cannot fire above one half (alpha <= 0.99 leaves T >= 0.005), so above one half this walk
+// and the blend's see the same T.  A plain serial walk on purpose: it leaves when every pixel of the patch is at T <= 0.5, which on
+// saturating frames is a few entries in; the blend kernels are not touched.
+__global__ void __launch_bounds__(64) k_render_median(const MedianFwdArgs a) {
+    __shared__ float4 s_rec[4 * LG_CHUNK];
+    __shared__ float4 s_oprow[LG_CHUNK];
+    __shared__ uint32_t s_gid[LG_CHUNK];
+    const int lane = threadIdx.x;
+    const int wpt = a.grid.waves_per_tile;
+    const int patch = a.grid.global_patch(blockIdx.x);
+    const int tile = patch / wpt, sub = patch - tile * wpt;
+    const uint2 tr = a.ranges[tile];
+    const uint32_t n = tr.y - tr.x;
+    const PixelSetup px = pixel_setup(a.grid, a.coltab, a.rowtab, tile, sub, lane);
+    const int y0 = (tile / a.grid.tiles_x) * a.grid.TH + sub * LG_WAVE_ROWS;       // first pixel row of the patch
+    const float* oprow = reinterpret_cast<const float*>(s_oprow) + (lane >> 4);
+    const v2f qxy = v2f{px.q.x, px.q.y};
+
+    float T = 1.0f, range = 0.f;
+    uint32_t id = 0xFFFFFFFFu;
+    bool open = px.inside;                                             // T > 0.5: the next entry taken is still a candidate
+    const uint32_t nchunks = (n + LG_CHUNK - 1) / LG_CHUNK;
+    for (uint32_t c = 0; c < nchunks && __ballot(open) != 0ull; c++) { // (wave-uniform: the workgroup is one wave)
+        const uint32_t k = c * LG_CHUNK + (uint32_t)lane;
+        const bool have = k < n;
+        const uint32_t g = have ? a.point_list[tr.x + k] : 0u;
+        const Staged st = gather_record(a.rec, a.rowspan, g, have);
+        __syncthreads();
+        park_record(s_rec, lane, st);
+        s_oprow[lane] = rows_opacity(st.span, st.a3.y, y0);
+        s_gid[lane] = g;
+        __syncthreads();
+        const int cnt = (int)min((uint32_t)LG_CHUNK, n - c * LG_CHUNK);
+        for (int j = 0; j < cnt && __ballot(open) != 0ull; j++) {
+            const float alpha = entry_alpha(s_rec[j], s_rec[LG_CHUNK + j], s_rec[2 * LG_CHUNK + j], oprow[4 * j], qxy, px.q.z);
+            const bool take = open && alpha > 0.f;
+            range = take ? s_rec[3 * LG_CHUNK + j].x : range;
+            id = take ? s_gid[j] : id;
+            T = take ? T * (1.f - alpha) : T;
+            open = open && T > 0.5f;
+        }
+    }
+    if (px.inside) { a.out_depth[px.pix] = range; a.median_id[px.pix] = id; }
+}
+void launch_render_median(const MedianFwdArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(k_render_median, dim3((unsigned)a.grid.window_patches()), dim3(64), 0, s, a);
+}
+
+// ------------------------------------------------------------------------------------------------
 // Cross-lane exchanges for the reduce-scatter below.
 __device__ __forceinline__ float xchg_xor1(float x) {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xF, 0xF, true));   // quad_perm [1,0,3,2]
@@ -1013,7 +1072,7 @@ __device__ __forceinline__ float reduce_scatter16(float (&v)[16], int lane) {
 // terms are the same numbers in whatever order the workgroups run.
 enum { BWD_PLAIN = 0, BWD_FIRST = 1, BWD_SECOND = 2 };
 template <bool V2, int MODE>
-__device__ __forceinline__ void backward_walk(const RenderBwdArgs& a, const unsigned bid, const bool det) {
+__device__ __forceinline__ void backward_walk(const RenderBwdArgs& a, const unsigned bid, const bool det, const bool median) {
     constexpr bool SECOND = MODE == BWD_SECOND;
     constexpr int OFS = V2 ? 2 : 0;                                    // slack slots below slot 0 (V2's look-ahead reads)
     __shared__ float4 s_rec_[4 * (LG_CHUNK + OFS)];
@@ -1080,6 +1139,9 @@ __device__ __forceinline__ void backward_walk(const RenderBwdArgs& a, const unsi
     const float T_final = px.inside ? (a.T_final_global ? a.T_final_global[px.pix] : a.final_T[px.pix]) : 0.f;
     float g0 = 0.f, g1 = 0.f, gd = 0.f, go = 0.f;
     if (px.inside) { g0 = a.dL_dpix[px.pix]; g1 = a.dL_dpix[N + px.pix]; gd = a.dL_ddepth[px.pix]; go = a.dL_docc[px.pix]; }
+    // median buffers (LG_MODE_MEDIAN): out_depth is not the blend's sum, so neither its term in dL/dalpha nor w dL/ddepth exists here --
+    // k_median_backward hands each pixel's dL/ddepth to the one Gaussian whose range it returned.  (Wave-uniform; false by constant in the plain form.)
+    if (median) gd = 0.f;
     const float bgdot = a.bg ? (a.bg[0] * g0 + a.bg[1] * g1) : 0.f;
     Staged st; uint32_t gid = 0u; bool have = false;
     if (V2) { have = have_first; gid = have ? g_first : 0u; st = gather_record(a.rec, a.rowspan, g_first, have); }   // behind the ids, in front of the plane sums
@@ -1279,13 +1341,14 @@ template <bool V2>
 __attribute__((amdgpu_waves_per_eu(LG_BWD_WAVES, LG_BWD_WAVES)))
 #endif
 __global__ void __launch_bounds__(64) k_render_backward(const RenderBwdArgs a) {
-    backward_walk<V2, BWD_PLAIN>(a, blockIdx.x, false);
+    backward_walk<V2, BWD_PLAIN>(a, blockIdx.x, false, false);
 }
-// the first walk on buffers that may be deterministic: their mode word decides what the sums are combined with
+// the first walk on buffers that may be deterministic or median ones: their mode word decides what the sums are combined with and
+// whether the blend owns dL/ddepth
 template <bool V2>
 __global__ void __launch_bounds__(64) k_render_backward_first(const RenderBwdArgs a) {
-    const bool det = *a.det_mode != 0u;                                // (a scalar load, needed at the first entry's atomic)
-    backward_walk<V2, BWD_FIRST>(a, blockIdx.x, det);
+    const uint32_t mode = *a.det_mode;                                 // (a scalar load, needed at the first entry's atomic)
+    backward_walk<V2, BWD_FIRST>(a, blockIdx.x, (mode & LG_MODE_DETERMINISTIC) != 0u, (mode & LG_MODE_MEDIAN) != 0u);
 }
 
 // The deterministic mode's second walk.  The host does not know the buffers' mode (it travels in them), so this is launched behind every
@@ -1294,8 +1357,8 @@ __global__ void __launch_bounds__(64) k_render_backward_first(const RenderBwdArg
 #define LG_DET_GRID 4096                 // 16 single-wave workgroups per CU (what the 9.7 KB of LDS admit) on 256 CUs
 template <bool V2>
 __global__ void __launch_bounds__(64) k_render_backward_det(const RenderBwdArgs a, const unsigned slots) {
-    if (*a.det_mode == 0u) return;
-    for (unsigned bid = blockIdx.x; bid < slots; bid += gridDim.x) backward_walk<V2, BWD_SECOND>(a, bid, true);
+    if ((*a.det_mode & LG_MODE_DETERMINISTIC) == 0u) return;
+    for (unsigned bid = blockIdx.x; bid < slots; bid += gridDim.x) backward_walk<V2, BWD_SECOND>(a, bid, true, false);   // (never a median buffer: the forward refuses both)
 }
 
 // Diagnostics (lidargs_counters_enable + lidargs_last_counters, outside any timed region): the list entries k_render_backward gathers for a frame -- per (patch,
@@ -1339,9 +1402,28 @@ void launch_render_backward(const RenderBwdArgs& a, hipStream_t s) {
     if (!blocks) return;
     if (walk2() & 4) hipLaunchKernelGGL(k_render_backward_first<true>, dim3(blocks), dim3(64), 0, s, a);
     else hipLaunchKernelGGL(k_render_backward_first<false>, dim3(blocks), dim3(64), 0, s, a);
+    if (!a.acc64) return;                                              // no deterministic buffer in this process: the word was asked for the median bit
     const unsigned grid = blocks < (unsigned)LG_DET_GRID ? blocks : (unsigned)LG_DET_GRID;
     if (walk2() & 4) hipLaunchKernelGGL(k_render_backward_det<true>, dim3(grid), dim3(64), 0, s, a, blocks);
     else hipLaunchKernelGGL(k_render_backward_det<false>, dim3(grid), dim3(64), 0, s, a, blocks);
+}
+
+// The median mode's depth gradient: out_depth[pixel] = range of Gaussian median_id[pixel], so dL_ddepth[pixel] goes, with weight 1, into
+// the range slot (9) of that Gaussian's packed line -- a taker of the forward, hence marked as touched: its line was cleared by
+// k_zero_touched and is read by k_gaussian_backward, which carries the sum into the mean.  The host does not know the buffers' mode:
+// launched in every backward of a process that has made median buffers, a fixed small grid that retires on one load on a default buffer
+// (where median_id points behind the image buffer and is never read).
+#define LG_MEDIAN_GRID 1024
+__global__ void __launch_bounds__(256) k_median_backward(const MedianBwdArgs a) {
+    if ((*a.mode & LG_MODE_MEDIAN) == 0u) return;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < a.N; i += (size_t)gridDim.x * 256) {
+        const uint32_t g = a.median_id[i];
+        if (g < a.P) atomicAdd(a.gacc + 16 * (size_t)g + 9, a.dL_ddepth[i]);   // (0xFFFFFFFF: no taker)
+    }
+}
+void launch_median_backward(const MedianBwdArgs& a, hipStream_t s) {
+    const size_t want = (a.N + 255) / 256;
+    hipLaunchKernelGGL(k_median_backward, dim3((unsigned)(want < LG_MEDIAN_GRID ? want : LG_MEDIAN_GRID)), dim3(256), 0, s, a);
 }
 
 }  // namespace lg

@@ -75,6 +75,11 @@ inline bool uses_small_sort(size_t n) { return n <= switches().small_sort_max &&
 // function of its inputs (lidargs_common.h "deterministic accumulation").  Read at EVERY call (a caller may flip it between two frames of
 // one process), and by forward entry points only: a backward takes the mode from the buffers.  Unset, empty, 0: off.
 inline bool deterministic_requested() { return env_on("LIDARGS_DETERMINISTIC"); }
+// LIDARGS_DEPTH=median: a supported mode -- lidargs_forward returns the median range per pixel (the range of the Gaussian at which the
+// transmittance falls through one half: render.hip k_render_median) instead of the expected range, and makes buffers on which every
+// lidargs_backward sends a pixel's depth gradient to that one Gaussian.  Read at EVERY call, by forward entry points only (the mode
+// travels in the buffers, like the deterministic one).  Only the literal value `median` turns it on: unset, empty, anything else = expected.
+inline bool median_depth_requested() { const char* e = getenv("LIDARGS_DEPTH"); return e && strcmp(e, "median") == 0; }
 // LIDARGS_NG_FORWARD_T16=0, LIDARGS_NG_BACKWARD_T16=0 (first character '0'): the decode's forward / backward on the 32x32x2 kernels, which
 // k = 8, 10 take in any case, instead of the 16x16x4 ones (A/B, test variants)
 inline bool ng_forward_t16_allowed() { return !env_starts_with("LIDARGS_NG_FORWARD_T16", '0'); }

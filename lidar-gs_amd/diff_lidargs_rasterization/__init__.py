@@ -21,7 +21,14 @@ import torch.nn as nn
 
 from . import _C
 
-__all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians"]
+__all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "depth_mode"]
+
+
+def depth_mode():
+    """Which depth the next forward of this process returns: "median" (the range of the Gaussian at which the transmittance falls through
+    one half; LIDARGS_DEPTH=median, read by the library at every lidargs_forward) or "expected" (sum of range x alpha x T: unset, empty or
+    any other value).  The backward follows the forward that made its buffers, not the environment at its own time."""
+    return "median" if os.environ.get("LIDARGS_DEPTH") == "median" else "expected"
 
 
 class GaussianRasterizationSettings(NamedTuple):
