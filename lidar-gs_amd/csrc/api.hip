@@ -281,13 +281,14 @@ int refuse_deterministic(const char* entry) {
     if (!deterministic_requested()) return 0;
     return fail(LIDARGS_ERR_INVALID_ARGUMENT, "%s: LIDARGS_DETERMINISTIC=1 is not supported by this entry point (only lidargs_forward / lidargs_backward are); unset it for this call", entry);
 }
-// LIDARGS_DEPTH=median, the same way: set by the first median forward, never cleared.  Until then a backward launches exactly what it
-// launched before the mode existed; from then on the first blend walk asks the buffer's mode word and k_median_backward is queued
-// (it retires on one load on a default buffer).  The buffer's word decides every result, not this flag.
+// LIDARGS_DEPTH=median / strongest, the same way: set by the first forward whose depth is one Gaussian's range (either value makes
+// "median buffers": LG_MODE_MEDIAN and the id plane), never cleared.  Until then a backward launches exactly what it launched before
+// the modes existed; from then on the first blend walk asks the buffer's mode word and k_median_backward is queued (it retires on one
+// load on a default buffer).  The buffer's word decides every result, not this flag.
 std::atomic<bool> g_median_seen{false};
-int refuse_median_depth(const char* entry) {
-    if (!median_depth_requested()) return 0;
-    return fail(LIDARGS_ERR_INVALID_ARGUMENT, "%s: LIDARGS_DEPTH=median is not supported by this entry point (only lidargs_forward / lidargs_backward are); unset it for this call", entry);
+int refuse_depth_mode(const char* entry) {
+    if (!picked_depth_requested()) return 0;
+    return fail(LIDARGS_ERR_INVALID_ARGUMENT, "%s: a non-default LIDARGS_DEPTH (median, strongest) is not supported by this entry point (only lidargs_forward / lidargs_backward are); unset it for this call", entry);
 }
 int api_read_words_zero_behind(const uint32_t* dev, int n, uint32_t* out, void* zero, size_t zero_bytes, hipStream_t s) {
     hipError_t e = (hipError_t)read_words_begin(dev, n, s);
@@ -494,9 +495,10 @@ struct FrameMode {
     // lidargs_forward under LIDARGS_DETERMINISTIC=1: the geometry buffer is asked for with its 64-bit accumulator lines behind everything
     // else and its mode word set (lidargs_common.h LG_TOTALS_MODE_WORD); every backward on these buffers then adds up in fixed point.
     bool deterministic = false;
-    // lidargs_forward under LIDARGS_DEPTH=median: the image buffer is asked for with the median_id plane behind everything else, the mode
-    // word gets LG_MODE_MEDIAN, and k_render_median overwrites out_depth behind the blend (never together with `deterministic`)
-    bool median = false;
+    // lidargs_forward under LIDARGS_DEPTH=median or strongest -- the depth is one Gaussian's range: the image buffer is asked for with the
+    // median_id plane behind everything else, the mode word gets LG_MODE_MEDIAN, and k_render_median / k_render_strongest overwrites
+    // out_depth behind the blend (never together with `deterministic`).  `strongest` (only with `median`) picks the rule of that walk.
+    bool median = false, strongest = false;
 };
 
 // The preprocess' parameters of a whole frame on `grid`: no column wedge, full span records, pruning on, every row valid.  The forward,
@@ -620,13 +622,13 @@ int forward_impl(lidargs_alloc_fn geometry_alloc, void* geometry_user, lidargs_a
     LG_STAGE_CHECK("render combine");
     lg::prof_mark("render_combine", stream);
     }
-    if (mode.median) {   // behind either form of the blend: out_depth becomes the median range, the image buffer's last plane names its Gaussian
+    if (mode.median) {   // behind either form of the blend: out_depth becomes the picked Gaussian's range, the image buffer's last plane names it
         lg::MedianFwdArgs ma;
         ma.grid = L.grid; ma.ranges = img.ranges; ma.point_list = bin.val_a; ma.rec = geom.rec; ma.rowspan = geom.rowspan;
         ma.coltab = img.coltab; ma.rowtab = img.rowtab; ma.out_depth = out_depth; ma.median_id = img.median_id;
-        lg::launch_render_median(ma, stream);
-        LG_STAGE_CHECK("render median");
-        lg::prof_mark("render_median", stream);
+        lg::launch_render_median(ma, mode.strongest, stream);
+        LG_STAGE_CHECK(mode.strongest ? "render strongest" : "render median");
+        lg::prof_mark(mode.strongest ? "render_strongest" : "render_median", stream);
     }
 
     // the selection a backward on these buffers will make (backward_impl builds the same view): counted now, while the buffers are certainly alive
@@ -746,9 +748,10 @@ int lidargs_forward(lidargs_alloc_fn geometry_alloc, void* geometry_user, lidarg
     const float inf = std::numeric_limits<float>::infinity();
     FrameMode mode;
     mode.deterministic = lg::deterministic_requested();
-    mode.median = lg::median_depth_requested();
-    if (mode.deterministic && mode.median)   // (the median mode's depth gradient is added with a float atomic: not what the other switch promises)
-        return fail(LIDARGS_ERR_INVALID_ARGUMENT, "%s: LIDARGS_DEPTH=median is not supported together with LIDARGS_DETERMINISTIC=1; unset one of them for this call", "lidargs_forward");
+    mode.strongest = lg::strongest_depth_requested();
+    mode.median = mode.strongest || lg::median_depth_requested();
+    if (mode.deterministic && mode.median)   // (a picked Gaussian's depth gradient is added with a float atomic: not what the other switch promises)
+        return fail(LIDARGS_ERR_INVALID_ARGUMENT, "%s: a non-default LIDARGS_DEPTH (median, strongest) is not supported together with LIDARGS_DETERMINISTIC=1; unset one of them for this call", "lidargs_forward");
     return forward_impl(geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user, P, background, width,
                         height, means3D, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix,
                         beam_inclinations, (float)lidar_near, (float)lidar_far, -inf, inf, nullptr, 0, out_color, out_depth,
@@ -764,7 +767,7 @@ int lidargs_forward_enqueue(lidargs_alloc_fn geometry_alloc, void* geometry_user
                             int* radii, int* radii_xy, int debug, int instance_capacity, int tile_rows, unsigned* status_host, void* stream) {
     (void)D; (void)M; (void)shs; (void)projmatrix; (void)cam_pos; (void)prefiltered;
     if (const int rc = lg::refuse_deterministic("lidargs_forward_enqueue")) return rc;
-    if (const int rc = lg::refuse_median_depth("lidargs_forward_enqueue")) return rc;
+    if (const int rc = lg::refuse_depth_mode("lidargs_forward_enqueue")) return rc;
     if (instance_capacity <= 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward_enqueue: instance_capacity must be positive%s");
     const float inf = std::numeric_limits<float>::infinity();
     FrameMode mode;
@@ -1035,7 +1038,7 @@ int lidargs_forward_shell(lidargs_alloc_fn geometry_alloc, void* geometry_user, 
                           const float* T_in, int transmittance_pass, float* out_color, float* out_depth, float* out_occ,
                           float* T_out, int* radii, int* radii_xy, int debug, void* stream) {
     if (const int rc = lg::refuse_deterministic("lidargs_forward_shell")) return rc;
-    if (const int rc = lg::refuse_median_depth("lidargs_forward_shell")) return rc;
+    if (const int rc = lg::refuse_depth_mode("lidargs_forward_shell")) return rc;
     FrameMode mode;
     mode.is_shell = true;
     return forward_impl(geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user, P, background, width,
@@ -1053,7 +1056,7 @@ int lidargs_forward_shell_enqueue(lidargs_alloc_fn geometry_alloc, void* geometr
                                   float* T_out, int* radii, int* radii_xy, int debug, const unsigned* n_valid, int instance_capacity,
                                   int tile_rows, unsigned* status_host, void* stream) {
     if (const int rc = lg::refuse_deterministic("lidargs_forward_shell_enqueue")) return rc;
-    if (const int rc = lg::refuse_median_depth("lidargs_forward_shell_enqueue")) return rc;
+    if (const int rc = lg::refuse_depth_mode("lidargs_forward_shell_enqueue")) return rc;
     if (instance_capacity <= 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward_shell_enqueue: instance_capacity must be positive%s");
     FrameMode mode;
     mode.is_shell = true; mode.n_valid = n_valid;
@@ -1072,7 +1075,7 @@ int lidargs_forward_wedge(lidargs_alloc_fn geometry_alloc, void* geometry_user, 
                           const float* beam_inclinations, int lidar_far, int lidar_near, int col_lo, int col_hi, float* out_color,
                           float* out_depth, float* out_occ, int* radii, int* radii_xy, int debug, void* stream) {
     if (const int rc = lg::refuse_deterministic("lidargs_forward_wedge")) return rc;
-    if (const int rc = lg::refuse_median_depth("lidargs_forward_wedge")) return rc;
+    if (const int rc = lg::refuse_depth_mode("lidargs_forward_wedge")) return rc;
     if (col_lo < 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward_wedge: col_lo < 0%s");
     // lidargs_wedge_select_count bounds a Gaussian's reach from its scales and rotation; a precomputed covariance has no such bound
     // there, and a wedge rendered from an under-selected set would silently miss its boundary Gaussians
@@ -1094,7 +1097,7 @@ int lidargs_forward_wedge_enqueue(lidargs_alloc_fn geometry_alloc, void* geometr
                                   float* out_depth, float* out_occ, int* radii, int* radii_xy, int debug, const unsigned* n_valid,
                                   int instance_capacity, int tile_rows, unsigned* status_host, void* stream) {
     if (const int rc = lg::refuse_deterministic("lidargs_forward_wedge_enqueue")) return rc;
-    if (const int rc = lg::refuse_median_depth("lidargs_forward_wedge_enqueue")) return rc;
+    if (const int rc = lg::refuse_depth_mode("lidargs_forward_wedge_enqueue")) return rc;
     if (col_lo < 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward_wedge: col_lo < 0%s");
     if (cov3D_precomp) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward_wedge: cov3D_precomp is not supported on the column-wedge path (give scales + rotations)%s");
     if (instance_capacity <= 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward_wedge_enqueue: instance_capacity must be positive%s");

@@ -107,9 +107,10 @@ __device__ __forceinline__ uint2 span_unpack(uint32_t w) {            // -> (xsp
 // Word 4 now carries the forward's accumulation mode to every backward on the buffer: 0 (the forward's memset) = float atomics,
 // 1 = deterministic (LIDARGS_DETERMINISTIC=1 at the forward: the geometry buffer then ends in GeomView::acc64).  The backward's
 // KERNELS read it; the host never does, so a cloned or offloaded buffer carries its mode along and no backward waits for a read.
-// Bit 1 (LIDARGS_DEPTH=median at the forward): out_depth is the median range and the image buffer ends in ImgView::median_id; the
-// backward's blend then treats dL/ddepth as zero and k_median_backward sends it to the one Gaussian each pixel names.  The two modes
-// exclude each other (lidargs_forward refuses both at once: the median add is a float atomic), so the word is 0, 1 or 2.
+// Bit 1 (LIDARGS_DEPTH=median or strongest at the forward): out_depth is one Gaussian's range -- the median's or the strongest
+// return's; a backward need not know which -- and the image buffer ends in ImgView::median_id; the backward's blend then treats
+// dL/ddepth as zero and k_median_backward sends it to the one Gaussian each pixel names.  The two bits exclude each other
+// (lidargs_forward refuses both at once: that add is a float atomic), so the word is 0, 1 or 2.
 #define LG_TOTALS_MODE_WORD 4
 constexpr uint32_t LG_MODE_DETERMINISTIC = 1u, LG_MODE_MEDIAN = 2u;
 // behind the status words: LG_INST_SLOTS slots of (~smallest, largest) range key of the frame's visible Gaussians (atomicMax of the
@@ -267,11 +268,11 @@ struct ImgView {
     uint2* ranges;        // [tiles]
     float2* coltab;       // [W]  (cos beta, sin beta)
     float2* rowtab;       // [H]  (cos alpha, sin alpha) of pixel row y
-    uint32_t* median_id;  // [N] median mode only (behind everything else, as GeomView::acc64 is: the default buffer is byte for byte what it
-                          //     was): the Gaussian whose range the pixel returned, 0xFFFFFFFF = none (render.hip k_render_median)
+    uint32_t* median_id;  // [N] median and strongest modes only (behind everything else, as GeomView::acc64 is: the default buffer is byte for byte
+                          //     what it was): the Gaussian whose range the pixel returned, 0xFFFFFFFF = none (render.hip depth_pick_walk)
 };
 
-// median: carve ImgView::median_id as well.  The forward asks for it only under LIDARGS_DEPTH=median; a backward always computes the
+// median: carve ImgView::median_id as well.  The forward asks for it only under LIDARGS_DEPTH=median / strongest; a backward always computes the
 // address (it does not know the mode) and hands it to a kernel that reads it only where the buffer's mode word says it is there.
 inline size_t img_carve(char* base, int W, int H, int tiles, ImgView* v, bool median = false) {
     Carver c(base);
@@ -342,7 +343,7 @@ void lane_stats_read(unsigned long long* out, int reset);              // render
 int api_fail(int code, const char* msg);
 int api_check_launch(hipStream_t s, int debug, const char* what);
 int refuse_deterministic(const char* entry);    // 0, or LIDARGS_ERR_INVALID_ARGUMENT (message set) when the switch is on: entry points the mode does not cover
-int refuse_median_depth(const char* entry);     // the same for LIDARGS_DEPTH=median
+int refuse_depth_mode(const char* entry);       // the same for a non-default depth mode (LIDARGS_DEPTH=median, strongest)
 // Device -> host read of `n` (<= 1024) words with `zero_bytes` at `zero` cleared BEHIND the copy on the same stream: the host waits
 // for the copy only.  Returns a hipError_t.
 int api_read_words_zero_behind(const uint32_t* dev, int n, uint32_t* out, void* zero, size_t zero_bytes, hipStream_t s);
@@ -566,15 +567,17 @@ void launch_render_backward(const RenderBwdArgs& a, hipStream_t s);
 
 // LIDARGS_DEPTH=median (DESIGN.md "Median-range depth").  Forward: behind the blend, one wave per 16 x 4 patch walks the tile's list from
 // T = 1 until every pixel's transmittance has fallen to one half, overwrites out_depth with the range of the last entry taken above one
-// half and names that Gaussian in median_id.  Backward: dL_ddepth[pixel] is added (weight 1) to the range slot of that Gaussian's packed
-// line; a fixed small grid that retires on one load unless the buffer's mode word has LG_MODE_MEDIAN.
+// half and names that Gaussian in median_id.  LIDARGS_DEPTH=strongest (`strongest` below): the same walk with the other rule -- the
+// entry with the largest blend weight alpha x T, until no pixel's T exceeds its best weight.  Backward, for both: dL_ddepth[pixel] is
+// added (weight 1) to the range slot of that Gaussian's packed line; a fixed small grid that retires on one load unless the buffer's
+// mode word has LG_MODE_MEDIAN.
 struct MedianFwdArgs {
     TileGrid grid;
     const uint2* ranges; const uint32_t* point_list; const float4* rec; const uint32_t* rowspan;
     const float2* coltab; const float2* rowtab;
     float* out_depth; uint32_t* median_id;
 };
-void launch_render_median(const MedianFwdArgs& a, hipStream_t s);
+void launch_render_median(const MedianFwdArgs& a, bool strongest, hipStream_t s);   // k_render_median, or k_render_strongest
 struct MedianBwdArgs { const uint32_t* mode; const uint32_t* median_id; const float* dL_ddepth; float* gacc; size_t N; uint32_t P; };
 void launch_median_backward(const MedianBwdArgs& a, hipStream_t s);
 void launch_count_backward_entries(const RenderBwdArgs& a, unsigned long long* out, hipStream_t s);   // diagnostics: adds the list entries k_render_backward gathers to *out

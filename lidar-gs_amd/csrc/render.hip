@@ -314,7 +314,7 @@ __device__ __forceinline__ void walk_T_only_v2(const int cnt, const float4* s_re
 // compose) is T while the pixel is live and 0 once its walk has tripped here.
 // alpha of one parked entry (park_record / park_compact: r0 = s.xyz | B, r1, r2) for the pixel looking along (qxy, qz), `op` being the
 // entry's opacity on the pixel's row (0 outside its row span: the rect's row test); 0 where the pixel does not take the entry.  The
-// one text of the expression for the full walk below and the median walk (k_render_median), which must take exactly the same entries.
+// one text of the expression for the full walk below and the median / strongest walk (depth_pick_walk), which must take exactly the same entries.
 __device__ __forceinline__ float entry_alpha(const float4& r0, const float4& r1, const float4& r2, const float op, const v2f qxy, const float qz) {
     const v2f exy = v2f{r0.x, r0.y} - qxy;
     const float ez = r0.z - qz;
@@ -958,15 +958,21 @@ void launch_render_combine(const RenderFwdArgs& a, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// LIDARGS_DEPTH=median: the median range of every pixel, in a launch of its own behind the blend (whichever form that took).
-// One wave64 per 16 x 4 patch walks its tile's list in list order from T = 1, 64 records at a time through LDS.  Per pixel, for every
-// entry it takes (entry_alpha: the full walk's membership, skips and alpha):
-//     if T > 0.5:  median = the entry's range, median_id = its Gaussian;      then  T *= 1 - alpha
-// so the pixel ends with the entry at which T falls through one half -- or its last taker, if T never gets there; no taker: range 0,
-// id 0xFFFFFFFF.  The blend's T < 1e-4 stop cannot fire above one half (alpha <= 0.99 leaves T >= 0.005), so above one half this walk
-// and the blend's see the same T.  A plain serial walk on purpose: it leaves when every pixel of the patch is at T <= 0.5, which on
+// LIDARGS_DEPTH=median / strongest: the range of ONE Gaussian per pixel, in a launch of its own behind the blend (whichever form that
+// took).  One wave64 per 16 x 4 patch walks its tile's list in list order from T = 1, 64 records at a time through LDS.  Per pixel, for
+// every entry it takes (entry_alpha: the full walk's membership, skips and alpha) --
+//   median:     if T > 0.5:  pick = the entry;      then  T *= 1 - alpha
+//     so the pixel ends with the entry at which T falls through one half -- or its last taker, if T never gets there.  The blend's
+//     T < 1e-4 stop cannot fire above one half (alpha <= 0.99 leaves T >= 0.005), so above one half this walk and the blend's see the
+//     same T.  The pixel leaves at T <= 0.5.
+//   strongest:  test = T (1 - alpha);  if test < 1e-4 the pixel ends and this entry does not count (the blend's stop, its expression);
+//     otherwise  w = alpha T (the blend's weight);  if w > best (strict: among equal weights the nearer entry stays):  best = w,
+//     pick = the entry;      then  T = test
+//     so the pixel ends with its strongest return.  It leaves at T <= best: a later weight is alpha' T' <= 0.99 T < best.
+// No taker: range 0, id 0xFFFFFFFF.  A plain serial walk on purpose: it leaves when every pixel of the patch has left, which on
 // saturating frames is a few entries in; the blend kernels are not touched.
-__global__ void __launch_bounds__(64) k_render_median(const MedianFwdArgs a) {
+template <bool STRONGEST>
+__device__ __forceinline__ void depth_pick_walk(const MedianFwdArgs& a) {
     __shared__ float4 s_rec[4 * LG_CHUNK];
     __shared__ float4 s_oprow[LG_CHUNK];
     __shared__ uint32_t s_gid[LG_CHUNK];
@@ -982,8 +988,9 @@ __global__ void __launch_bounds__(64) k_render_median(const MedianFwdArgs a) {
     const v2f qxy = v2f{px.q.x, px.q.y};
 
     float T = 1.0f, range = 0.f;
+    float best = 0.f;                                                  // (strongest only) the largest weight so far
     uint32_t id = 0xFFFFFFFFu;
-    bool open = px.inside;                                             // T > 0.5: the next entry taken is still a candidate
+    bool open = px.inside;                                             // median: T > 0.5; strongest: T > best and not stopped -- an entry behind can still be the pick
     const uint32_t nchunks = (n + LG_CHUNK - 1) / LG_CHUNK;
     for (uint32_t c = 0; c < nchunks && __ballot(open) != 0ull; c++) { // (wave-uniform: the workgroup is one wave)
         const uint32_t k = c * LG_CHUNK + (uint32_t)lane;
@@ -996,19 +1003,46 @@ __global__ void __launch_bounds__(64) k_render_median(const MedianFwdArgs a) {
         s_gid[lane] = g;
         __syncthreads();
         const int cnt = (int)min((uint32_t)LG_CHUNK, n - c * LG_CHUNK);
-        for (int j = 0; j < cnt && __ballot(open) != 0ull; j++) {
-            const float alpha = entry_alpha(s_rec[j], s_rec[LG_CHUNK + j], s_rec[2 * LG_CHUNK + j], oprow[4 * j], qxy, px.q.z);
-            const bool take = open && alpha > 0.f;
-            range = take ? s_rec[3 * LG_CHUNK + j].x : range;
-            id = take ? s_gid[j] : id;
-            T = take ? T * (1.f - alpha) : T;
-            open = open && T > 0.5f;
+        // Four entries per exit test: their LDS reads and alphas do not depend on the pixel's state and are in flight together, the four
+        // updates behind them are a few selects each.  A pixel that has left ignores every later entry (`take` asks `open`), so WHEN the
+        // wave leaves changes no result; the slots in [cnt, 64) hold this chunk's zero records (alpha = 0), so a last group may reach over cnt.
+        for (int j = 0; j < cnt && __ballot(open) != 0ull; j += 4) {
+            float alpha[4], depth[4]; uint32_t gid[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                alpha[u] = entry_alpha(s_rec[j + u], s_rec[LG_CHUNK + j + u], s_rec[2 * LG_CHUNK + j + u], oprow[4 * (j + u)], qxy, px.q.z);
+                depth[u] = s_rec[3 * LG_CHUNK + j + u].x;
+                gid[u] = s_gid[j + u];
+            }
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const bool take = open && alpha[u] > 0.f;
+                if (STRONGEST) {
+                    const float test = T * (1.f - alpha[u]);
+                    const bool counts = take && test >= 0.0001f;
+                    const bool wins = counts && alpha[u] * T > best;
+                    best = wins ? alpha[u] * T : best;
+                    range = wins ? depth[u] : range;
+                    id = wins ? gid[u] : id;
+                    T = counts ? test : T;
+                    open = open && (counts || !take) && T > best;
+                } else {
+                    range = take ? depth[u] : range;
+                    id = take ? gid[u] : id;
+                    T = take ? T * (1.f - alpha[u]) : T;
+                    open = open && T > 0.5f;
+                }
+            }
         }
     }
     if (px.inside) { a.out_depth[px.pix] = range; a.median_id[px.pix] = id; }
 }
-void launch_render_median(const MedianFwdArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(k_render_median, dim3((unsigned)a.grid.window_patches()), dim3(64), 0, s, a);
+__global__ void __launch_bounds__(64) k_render_median(const MedianFwdArgs a) { depth_pick_walk<false>(a); }
+__global__ void __launch_bounds__(64) k_render_strongest(const MedianFwdArgs a) { depth_pick_walk<true>(a); }
+void launch_render_median(const MedianFwdArgs& a, const bool strongest, hipStream_t s) {
+    const dim3 grid((unsigned)a.grid.window_patches());
+    if (strongest) hipLaunchKernelGGL(k_render_strongest, grid, dim3(64), 0, s, a);
+    else hipLaunchKernelGGL(k_render_median, grid, dim3(64), 0, s, a);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1139,7 +1173,7 @@ __device__ __forceinline__ void backward_walk(const RenderBwdArgs& a, const unsi
     const float T_final = px.inside ? (a.T_final_global ? a.T_final_global[px.pix] : a.final_T[px.pix]) : 0.f;
     float g0 = 0.f, g1 = 0.f, gd = 0.f, go = 0.f;
     if (px.inside) { g0 = a.dL_dpix[px.pix]; g1 = a.dL_dpix[N + px.pix]; gd = a.dL_ddepth[px.pix]; go = a.dL_docc[px.pix]; }
-    // median buffers (LG_MODE_MEDIAN): out_depth is not the blend's sum, so neither its term in dL/dalpha nor w dL/ddepth exists here --
+    // median buffers (LG_MODE_MEDIAN; the pick was the median's or the strongest return's): out_depth is not the blend's sum, so neither its term in dL/dalpha nor w dL/ddepth exists here --
     // k_median_backward hands each pixel's dL/ddepth to the one Gaussian whose range it returned.  (Wave-uniform; false by constant in the plain form.)
     if (median) gd = 0.f;
     const float bgdot = a.bg ? (a.bg[0] * g0 + a.bg[1] * g1) : 0.f;
@@ -1408,7 +1442,7 @@ void launch_render_backward(const RenderBwdArgs& a, hipStream_t s) {
     else hipLaunchKernelGGL(k_render_backward_det<false>, dim3(grid), dim3(64), 0, s, a, blocks);
 }
 
-// The median mode's depth gradient: out_depth[pixel] = range of Gaussian median_id[pixel], so dL_ddepth[pixel] goes, with weight 1, into
+// The depth gradient of median buffers (a median or a strongest forward's): out_depth[pixel] = range of Gaussian median_id[pixel], so dL_ddepth[pixel] goes, with weight 1, into
 // the range slot (9) of that Gaussian's packed line -- a taker of the forward, hence marked as touched: its line was cleared by
 // k_zero_touched and is read by k_gaussian_backward, which carries the sum into the mean.  The host does not know the buffers' mode:
 // launched in every backward of a process that has made median buffers, a fixed small grid that retires on one load on a default buffer

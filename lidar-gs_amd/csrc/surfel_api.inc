@@ -66,7 +66,7 @@ int lidargs_surfel_forward(lidargs_alloc_fn geometry_alloc, void* geometry_user,
     (void)D; (void)M; (void)shs; (void)projmatrix; (void)cam_pos; (void)prefiltered; (void)pixels;   // `pixels` is never written by the reference either (R2/cr/forward.cu:522)
     hipStream_t stream = (hipStream_t)stream_;
     if (const int rc = lg::refuse_deterministic("lidargs_surfel_forward")) return rc;   // (the surfel backward still adds with float atomics)
-    if (const int rc = lg::refuse_median_depth("lidargs_surfel_forward")) return rc;    // (the surfel variant returns its own median plane, others[5])
+    if (const int rc = lg::refuse_depth_mode("lidargs_surfel_forward")) return rc;    // (the surfel variant returns its own median plane, others[5])
     if (P < 0 || width <= 0 || height < 2 || height > 65535) return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "surfel forward: bad sizes");
     if (colors_precomp == nullptr) return lg::api_fail(LIDARGS_ERR_NO_COLORS, "For non-RGB, provide precomputed Gaussian colors!");
     // transMat_precomp, as the reference treats it: its preprocess builds T from scales and rotations unconditionally (rect, normal,

@@ -80,6 +80,12 @@ inline bool deterministic_requested() { return env_on("LIDARGS_DETERMINISTIC"); 
 // lidargs_backward sends a pixel's depth gradient to that one Gaussian.  Read at EVERY call, by forward entry points only (the mode
 // travels in the buffers, like the deterministic one).  Only the literal value `median` turns it on: unset, empty, anything else = expected.
 inline bool median_depth_requested() { const char* e = getenv("LIDARGS_DEPTH"); return e && strcmp(e, "median") == 0; }
+// LIDARGS_DEPTH=strongest: the other supported value of the same switch -- the range of the pixel's strongest return, the entry with the
+// largest blend weight alpha x T (render.hip k_render_strongest).  Its buffers are median buffers to every backward: the depth is one
+// Gaussian's, named in the same id plane.  Only the literal value `strongest`; read like `median`.
+inline bool strongest_depth_requested() { const char* e = getenv("LIDARGS_DEPTH"); return e && strcmp(e, "strongest") == 0; }
+// either of them: the depth of the next forward is one Gaussian's range, not the expected range (what the other entry points refuse)
+inline bool picked_depth_requested() { return median_depth_requested() || strongest_depth_requested(); }
 // LIDARGS_NG_FORWARD_T16=0, LIDARGS_NG_BACKWARD_T16=0 (first character '0'): the decode's forward / backward on the 32x32x2 kernels, which
 // k = 8, 10 take in any case, instead of the 16x16x4 ones (A/B, test variants)
 inline bool ng_forward_t16_allowed() { return !env_starts_with("LIDARGS_NG_FORWARD_T16", '0'); }

@@ -26,9 +26,11 @@ __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gau
 
 def depth_mode():
     """Which depth the next forward of this process returns: "median" (the range of the Gaussian at which the transmittance falls through
-    one half; LIDARGS_DEPTH=median, read by the library at every lidargs_forward) or "expected" (sum of range x alpha x T: unset, empty or
+    one half; LIDARGS_DEPTH=median, read by the library at every lidargs_forward), "strongest" (the range of the Gaussian with the largest
+    blend weight alpha x T, a LiDAR's strongest return; LIDARGS_DEPTH=strongest) or "expected" (sum of range x alpha x T: unset, empty or
     any other value).  The backward follows the forward that made its buffers, not the environment at its own time."""
-    return "median" if os.environ.get("LIDARGS_DEPTH") == "median" else "expected"
+    value = os.environ.get("LIDARGS_DEPTH")
+    return value if value in ("median", "strongest") else "expected"
 
 
 class GaussianRasterizationSettings(NamedTuple):
