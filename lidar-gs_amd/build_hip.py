@@ -26,6 +26,11 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 OUT = os.path.join(HERE, "diff_lidargs_rasterization", "liblidargs_hip.so")
+# The main library's second header directory and symbol prefix: the pose-gradient entry points (lgpose_*, include_pose/lidargs_pose.h)
+# need lidargs_backward's host sequence and process-wide state, so they are part of liblidargs_hip.so and not a library of their own;
+# include/ and the library's lidargs_* exports stay the drop-in boundary for the reference's interfaces.
+POSE_INCLUDE = os.path.join(ROOT, "include_pose")
+POSE_PREFIX = "lgpose_"
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-fno-gpu-rdc", "-Wall",
           "-Wno-unused-function", "-Wno-unused-value"]
 SOURCES = {
@@ -79,9 +84,10 @@ def _listed(d, keep=lambda f: True):
 
 def deps(target):
     """What a library is rebuilt for: its own sources, every shared file of csrc/ that is not a .hip (headers and .inc, whichever
-    target includes them: more than needed, never less), every header of its include directory and this file."""
+    target includes them: more than needed, never less), every header of its include directory and this file; the main library also
+    for the header of its pose entry points (POSE_INCLUDE)."""
     return ([os.path.join(CSRC, f) for f in target.sources] + _listed(CSRC, lambda f: not f.endswith(".hip"))
-            + _listed(target.include) + [os.path.abspath(__file__)])
+            + _listed(target.include) + (_listed(POSE_INCLUDE) if target.name == "hip" else []) + [os.path.abspath(__file__)])
 
 
 def stale(target):

@@ -13,6 +13,7 @@
 //   - errors are returned as negative codes instead of printf-and-continue.
 #include "lidargs_common.h"
 #include "../../include/lidargs_rasterizer.h"
+#include "../../include_pose/lidargs_pose.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -654,7 +655,7 @@ int backward_impl(int P, int R, const float* background, int width, int height, 
                   char* binning_buffer, char* image_buffer, const BackMode& mode, const float* dL_dpix, const float* dL_dout_depth, const float* dL_dout_occ, float* dL_dmean2D,
                   float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_ddepths, float* dL_dmean3D,
                   float* dL_dsphere_means3D, float* dL_dbasis_u1, float* dL_dbasis_u2, float* dL_dcov3D, float* dL_dscale,
-                  float* dL_drot, int debug, hipStream_t stream) {
+                  float* dL_drot, int debug, hipStream_t stream, float* dL_dviewmatrix = nullptr, float* view_partials = nullptr) {
     (void)colors_precomp; (void)beams;
     const int col_lo = mode.col_lo, col_hi = mode.col_hi;
     if (P < 0 || R < 0 || width <= 0 || height <= 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "backward: bad sizes%s");
@@ -724,7 +725,10 @@ int backward_impl(int P, int R, const float* background, int width, int height, 
     gb.dL_dsphere = dL_dsphere_means3D; gb.dL_dmean3D = dL_dmean3D; gb.dL_dcov3D = dL_dcov3D; gb.dL_dscale = dL_dscale;
     gb.dL_drot = dL_drot;
     gb.det_mode = det_mode; gb.acc64 = geom.acc64;
-    lg::launch_gaussian_backward(gb, stream);
+    if (dL_dviewmatrix) {   // lgpose_backward_view: the chain's pose form and the fold of its partial rows (two launches for one)
+        gb.view_partials = view_partials;
+        lg::launch_gaussian_backward_view(gb, dL_dviewmatrix, stream);
+    } else lg::launch_gaussian_backward(gb, stream);
     LG_STAGE_CHECK("gaussian backward");
     lg::prof_mark("gaussian_bwd", stream);
     return 0;
@@ -792,6 +796,33 @@ int lidargs_backward(int P, int D, int M, int R, const float* background, int wi
                          viewmatrix, beam_inclinations, radii, geom_buffer, binning_buffer, image_buffer, BackMode(), dL_dpix,
                          dL_dout_depth, dL_dout_occ, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_ddepths, dL_dmean3D,
                          dL_dsphere_means3D, dL_dbasis_u1, dL_dbasis_u2, dL_dcov3D, dL_dscale, dL_drot, debug, (hipStream_t)stream);
+}
+
+size_t lgpose_view_partial_floats(int P) { return lg::view_partial_floats(P); }
+
+int lgpose_backward_view(int P, int D, int M, int R, const float* background, int width, int height, const float* means3D,
+                          const float* shs, const float* colors_precomp, const float* scales, float scale_modifier,
+                          const float* rotations, const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                          const float* campos, const float* beam_inclinations, float tan_fovx, float tan_fovy, const int* radii,
+                          char* geom_buffer, char* binning_buffer, char* image_buffer, const float* dL_dpix,
+                          const float* dL_dout_depth, const float* dL_dout_occ, float* dL_dmean2D, float* dL_dconic,
+                          float* dL_dopacity, float* dL_dcolor, float* dL_ddepths, float* dL_dmean3D, float* dL_dsphere_means3D,
+                          float* dL_dbasis_u1, float* dL_dbasis_u2, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
+                          int debug, void* stream, float* dL_dviewmatrix, float* view_partials, size_t view_partial_floats) {
+    (void)D; (void)M; (void)shs; (void)projmatrix; (void)campos; (void)tan_fovx; (void)tan_fovy; (void)dL_dsh;
+    if (P < 0 || R < 0 || width <= 0 || height <= 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "backward_view: bad sizes%s");
+    if (!dL_dviewmatrix) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "backward_view: dL_dviewmatrix is NULL%s");
+    if (P == 0) {   // lidargs_backward's early return, and the sixteen zeros
+        LG_HIP(hipMemsetAsync(dL_dviewmatrix, 0, 16 * sizeof(float), (hipStream_t)stream));
+        return 0;
+    }
+    if (!view_partials || ((uintptr_t)view_partials & 15u) || view_partial_floats < lg::view_partial_floats(P))
+        return fail(LIDARGS_ERR_INVALID_ARGUMENT, "backward_view: view_partials is NULL, not 16-byte aligned or shorter than lgpose_view_partial_floats(P)%s");
+    return backward_impl(P, R, background, width, height, means3D, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
+                         viewmatrix, beam_inclinations, radii, geom_buffer, binning_buffer, image_buffer, BackMode(), dL_dpix,
+                         dL_dout_depth, dL_dout_occ, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_ddepths, dL_dmean3D,
+                         dL_dsphere_means3D, dL_dbasis_u1, dL_dbasis_u2, dL_dcov3D, dL_dscale, dL_drot, debug, (hipStream_t)stream,
+                         dL_dviewmatrix, view_partials);
 }
 
 int lidargs_visible_filter(lidargs_alloc_fn geometry_alloc, void* geometry_user, lidargs_alloc_fn binning_alloc, void* binning_user,
@@ -1027,6 +1058,42 @@ int lidargs_debug_gaussian_backward(int P, int line_f4, int stage, const unsigne
     gb.dL_drot = dL_drot;
     lg::launch_gaussian_backward(gb, stream);
     LG_STAGE_CHECK("debug gaussian backward");
+    return 0;
+}
+
+int lgpose_debug_view_backward(int P, const float* gacc, const float* means3D, const float* scales, float scale_modifier, const float* rotations,
+                                const float* cov3D_precomp, const float* viewmatrix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity,
+                                float* dL_dcolor, float* dL_ddepths, float* dL_dmean3D, float* dL_dsphere_means3D, float* dL_dbasis_u1,
+                                float* dL_dbasis_u2, float* dL_dcov3D, float* dL_dscale, float* dL_drot, const unsigned char* tlist,
+                                const unsigned short* tcount, const unsigned* mode_word, const long long* acc64, float* dL_dviewmatrix,
+                                float* view_partials, size_t view_partial_floats, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const int debug = 0;
+    if (P < 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_view_backward: bad size%s");
+    if (!dL_dviewmatrix) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_view_backward: dL_dviewmatrix is NULL%s");
+    if (P == 0) {
+        LG_HIP(hipMemsetAsync(dL_dviewmatrix, 0, 16 * sizeof(float), stream));
+        return 0;
+    }
+    if (!view_partials || ((uintptr_t)view_partials & 15u) || view_partial_floats < lg::view_partial_floats(P))
+        return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_view_backward: view_partials is NULL, not 16-byte aligned or shorter than lgpose_view_partial_floats(P)%s");
+    if (!gacc || !tlist || !tcount || !means3D || !viewmatrix || !dL_dmean2D || !dL_dopacity || !dL_dcolor || !dL_dmean3D || !dL_dscale || !dL_drot ||
+        (cov3D_precomp && !dL_dcov3D) || ((mode_word == nullptr) != (acc64 == nullptr)))
+        return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_view_backward: NULL required pointer%s");
+    if (!cov3D_precomp && (!scales || !rotations)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_view_backward: need scales+rotations or cov3D_precomp%s");
+    lg::GaussBwdArgs gb;
+    gb.P = P; gb.scale_modifier = scale_modifier;
+    gb.view = viewmatrix;
+    gb.means3D = means3D; gb.scales = scales; gb.rotations = rotations; gb.cov3D_precomp = cov3D_precomp; gb.radii = nullptr;
+    gb.gacc = gacc; gb.tlist = tlist; gb.tcount = tcount;
+    gb.dL_dmean2D = dL_dmean2D; gb.dL_dconic = dL_dconic; gb.dL_dopacity = dL_dopacity; gb.dL_dcolor = dL_dcolor;
+    gb.dL_ddepths = dL_ddepths; gb.dL_dbasis_u1 = dL_dbasis_u1; gb.dL_dbasis_u2 = dL_dbasis_u2;
+    gb.dL_dsphere = dL_dsphere_means3D; gb.dL_dmean3D = dL_dmean3D; gb.dL_dcov3D = dL_dcov3D; gb.dL_dscale = dL_dscale;
+    gb.dL_drot = dL_drot;
+    gb.det_mode = mode_word; gb.acc64 = acc64;
+    gb.view_partials = view_partials;
+    lg::launch_gaussian_backward_view(gb, dL_dviewmatrix, stream);
+    LG_STAGE_CHECK("debug view backward");
     return 0;
 }
 

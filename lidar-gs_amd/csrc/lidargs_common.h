@@ -595,8 +595,13 @@ struct GaussBwdArgs {
     float* dL_dbasis_u1; float* dL_dbasis_u2;
     float* dL_dsphere; float* dL_dmean3D; float* dL_dcov3D; float* dL_dscale; float* dL_drot;
     const uint32_t* det_mode = nullptr; const long long* acc64 = nullptr;   // as in RenderBwdArgs: where *det_mode has LG_MODE_DETERMINISTIC a line is det_decode(gacc, acc64)
+    float* view_partials = nullptr;   // the pose form alone: one 64-byte row of dL/dviewmatrix sums per region of LG_REGION Gaussians (view_partial_floats)
 };
 void launch_gaussian_backward(const GaussBwdArgs& a, hipStream_t s);
+// The pose form (lgpose_backward_view): the same chain, every region's twelve sums of dL/dviewmatrix written to
+// a.view_partials, and a one-workgroup launch that folds the rows in double into dL_dviewmatrix[16].  No atomics, no host read.
+void launch_gaussian_backward_view(const GaussBwdArgs& a, float* dL_dviewmatrix, hipStream_t s);
+size_t view_partial_floats(int P);   // floats of view_partials for P Gaussians
 
 // ---- device-side helpers shared by the blend kernels (render.hip, surfel.hip) ----------------------------------------
 #ifdef __HIPCC__

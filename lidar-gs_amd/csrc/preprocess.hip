@@ -4,6 +4,7 @@
 //   k_preprocess        K1 (R3/cr/forward.cu:256-384) and, with FILTER, K2 (:388-497)
 //   k_mark_visible      K11 (R3/cr/rasterizer_impl.cu:54-66)
 //   k_gaussian_backward K9 + K10 fused (R3/cr/backward.cu:157-382, :453-532, :385-448)
+//   k_gaussian_backward_view / k_fold_view_partials   the same chain + the gradient with respect to the view matrix (no reference counterpart)
 //   k_zero_touched / k_touch_visible   the touched-Gaussian lists the backward starts from
 //
 // All of them are one-thread-per-Gaussian HBM streams: 44 B in, <= 100 B out per Gaussian for
@@ -442,8 +443,10 @@ void launch_debug_rects(int n, int surfel, const float* p_cr, const int* r_xy, i
 // the same zeros from torch::zeros, R3/rasterize_points.cu:163-175).  The backward's first launch (k_zero_touched below) zeroes all
 // rows and lists the touched Gaussians region by region; k_gaussian_backward runs the chain on the listed ones only and overwrites
 // their rows.  An untouched Gaussian costs its mark and 68 bytes of zeros: no inputs, no radius, no 64-byte line.
-// the chain of one touched Gaussian
-__device__ __forceinline__ void gb_row(const GaussBwdArgs& a, const int idx) {
+// the chain of one touched Gaussian.  POSE (the pose form, k_gaussian_backward_view below): the row's twelve products of dL/dviewmatrix are
+// added to the lane's running sums ps[16] as well (slot 4r + k = element [r][k] of the matrix; slots 3, 7, 11, 15 stay zero)
+template <bool POSE = false>
+__device__ __forceinline__ void gb_row(const GaussBwdArgs& a, const int idx, float* ps = nullptr) {
 #pragma clang fp contract(fast)                                        // (see below, behind the early return)
     const float* vm = a.view;
 
@@ -583,6 +586,20 @@ __device__ __forceinline__ void gb_row(const GaussBwdArgs& a, const int idx) {
     v.z = g_mean.z + (n2 * gs.z - d.z * dgs) * id3 + gdep * dir.z;
     const float3 gw = view_to_world(vm, v);                            // transformVec4x3Transpose (:525)
     put3(a.dL_dmean3D, idx, gw.x, gw.y, gw.z);
+    if constexpr (POSE) {
+        // The matrix enters K1 twice: d[k] = sum_r vm[4r+k] pw[r] + vm[12+k] and t_i[r] = sum_k vm[4r+k] u_i[k].  v is the gradient
+        // on d, gt_i the one on t_i (the values world_to_view_dir was handed above), so this row's share of dL/dvm[4r+k] is
+        // v[k] pw[r] + gt1[r] u1[k] + gt2[r] u2[k], and of dL/dvm[12+k] it is v[k].
+        const float pr[3] = {pw.x, pw.y, pw.z}, vk[3] = {v.x, v.y, v.z};
+        const float g1[3] = {gt1.x, gt1.y, gt1.z}, g2[3] = {gt2.x, gt2.y, gt2.z};
+        const float a1[3] = {u1.x, u1.y, u1.z}, a2[3] = {u2.x, u2.y, u2.z};
+#pragma unroll
+        for (int r = 0; r < 3; r++)
+#pragma unroll
+            for (int k = 0; k < 3; k++) ps[4 * r + k] += vk[k] * pr[r] + g1[r] * a1[k] + g2[r] * a2[k];
+#pragma unroll
+        for (int k = 0; k < 3; k++) ps[12 + k] += vk[k];
+    }
 
     if (!a.scales) {
         put3(a.dL_dscale, idx, 0.f, 0.f, 0.f);
@@ -624,6 +641,74 @@ __global__ void __launch_bounds__(256) k_gaussian_backward(const GaussBwdArgs a)
     for (int j = lane; j < cnt; j += 64) {
         gb_row(a, base + off);
         if (j + 64 < cnt) off = (int)a.tlist[base + j + 64];
+    }
+}
+
+// The pose form of the launch above (lgpose_backward_view): the same chain on the same lists, and the gradient with respect to the
+// view matrix on top.  A lane adds the twelve products of its rows (at most LG_REGION / 64 = 4 of them, in list order) to running sums;
+// the wave folds the sums over its 64 lanes in a fixed order -- two gfx950 lane swaps, then DPP row rotations and quad permutes -- and
+// writes them as the region's 64-byte partial row: view_partials[16 region + 4r + k], zeros in column 3.  Every region of the launch
+// writes its row (zeros where nothing was touched), so the buffer need not be cleared.  No atomics: given the same packed lines the rows
+// are the same bits whatever the order the waves run in.
+__global__ void __launch_bounds__(256) k_gaussian_backward_view(const GaussBwdArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int region = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int base = region * LG_REGION;
+    if (base >= a.P) return;
+    int off = (int)a.tlist[base + lane];
+    int cnt = (int)a.tcount[region];
+    asm volatile("" : "+v"(off), "+v"(cnt));
+    float ps[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) ps[k] = 0.f;
+    for (int j = lane; j < cnt; j += 64) {
+        gb_row<true>(a, base + off, ps);
+        if (j + 64 < cnt) off = (int)a.tlist[base + j + 64];
+    }
+    // (every lane of the wave is here again: the loop's trip count differs between lanes, the reduction below is wave-wide)
+    // halves of 32, then of 16: lane L is left with slots 4 (L >> 4) .. 4 (L >> 4) + 3 in ps[0..3], i.e. row L >> 4 of the matrix
+#pragma unroll
+    for (int k = 0; k < 8; k++) ps[k] = fold_halves32(ps[k], ps[k + 8]);
+#pragma unroll
+    for (int k = 0; k < 4; k++) ps[k] = fold_halves16(ps[k], ps[k + 4]);
+    // the sixteen lanes of a row hold partial sums of the same four slots: rotations by 8 and 4, then the quad's lanes 2 and 1 apart
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        float x = ps[k];
+        x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x128, 0xF, 0xF, true));   // row_ror:8
+        x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x124, 0xF, 0xF, true));   // row_ror:4
+        x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
+        x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
+        ps[k] = x;
+    }
+    // lanes 0, 16, 32, 48 store the four 16-byte quarters of the region's line with one instruction
+    if ((lane & 15) == 0)
+        reinterpret_cast<float4*>(a.view_partials)[4 * (size_t)region + (lane >> 4)] = make_float4(ps[0], ps[1], ps[2], ps[3]);
+}
+
+// The second launch of the pose form: the partial rows folded into dL_dviewmatrix[16] in double, in a fixed order.  One workgroup;
+// thread (g, e) = (tid / 16, tid % 16) adds element e of rows g, g + 64, g + 128, ... in ascending order, thread e < 16 then adds the 64
+// group sums in ascending g and rounds once.  All sixteen outputs are written; column 3 is a sum of +0s.
+constexpr int LG_VIEW_FOLD_GROUPS = 64;
+__global__ void __launch_bounds__(16 * LG_VIEW_FOLD_GROUPS) k_fold_view_partials(const float* __restrict__ partials, int rows, float* __restrict__ out) {
+    __shared__ double s_sum[LG_VIEW_FOLD_GROUPS][16];
+    const int e = threadIdx.x & 15, g = threadIdx.x >> 4;
+    double acc = 0.0;
+    int r = g;
+    for (; r + 7 * LG_VIEW_FOLD_GROUPS < rows; r += 8 * LG_VIEW_FOLD_GROUPS) {   // eight loads in flight, added in row order
+        float x[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++) x[i] = partials[16 * (size_t)(r + i * LG_VIEW_FOLD_GROUPS) + e];
+#pragma unroll
+        for (int i = 0; i < 8; i++) acc += (double)x[i];
+    }
+    for (; r < rows; r += LG_VIEW_FOLD_GROUPS) acc += (double)partials[16 * (size_t)r + e];
+    s_sum[g][e] = acc;
+    __syncthreads();
+    if (threadIdx.x < 16) {
+        double t = 0.0;
+        for (int k = 0; k < LG_VIEW_FOLD_GROUPS; k++) t += s_sum[k][e];
+        out[e] = (float)t;
     }
 }
 
@@ -713,5 +798,12 @@ void launch_gaussian_backward(const GaussBwdArgs& a, hipStream_t s) {
     const unsigned regions = (unsigned)((a.P + LG_REGION - 1) / LG_REGION);
     hipLaunchKernelGGL(k_gaussian_backward, dim3((regions + 3) / 4), dim3(256), 0, s, a);
 }
+// the pose form + the fold: a.view_partials holds 16 floats per region (view_partial_floats), dL_dviewmatrix 16 floats
+void launch_gaussian_backward_view(const GaussBwdArgs& a, float* dL_dviewmatrix, hipStream_t s) {
+    const unsigned regions = (unsigned)((a.P + LG_REGION - 1) / LG_REGION);
+    hipLaunchKernelGGL(k_gaussian_backward_view, dim3((regions + 3) / 4), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_fold_view_partials, dim3(1), dim3(16 * LG_VIEW_FOLD_GROUPS), 0, s, a.view_partials, (int)regions, dL_dviewmatrix);
+}
+size_t view_partial_floats(int P) { return P > 0 ? 16 * (((size_t)P + LG_REGION - 1) / LG_REGION) : 0; }
 
 }  // namespace lg

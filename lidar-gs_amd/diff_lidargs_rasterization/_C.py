@@ -21,6 +21,7 @@ import lidargs_abi
 NUM_CHANNELS = 2  # R3/cr/config.h:15
 # The one CDLL of the process, every lidargs_* function typed from the headers (restype and argtypes: lidargs_abi).
 _lib = lidargs_abi.library("hip")
+lidargs_abi.type_also(_lib, lidargs_abi.build_hip.POSE_INCLUDE, lidargs_abi.build_hip.POSE_PREFIX)     # lgpose_*: include_pose/lidargs_pose.h
 _ptr, _stream = lidargs_abi.ptr, lidargs_abi.stream
 _ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_size_t)
 
@@ -153,12 +154,14 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
                                  viewmatrix, projmatrix, beam_inclinations, tan_fovx, tan_fovy, dL_dout_color,
                                  dL_dout_depth, dL_dout_occ, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer,
-                                 debug, want_cov3D_grad=True):
+                                 debug, want_cov3D_grad=True, want_viewmatrix_grad=False):
     """RasterizeGaussiansBackwardCUDA (R3/rasterize_points.cu:126-219).
 
     Returns (dL_dmeans2D[P,4], dL_dcolors[P,2], dL_dopacity[P,1], dL_dmeans3D[P,3], dL_dcov3D[P,6],
     dL_dsh[P,M,3], dL_dscales[P,3], dL_drotations[P,4]).  want_cov3D_grad=False (only with scales + rotations, where the
-    reference's dL_dcov3D is an intermediate nobody receives): dL_dcov3D is not materialised and None is returned for it."""
+    reference's dL_dcov3D is an intermediate nobody receives): dL_dcov3D is not materialised and None is returned for it.
+    want_viewmatrix_grad=True (no reference counterpart): lgpose_backward_view is called instead of lidargs_backward and
+    dL_dviewmatrix[4,4] is returned as a ninth element; every other element is the same."""
     _require_device(means3D, "means3D")
     dev = means3D.device
     P = int(means3D.size(0))
@@ -178,6 +181,13 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
         dL_dcov3D = None
     dL_ddepths = dL_dconic = dL_dsphere = dL_du1 = dL_du2 = None
     dL_dsh = torch.zeros((P, M, 3), dtype=torch.float32, device=dev)
+    if want_viewmatrix_grad:
+        # the sixteen floats (all written by the library) in front of the partial rows: 64 bytes, so the rows stay whole lines
+        n_part = int(_lib.lgpose_view_partial_floats(P))
+        view_slab = torch.empty(16 + n_part, dtype=torch.float32, device=dev)
+        dL_dviewmatrix, view_partials = view_slab[:16].view(4, 4), view_slab[16:]
+        if P == 0:
+            dL_dviewmatrix.zero_()
     if P != 0:
         bg, m3, col = _f32(background, "background"), _f32(means3D, "means3D"), _f32(colors, "colors")
         cov, vm, beams = _f32(cov3D_precomp, "cov3D_precomp"), _f32(viewmatrix, "viewmatrix"), _f32(beam_inclinations, "beam_inclinations")
@@ -186,17 +196,23 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
         # the reference passes scales/rotations by raw data_ptr here (:185,:187); contiguity is the caller's business there,
         # we make it explicit instead of silently reading a strided tensor wrongly
         sc, rot = _f32(scales, "scales"), _f32(rotations, "rotations")
+        common = (
+            P, int(degree), M, int(R), _ptr(bg), W, H, _ptr(m3), None, _ptr(col), _ptr(sc if sc.is_cuda else None),
+            float(scale_modifier), _ptr(rot if rot.is_cuda else None), _ptr(cov if cov.is_cuda else None), _ptr(vm), None, None,
+            _ptr(beams), float(tan_fovx), float(tan_fovy), _ptr(rad),
+            _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(g0), _ptr(g1), _ptr(g2),
+            _ptr(dL_dmeans2D), _ptr(dL_dconic), _ptr(dL_dopacity), _ptr(dL_dcolors), _ptr(dL_ddepths), _ptr(dL_dmeans3D),
+            _ptr(dL_dsphere), _ptr(dL_du1), _ptr(dL_du2), _ptr(dL_dcov3D), None, _ptr(dL_dscales), _ptr(dL_drotations),
+            int(bool(debug)), _stream(dev))
         with torch.cuda.device(dev):
-            rc = _lib.lidargs_backward(
-                P, int(degree), M, int(R), _ptr(bg), W, H, _ptr(m3), None, _ptr(col), _ptr(sc if sc.is_cuda else None),
-                float(scale_modifier), _ptr(rot if rot.is_cuda else None), _ptr(cov if cov.is_cuda else None), _ptr(vm), None, None,
-                _ptr(beams), float(tan_fovx), float(tan_fovy), _ptr(rad),
-                _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(g0), _ptr(g1), _ptr(g2),
-                _ptr(dL_dmeans2D), _ptr(dL_dconic), _ptr(dL_dopacity), _ptr(dL_dcolors), _ptr(dL_ddepths), _ptr(dL_dmeans3D),
-                _ptr(dL_dsphere), _ptr(dL_du1), _ptr(dL_du2), _ptr(dL_dcov3D), None, _ptr(dL_dscales), _ptr(dL_drotations),
-                int(bool(debug)), _stream(dev))
+            if want_viewmatrix_grad:
+                rc = _lib.lgpose_backward_view(*common, _ptr(dL_dviewmatrix), _ptr(view_partials), n_part)
+            else:
+                rc = _lib.lidargs_backward(*common)
         if rc < 0:
             _raise(rc, "rasterize_gaussians_backward")
+    if want_viewmatrix_grad:
+        return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, dL_dviewmatrix
     return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
 
 

@@ -9,7 +9,8 @@ Public surface (what gaussian_renderer/__init__.py:121 imports and :145-179, :25
 
 `forward` returns (color[2,H,W], depth[1,H,W], occ[1,H,W], radii[P]) and is differentiable
 w.r.t. means3D, means2D (a gradient sink: .grad[:, :2] / [:, 2] feed densification,
-scene/gaussian_model.py:617-619), colors_precomp, opacities, scales, rotations, cov3D_precomp.
+scene/gaussian_model.py:617-619), colors_precomp, opacities, scales, rotations, cov3D_precomp -- and, beyond the reference, w.r.t.
+raster_settings.viewmatrix (the sensor pose) when that tensor requires grad.
 The native side is lidar-gs_amd/csrc/*.hip behind the C ABI of include/lidargs_rasterizer.h.
 """
 from typing import NamedTuple
@@ -174,8 +175,38 @@ class _RasterizeGaussians(torch.autograd.Function):
                 grad_cov3Ds, None, None)
 
 
+class _RasterizeGaussiansPose(torch.autograd.Function):
+    """The node of a frame whose `raster_settings.viewmatrix` requires grad (no reference counterpart): that tensor is one more input, in
+    front of `_RasterizeGaussians`' ten, and the backward asks the library for its gradient as well (lgpose_backward_view).  A node of its
+    own, so that the node above -- every other frame's -- stays what it was, line for line."""
+
+    @staticmethod
+    def forward(ctx, viewmatrix, *inputs):
+        return _RasterizeGaussians.forward(ctx, *inputs)                # (raster_settings.viewmatrix is this tensor)
+
+    @staticmethod
+    def backward(ctx, grad_out_color, grad_out_depth, grad_out_occ, _grad_radii):
+        rs = ctx.raster_settings
+        colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom_buffer, binning_buffer, img_buffer = ctx.saved_tensors
+        plane = lambda g, c: g if g is not None else torch.zeros((c, rs.image_height, rs.image_width), dtype=torch.float32, device=means3D.device)
+        args = (rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix,
+                rs.projmatrix, rs.beam_inclinations, rs.tanfovx, rs.tanfovy, plane(grad_out_color, 2), plane(grad_out_depth, 1), plane(grad_out_occ, 1),
+                sh, rs.sh_degree, rs.campos, geom_buffer, ctx.num_rendered, binning_buffer, img_buffer, rs.debug)
+        grads = _C.rasterize_gaussians_backward(*args, want_cov3D_grad=cov3Ds_precomp.numel() != 0, want_viewmatrix_grad=True)
+        grad_means2D, grad_colors, grad_opacities, grad_means3D, grad_cov3Ds, grad_sh, grad_scales, grad_rotations, grad_viewmatrix = grads
+        # float32 [4, 4] in the layout of raster_settings.viewmatrix, then the ten slots of the node above
+        return (grad_viewmatrix.reshape(rs.viewmatrix.shape), grad_means3D, grad_means2D, grad_sh, grad_colors, grad_opacities, grad_scales,
+                grad_rotations, grad_cov3Ds, None, None)
+
+
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
                         enqueue_state=None):
+    # The sensor pose is differentiable on request: a viewmatrix that requires grad becomes one more tensor input of the node and
+    # receives dL/dviewmatrix (the reference's formulas as written; culling, binning and the decode's view direction are not
+    # differentiated).  Otherwise the node is called exactly as before.
+    if raster_settings.viewmatrix.requires_grad and torch.is_grad_enabled():
+        return _RasterizeGaussiansPose.apply(raster_settings.viewmatrix, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                             cov3Ds_precomp, raster_settings, enqueue_state)
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                                      raster_settings, enqueue_state)
 

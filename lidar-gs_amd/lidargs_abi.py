@@ -59,16 +59,18 @@ def _param_type(decl, name):
     return ctype
 
 
-def parse_header(text):
+def parse_header(text, prefix="lidargs_"):
     """{function name: (restype, (argtypes, ...))} of every prototype in a header's text.  Comments, preprocessor lines, typedefs,
-    enums and the extern "C" braces are dropped; every statement that is left must be a `lidargs_*` prototype."""
+    enums and the extern "C" braces are dropped; every statement that is left must be a `lidargs_*` prototype (`prefix`: another
+    family of names, as the pose header's `lgpose_`)."""
+    prototype = _PROTOTYPE if prefix == "lidargs_" else re.compile(_PROTOTYPE.pattern.replace("lidargs_", re.escape(prefix)), re.S)
     src = _COMMENT.sub(" ", text)
     src = re.sub(r"^[ \t]*#.*$", " ", src, flags=re.M)
     src = re.sub(r"\b(typedef|enum)\b[^;{]*(\{[^}]*\})?[^;]*;", " ", src)
     src = re.sub(r'extern\s+"C"\s*\{', " ", src).replace("}", " ")
     sigs = {}
     for stmt in filter(None, (s.strip() for s in src.split(";"))):
-        m = _PROTOTYPE.fullmatch(stmt)
+        m = prototype.fullmatch(stmt)
         if m is None:
             raise ImportError(f"lidargs_abi: cannot parse the declaration `{' '.join(stmt.split())[:120]}`")
         name, ret = m["name"], re.sub(r"\s*\*", "*", " ".join(m["ret"].split()))
@@ -88,12 +90,24 @@ def _headers(include):
             yield f.read()
 
 
-def signatures(include=INCLUDE):
+def signatures(include=INCLUDE, prefix="lidargs_"):
     """The signatures of every header of a header directory (include/ unless another is named)."""
     sigs = {}
     for text in _headers(include):
-        sigs.update(parse_header(text))
+        sigs.update(parse_header(text, prefix))
     return sigs
+
+
+def type_also(lib, include, prefix, package="diff_lidargs_rasterization"):
+    """Types, on an already loaded `lib`, every function that the headers of a further directory declare under `prefix` (the main
+    library's pose entry points: build_hip.POSE_INCLUDE, POSE_PREFIX); a declared function the library lacks is an ImportError."""
+    for name, (restype, argtypes) in signatures(include, prefix).items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            raise ImportError(f"{package}: {os.path.basename(lib._name)} does not export {name}, which the headers declare; rebuild it") from None
+        fn.restype, fn.argtypes = restype, argtypes
+    return lib
 
 
 def constants(include=INCLUDE):
