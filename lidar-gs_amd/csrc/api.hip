@@ -475,7 +475,64 @@ int bin_frame(const BinSpec& spec, const GeomView& geom, uint2* ranges, size_t P
 
 namespace {
 
-// Which kind of frame a forward entry point asks forward_impl for: filled by field name, so that no mode hangs on an argument's position.
+// ---- a frame's arguments, stated once ---------------------------------------------------------------------------------------------
+// Every entry point fills these values BY FIELD NAME from its C parameter list and hands them on whole, so nothing in the host sequence hangs on an
+// argument's position (two swapped float* compile cleanly and show up as a wrong gradient).  What a frame does not have stays NULL / 0.
+struct FrameAllocs { lidargs_alloc_fn geometry = nullptr, binning = nullptr, image = nullptr; void* geometry_user = nullptr; void* binning_user = nullptr; void* image_user = nullptr; };
+// The scene and the sensor, for the forward and the backward alike: a backward, and the per-Gaussian chain's test hooks, leave unset what they do not read.
+struct SceneArgs {
+    int P = 0, width = 0, height = 0; float scale_modifier = 1.f, near_f = 0.f, far_f = 0.f;
+    const float* background = nullptr; const float* means3D = nullptr; const float* colors_precomp = nullptr; const float* opacities = nullptr;
+    const float* scales = nullptr; const float* rotations = nullptr; const float* cov3D_precomp = nullptr; const float* viewmatrix = nullptr; const float* beams = nullptr;
+};
+struct FrameOutputs { float* out_color = nullptr; float* out_depth = nullptr; float* out_occ = nullptr; int* radii = nullptr; int* radii_xy = nullptr; };
+struct SavedFrame {   // what a forward left for its backward
+    int R = 0; const int* radii = nullptr; char* geom_buffer = nullptr; char* binning_buffer = nullptr; char* image_buffer = nullptr; };
+// A backward's twelve gradient rows.  dL_dconic, dL_ddepths, dL_dsphere_means3D, dL_dbasis_u1/u2 are the reference's scratch gradients: optional (NULL = not materialised).
+struct GradRows {
+    float* dL_dmean2D = nullptr; float* dL_dconic = nullptr; float* dL_dopacity = nullptr; float* dL_dcolor = nullptr; float* dL_ddepths = nullptr; float* dL_dmean3D = nullptr;
+    float* dL_dsphere_means3D = nullptr; float* dL_dbasis_u1 = nullptr; float* dL_dbasis_u2 = nullptr; float* dL_dcov3D = nullptr; float* dL_dscale = nullptr; float* dL_drot = nullptr;
+    bool required(const float* cov3D_precomp) const { return dL_dmean2D && dL_dopacity && dL_dcolor && dL_dmean3D && dL_dscale && dL_drot && (!cov3D_precomp || dL_dcov3D); }
+    lg::ZeroRows zero_rows() const {   // what a backward's first launch zeroes, with the rows' widths
+        lg::ZeroRows zr; zr.add(dL_dmean2D, 4); zr.add(dL_dconic, 4); zr.add(dL_dopacity, 1); zr.add(dL_dcolor, 2); zr.add(dL_ddepths, 1); zr.add(dL_dmean3D, 3);
+        zr.add(dL_dsphere_means3D, 3); zr.add(dL_dbasis_u1, 3); zr.add(dL_dbasis_u2, 3); zr.add(dL_dcov3D, 6); zr.add(dL_dscale, 3); zr.add(dL_drot, 4);
+        return zr;
+    }
+};
+struct FrameGrads {   // in per pixel, out per Gaussian
+    const float* dL_dpix = nullptr; const float* dL_dout_depth = nullptr; const float* dL_dout_occ = nullptr; GradRows rows; };
+
+// The per-Gaussian chain's arguments from (scene, gradient rows, packed sums and touched lists); radii, det_mode, acc64, view_partials: each caller's own.
+lg::GaussBwdArgs gauss_bwd_args(const SceneArgs& sc, const GradRows& g, const float* gacc, const uint8_t* tlist, const uint16_t* tcount) {
+    lg::GaussBwdArgs gb;
+    gb.P = sc.P; gb.scale_modifier = sc.scale_modifier; gb.view = sc.viewmatrix; gb.gacc = gacc; gb.tlist = tlist; gb.tcount = tcount;
+    gb.means3D = sc.means3D; gb.scales = sc.scales; gb.rotations = sc.rotations; gb.cov3D_precomp = sc.cov3D_precomp; gb.dL_dmean2D = g.dL_dmean2D; gb.dL_dconic = g.dL_dconic; gb.dL_dopacity = g.dL_dopacity; gb.dL_dcolor = g.dL_dcolor; gb.dL_ddepths = g.dL_ddepths;
+    gb.dL_dbasis_u1 = g.dL_dbasis_u1; gb.dL_dbasis_u2 = g.dL_dbasis_u2; gb.dL_dsphere = g.dL_dsphere_means3D; gb.dL_dmean3D = g.dL_dmean3D;
+    gb.dL_dcov3D = g.dL_dcov3D; gb.dL_dscale = g.dL_dscale; gb.dL_drot = g.dL_drot;
+    return gb;
+}
+// What a blend of a frame's lists takes from (layout, the three buffer views, background, outputs), covering every segment.  What the
+// plain forward and a shell's phase 2 differ in -- run_pass1, flags, alive, T_end_out, fill -- and the T planes are each site's own.
+lg::RenderFwdArgs render_fwd_args(const lg::FrameLayout& L, const lg::GeomView& geom, const lg::BinView& bin, const lg::ImgView& img,
+                                  const float* background, const FrameOutputs& out) {
+    lg::RenderFwdArgs ra;
+    ra.grid = L.grid; ra.ranges = img.ranges; ra.point_list = bin.val_a; ra.rec = geom.rec; ra.rowspan = geom.rowspan;
+    ra.coltab = img.coltab; ra.rowtab = img.rowtab; ra.bg = background; ra.final_T = img.final_T;
+    ra.out_color = out.out_color; ra.out_depth = out.out_depth; ra.out_occ = out.out_occ;
+    ra.seg = bin.seg; ra.S = L.S; ra.seg_len = L.plan.seg_len; ra.R = L.Rp; ra.seg_lo = 0; ra.seg_hi = L.S; ra.front = 0;
+    ra.touched = geom.touched;                                         // marked wherever a contribution flag is set (cleared by the preprocess)
+    return ra;
+}
+// The selection a backward on a frame's buffers makes: which lists, which segments of them, behind which limits and flags.  The forward
+// counts with it (note_forward) and backward_impl walks with it, so the two cannot differ.
+lg::RenderBwdArgs backward_selection(const lg::FrameLayout& L, const lg::ImgView& img, const lg::BinView& bin) {
+    lg::RenderBwdArgs v = lg::RenderBwdArgs();
+    v.walk.cnt = nullptr; v.grid = L.grid; v.ranges = img.ranges; v.seg = bin.seg; v.S = L.S; v.seg_len = L.plan.seg_len; v.R = L.Rp;
+    v.alive = L.gated ? bin.alive : nullptr; v.flags = L.flags ? bin.flags : nullptr;
+    return v;
+}
+
+// Which kind of frame a forward entry point asks forward_impl for, and what only some kinds have: filled by field name like the rest.
 struct FrameMode {
     // > 0: ENQUEUE-ONLY mode.  Nothing is read back: the binning buffer is sized for `instance_capacity` instances at the caller's
     // tile height (fixed_tile_rows: 4, 8, 16 or 32), every count the later stages need stays on the device, and the 16 status words
@@ -490,6 +547,10 @@ struct FrameMode {
     // mode is the entry point's, not inferred from those arguments (round-3 advisor finding: a direct ABI caller of a single shell got
     // the fused blend and a work list here, and a backward that read planes and flags the fused blend never wrote).
     bool is_shell = false;
+    // A shell's own arguments (the defaults are the plain frame's): only Gaussians whose range lies in [shell_lo, shell_hi) are rendered, the
+    // walk starts from the T_in plane (NULL = 1), a transmittance pass produces T_out alone.
+    float shell_lo = -std::numeric_limits<float>::infinity(), shell_hi = std::numeric_limits<float>::infinity();
+    const float* T_in = nullptr; int transmittance_pass = 0; float* T_out = nullptr;
     // device word, optional: the P rows are a capacity-sized selection of which only the first *n_valid exist (enqueue-only rank frames
     // of the sharded path): the preprocess culls the rest before reading them, everything behind it sees culled Gaussians.
     const uint32_t* n_valid = nullptr;
@@ -519,36 +580,30 @@ lg::PreprocessParams preprocess_params(int P, const lg::TileGrid& grid, float sc
     return pp;
 }
 
-int forward_impl(lidargs_alloc_fn geometry_alloc, void* geometry_user, lidargs_alloc_fn binning_alloc, void* binning_user,
-                 lidargs_alloc_fn image_alloc, void* image_user, int P, const float* background, int width, int height,
-                 const float* means3D, const float* colors_precomp, const float* opacities, const float* scales,
-                 float scale_modifier, const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
-                 const float* beams, float near_f, float far_f, float shell_lo, float shell_hi, const float* T_in,
-                 int transmittance_pass, float* out_color, float* out_depth, float* out_occ, float* T_out, int* radii,
-                 int* radii_xy, int debug, hipStream_t stream, const FrameMode& mode) {
+int forward_impl(const FrameAllocs alloc, const SceneArgs sc, const FrameOutputs out, const FrameMode mode, int debug, hipStream_t stream) {
+    const int P = sc.P, width = sc.width, height = sc.height;
     const long long instance_capacity = mode.instance_capacity;
-    const int fixed_tile_rows = mode.fixed_tile_rows, col_lo = mode.col_lo, col_hi = mode.col_hi;
-    const bool is_shell = mode.is_shell;
-    const bool enqueue_only = instance_capacity > 0;
+    const int fixed_tile_rows = mode.fixed_tile_rows, col_lo = mode.col_lo, col_hi = mode.col_hi, transmittance_pass = mode.transmittance_pass;
+    const bool is_shell = mode.is_shell, enqueue_only = instance_capacity > 0;
     if (enqueue_only && !(fixed_tile_rows == 4 || fixed_tile_rows == 8 || fixed_tile_rows == 16 || fixed_tile_rows == 32))
         return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward (enqueue-only): tile_rows must be 4, 8, 16 or 32%s");
     if (enqueue_only && instance_capacity > (long long)std::numeric_limits<int>::max() - 4) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward (enqueue-only): capacity overflows int%s");
     if (P < 0 || width <= 0 || height <= 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward: bad sizes%s");
     if (height < 2) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward: need at least 2 beams%s");
     if (height > 65535 || width > 65535 * 16) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward: image too large%s");
-    if (colors_precomp == nullptr) return fail(LIDARGS_ERR_NO_COLORS, "For non-RGB, provide precomputed Gaussian colors!%s");
-    if (!means3D || !opacities || !viewmatrix || !beams || !out_color || !out_depth || !out_occ || !radii)   // radii_xy: optional
+    if (sc.colors_precomp == nullptr) return fail(LIDARGS_ERR_NO_COLORS, "For non-RGB, provide precomputed Gaussian colors!%s");
+    if (!sc.means3D || !sc.opacities || !sc.viewmatrix || !sc.beams || !out.out_color || !out.out_depth || !out.out_occ || !out.radii)   // radii_xy: optional
         return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward: NULL required pointer%s");
-    if (!cov3D_precomp && (!scales || !rotations)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward: need scales+rotations or cov3D_precomp%s");
-    if (!geometry_alloc || !binning_alloc || !image_alloc) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward: NULL allocator%s");
+    if (!sc.cov3D_precomp && (!sc.scales || !sc.rotations)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward: need scales+rotations or cov3D_precomp%s");
+    if (!alloc.geometry || !alloc.binning || !alloc.image) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward: NULL allocator%s");
     if (P == 0) return 0;   // R3/rasterize_points.cu:87: outputs stay as the caller initialised them
 
     const lg::TileGrid grid4 = lg::make_grid(width, height, 4);        // the image buffer is laid out for the finest tiling
     lg::prof_begin(stream, 0);
 
-    char* geom_p = geometry_alloc(geometry_user, lg::geom_carve(nullptr, (size_t)P, lg::GAUSS_BUFFERS, nullptr, mode.deterministic));
+    char* geom_p = alloc.geometry(alloc.geometry_user, lg::geom_carve(nullptr, (size_t)P, lg::GAUSS_BUFFERS, nullptr, mode.deterministic));
     if (!geom_p) return fail(LIDARGS_ERR_ALLOC, "geometry allocator returned NULL%s");
-    char* img_p = image_alloc(image_user, lg::img_carve(nullptr, width, height, grid4.num_tiles(), nullptr, mode.median));
+    char* img_p = alloc.image(alloc.image_user, lg::img_carve(nullptr, width, height, grid4.num_tiles(), nullptr, mode.median));
     if (!img_p) return fail(LIDARGS_ERR_ALLOC, "image allocator returned NULL%s");
     lg::GeomView geom; lg::geom_carve(geom_p, (size_t)P, lg::GAUSS_BUFFERS, &geom);
     lg::ImgView img; lg::img_carve(img_p, width, height, grid4.num_tiles(), &img);
@@ -562,7 +617,7 @@ int forward_impl(lidargs_alloc_fn geometry_alloc, void* geometry_user, lidargs_a
         LG_HIP(hipMemsetD32Async((hipDeviceptr_t)(geom.totals + LG_TOTALS_MODE_WORD), (int)lg::LG_MODE_MEDIAN, 1, stream));
     }
 
-    lg::PreprocessParams pp = preprocess_params(P, grid4, scale_modifier, near_f, far_f, shell_lo, shell_hi, viewmatrix);
+    lg::PreprocessParams pp = preprocess_params(P, grid4, sc.scale_modifier, sc.near_f, sc.far_f, mode.shell_lo, mode.shell_hi, sc.viewmatrix);
     pp.compact = lg::compact_spans(grid4.tiles_x, height) ? 1 : 0;
     pp.prune = lg::prune_footprints() ? 1 : 0;
     if (col_lo >= 0) {                                                   // column wedge: whole 16-pixel tile columns
@@ -572,35 +627,27 @@ int forward_impl(lidargs_alloc_fn geometry_alloc, void* geometry_user, lidargs_a
     }
     pp.n_valid = mode.n_valid;
 
-    lg::launch_preprocess(pp, means3D, scales, rotations, opacities, colors_precomp, cov3D_precomp, beams, radii, radii_xy,
+    lg::launch_preprocess(pp, sc.means3D, sc.scales, sc.rotations, sc.opacities, sc.colors_precomp, sc.cov3D_precomp, sc.beams, out.radii, out.radii_xy,
                           geom, &img, false, stream);                  // also fills the pixel-ray tables of the image buffer
     LG_STAGE_CHECK("preprocess");
     lg::prof_mark("preprocess", stream);
 
     const lg::BinSpec spec = {is_shell ? lg::FRAME_SHELL : lg::FRAME_GAUSS, fixed_tile_rows, instance_capacity, mode.status_host, "forward"};
     lg::BinnedFrame bf;
-    const int rendered = lg::bin_frame(spec, geom, img.ranges, (size_t)P, width, height, col_lo, col_hi, pp.compact != 0, binning_alloc, binning_user,
+    const int rendered = lg::bin_frame(spec, geom, img.ranges, (size_t)P, width, height, col_lo, col_hi, pp.compact != 0, alloc.binning, alloc.binning_user,
                                        debug, stream, &bf);
     if (rendered < 0) return rendered;
     const lg::FrameLayout& L = bf.L;
     const lg::BinView& bin = bf.bin;
     const size_t R = bf.R;
 
-    lg::RenderFwdArgs ra;
-    ra.fill.cnt = nullptr;
-    ra.grid = L.grid; ra.ranges = img.ranges; ra.point_list = bin.val_a; ra.rec = geom.rec; ra.rowspan = geom.rowspan;
-    ra.coltab = img.coltab; ra.rowtab = img.rowtab; ra.bg = background; ra.T_in = T_in;
-    ra.final_T = img.final_T; ra.T_pass = T_out;
-    ra.out_color = out_color; ra.out_depth = out_depth; ra.out_occ = out_occ;
-    ra.seg = bin.seg; ra.S = L.S; ra.seg_len = L.plan.seg_len;
+    lg::RenderFwdArgs ra = render_fwd_args(L, geom, bin, img, sc.background, out);
+    ra.fill.cnt = nullptr; ra.T_in = mode.T_in; ra.T_pass = mode.T_out; ra.transmittance_only = transmittance_pass;
     ra.run_pass1 = (L.S > 1 || transmittance_pass || is_shell) ? 1 : 0;   // (a shell's backward always reads the flags)
-    ra.flags = ra.run_pass1 ? bin.flags : nullptr; ra.R = L.Rp;
-    ra.touched = geom.touched;                                         // marked wherever a contribution flag is set (cleared by the preprocess)
-    ra.transmittance_only = transmittance_pass;
-    ra.seg_lo = 0; ra.seg_hi = L.S; ra.front = 0; ra.alive = nullptr;
+    ra.flags = ra.run_pass1 ? bin.flags : nullptr; ra.alive = nullptr;
     int head = 0;                                                      // segments at the head of every list that round 1 walked completely
     // no flags (a one-segment plan: LIDARGS_MAX_SEGMENTS=1): pass 2 and the backward walk every listed entry, so every Gaussian may be added to
-    if (!L.fused && !ra.run_pass1 && R) lg::launch_touch_all(geom.touched, radii, (size_t)P, stream);
+    if (!L.fused && !ra.run_pass1 && R) lg::launch_touch_all(geom.touched, out.radii, (size_t)P, stream);
     if (L.fused) {
         ra.flags = bin.flags; ra.alive = bin.alive;
         lg::launch_render_fused(ra, stream);
@@ -626,47 +673,38 @@ int forward_impl(lidargs_alloc_fn geometry_alloc, void* geometry_user, lidargs_a
     if (mode.median) {   // behind either form of the blend: out_depth becomes the picked Gaussian's range, the image buffer's last plane names it
         lg::MedianFwdArgs ma;
         ma.grid = L.grid; ma.ranges = img.ranges; ma.point_list = bin.val_a; ma.rec = geom.rec; ma.rowspan = geom.rowspan;
-        ma.coltab = img.coltab; ma.rowtab = img.rowtab; ma.out_depth = out_depth; ma.median_id = img.median_id;
+        ma.coltab = img.coltab; ma.rowtab = img.rowtab; ma.out_depth = out.out_depth; ma.median_id = img.median_id;
         lg::launch_render_median(ma, mode.strongest, stream);
         LG_STAGE_CHECK(mode.strongest ? "render strongest" : "render median");
         lg::prof_mark(mode.strongest ? "render_strongest" : "render_median", stream);
     }
 
-    // the selection a backward on these buffers will make (backward_impl builds the same view): counted now, while the buffers are certainly alive
-    lg::RenderBwdArgs v = lg::RenderBwdArgs();
-    v.walk.cnt = nullptr; v.grid = L.grid; v.ranges = img.ranges; v.seg = bin.seg; v.S = L.S; v.seg_len = L.plan.seg_len; v.R = L.Rp;
-    v.alive = L.gated ? bin.alive : nullptr;
-    v.flags = L.flags ? bin.flags : nullptr;
+    // the selection a backward on these buffers will make (backward_impl starts from the same call): counted now, while the buffers are certainly alive
+    const lg::RenderBwdArgs v = backward_selection(L, img, bin);
     lg::note_forward((size_t)P, R, L, geom.totals, ra.flags, geom.touched, (R != 0 && !transmittance_pass) ? &v : nullptr, stream);
     return rendered;
 }
 
-// The same for backward_impl: which forward made the buffers (its layout must be carved the same way) and what lies behind a shell.
+// The same for backward_impl: which forward made the buffers (its layout must be carved the same way), what lies behind a shell, the pose form's extras.
 struct BackMode {
     bool is_shell = false;                       // the buffers are lidargs_forward_shell*'s
     const float* behind = nullptr;               // shell: the colour / depth sums of the shells behind this one, per pixel
     const float* T_final_global = nullptr;       // shell: the frame's final transmittance, per pixel
     int col_lo = -1, col_hi = -1;                // >= 0: the buffers are a column wedge's
+    float* dL_dviewmatrix = nullptr;             // lgpose_backward_view: run the chain's pose form and fold its partial rows into these sixteen
+    float* view_partials = nullptr;              // ... through this scratch (lgpose_view_partial_floats)
 };
 
-int backward_impl(int P, int R, const float* background, int width, int height, const float* means3D,
-                  const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
-                  const float* cov3D_precomp, const float* viewmatrix, const float* beams, const int* radii, char* geom_buffer,
-                  char* binning_buffer, char* image_buffer, const BackMode& mode, const float* dL_dpix, const float* dL_dout_depth, const float* dL_dout_occ, float* dL_dmean2D,
-                  float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_ddepths, float* dL_dmean3D,
-                  float* dL_dsphere_means3D, float* dL_dbasis_u1, float* dL_dbasis_u2, float* dL_dcov3D, float* dL_dscale,
-                  float* dL_drot, int debug, hipStream_t stream, float* dL_dviewmatrix = nullptr, float* view_partials = nullptr) {
-    (void)colors_precomp; (void)beams;
-    const int col_lo = mode.col_lo, col_hi = mode.col_hi;
+int backward_impl(const SceneArgs sc, const SavedFrame saved, const FrameGrads grads, const BackMode mode, int debug, hipStream_t stream) {
+    const int P = sc.P, R = saved.R, width = sc.width, height = sc.height, col_lo = mode.col_lo, col_hi = mode.col_hi;
+    const GradRows& rows = grads.rows;
     if (P < 0 || R < 0 || width <= 0 || height <= 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "backward: bad sizes%s");
     if (P == 0) return 0;   // R3/rasterize_points.cu:177
-    if (!geom_buffer || !binning_buffer || !image_buffer) return fail(LIDARGS_ERR_STATE, "backward: missing forward buffers%s");
-    // dL_dconic, dL_ddepths, dL_dsphere_means3D, dL_dbasis_u1/u2 are the reference's scratch gradients: optional here
-    if (!means3D || !viewmatrix || !radii || !dL_dpix || !dL_dout_depth || !dL_dout_occ || !dL_dmean2D ||
-        !dL_dopacity || !dL_dcolor || !dL_dmean3D || !dL_dscale || !dL_drot || (cov3D_precomp && !dL_dcov3D))
+    if (!saved.geom_buffer || !saved.binning_buffer || !saved.image_buffer) return fail(LIDARGS_ERR_STATE, "backward: missing forward buffers%s");
+    if (!sc.means3D || !sc.viewmatrix || !saved.radii || !grads.dL_dpix || !grads.dL_dout_depth || !grads.dL_dout_occ || !rows.required(sc.cov3D_precomp))
         return fail(LIDARGS_ERR_INVALID_ARGUMENT, "backward: NULL required pointer%s");
 
-    lg::GeomView geom; lg::geom_carve(geom_buffer, (size_t)P, lg::GAUSS_BUFFERS, &geom);
+    lg::GeomView geom; lg::geom_carve(saved.geom_buffer, (size_t)P, lg::GAUSS_BUFFERS, &geom);
     // The accumulation mode is the forward's and travels in the geometry buffer (LG_TOTALS_MODE_WORD); the host never reads it.  On a plain
     // frame's buffers the kernels are handed the word and the place deterministic buffers keep their 64-bit lines at; shell and wedge
     // forwards refuse the mode, so their backwards do not look -- and nobody looks in a process that never made a deterministic forward.
@@ -678,27 +716,19 @@ int backward_impl(int P, int R, const float* background, int width, int height, 
     // a column wedge's buffers: only its own patches were rendered
     if (col_lo >= 0 && (col_lo % LG_TILE_W || col_hi <= col_lo || col_hi > width)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "backward: bad column wedge%s");
     const lg::FrameLayout L = lg::frame_layout(R, width, height, col_lo, col_hi, mode.is_shell ? lg::FRAME_SHELL : lg::FRAME_GAUSS);   // (from the forward's num_rendered)
-    lg::BinView bin; L.bin_carve(binning_buffer, &bin);
-    lg::ImgView img; lg::img_carve(image_buffer, width, height, lg::make_grid(width, height, 4).num_tiles(), &img);
+    lg::BinView bin; L.bin_carve(saved.binning_buffer, &bin);
+    lg::ImgView img; lg::img_carve(saved.image_buffer, width, height, lg::make_grid(width, height, 4).num_tiles(), &img);
     lg::prof_begin(stream, 1);
 
     // Only the Gaussians the forward marked as touched are ever added to, and every backward on these buffers (the first, or a later one
     // under retain_graph) starts by clearing exactly their packed lines, listing them, and zeroing the caller's gradient rows.
-    lg::ZeroRows zr;
-    zr.add(dL_dmean2D, 4); zr.add(dL_dconic, 4); zr.add(dL_dopacity, 1); zr.add(dL_dcolor, 2); zr.add(dL_ddepths, 1); zr.add(dL_dmean3D, 3);
-    zr.add(dL_dsphere_means3D, 3); zr.add(dL_dbasis_u1, 3); zr.add(dL_dbasis_u2, 3); zr.add(dL_dcov3D, 6); zr.add(dL_dscale, 3); zr.add(dL_drot, 4);
-    lg::launch_zero_touched(geom.touched, reinterpret_cast<float4*>(geom.gacc), 4, (size_t)P, geom.tlist, geom.tcount, zr, stream, det_mode, geom.acc64);
+    lg::launch_zero_touched(geom.touched, reinterpret_cast<float4*>(geom.gacc), 4, (size_t)P, geom.tlist, geom.tcount, rows.zero_rows(), stream, det_mode, geom.acc64);
     lg::prof_mark("bwd_zero", stream);
 
-    lg::RenderBwdArgs rb;
-    rb.walk.cnt = nullptr;
-    rb.grid = L.grid; rb.ranges = img.ranges; rb.point_list = bin.val_a; rb.rec = geom.rec; rb.rowspan = geom.rowspan;
-    rb.coltab = img.coltab; rb.rowtab = img.rowtab; rb.bg = background; rb.final_T = img.final_T;
-    rb.seg = bin.seg; rb.S = L.S; rb.seg_len = L.plan.seg_len;
-    rb.alive = L.gated ? bin.alive : nullptr;
-    rb.flags = L.flags ? bin.flags : nullptr; rb.R = L.Rp;
+    lg::RenderBwdArgs rb = backward_selection(L, img, bin);
+    rb.point_list = bin.val_a; rb.rec = geom.rec; rb.rowspan = geom.rowspan; rb.coltab = img.coltab; rb.rowtab = img.rowtab; rb.bg = sc.background; rb.final_T = img.final_T;
     rb.T_final_global = mode.T_final_global; rb.behind = mode.behind;
-    rb.dL_dpix = dL_dpix; rb.dL_ddepth = dL_dout_depth; rb.dL_docc = dL_dout_occ; rb.gacc = geom.gacc;
+    rb.dL_dpix = grads.dL_dpix; rb.dL_ddepth = grads.dL_dout_depth; rb.dL_docc = grads.dL_dout_occ; rb.gacc = geom.gacc;
     if (L.work_list) rb.walk = lg::work_list(bin);
     rb.det_mode = (may_be_det || may_be_median) ? geom.totals + LG_TOTALS_MODE_WORD : nullptr;
     rb.acc64 = may_be_det ? geom.acc64 : nullptr;
@@ -708,26 +738,18 @@ int backward_impl(int P, int R, const float* background, int width, int height, 
     if (may_be_median) {
         // (img.median_id is computed from the default size of the image buffer: on a default buffer it points behind it and is never read)
         lg::MedianBwdArgs mb;
-        mb.mode = geom.totals + LG_TOTALS_MODE_WORD; mb.median_id = img.median_id; mb.dL_ddepth = dL_dout_depth; mb.gacc = geom.gacc;
+        mb.mode = geom.totals + LG_TOTALS_MODE_WORD; mb.median_id = img.median_id; mb.dL_ddepth = grads.dL_dout_depth; mb.gacc = geom.gacc;
         mb.N = (size_t)width * height; mb.P = (uint32_t)P;
         lg::launch_median_backward(mb, stream);
         LG_STAGE_CHECK("median backward");
         lg::prof_mark("median_bwd", stream);
     }
 
-    lg::GaussBwdArgs gb;
-    gb.P = P; gb.scale_modifier = scale_modifier;
-    gb.view = viewmatrix;
-    gb.means3D = means3D; gb.scales = scales; gb.rotations = rotations; gb.cov3D_precomp = cov3D_precomp; gb.radii = radii;
-    gb.gacc = geom.gacc; gb.tlist = geom.tlist; gb.tcount = geom.tcount;
-    gb.dL_dmean2D = dL_dmean2D; gb.dL_dconic = dL_dconic; gb.dL_dopacity = dL_dopacity; gb.dL_dcolor = dL_dcolor;
-    gb.dL_ddepths = dL_ddepths; gb.dL_dbasis_u1 = dL_dbasis_u1; gb.dL_dbasis_u2 = dL_dbasis_u2;
-    gb.dL_dsphere = dL_dsphere_means3D; gb.dL_dmean3D = dL_dmean3D; gb.dL_dcov3D = dL_dcov3D; gb.dL_dscale = dL_dscale;
-    gb.dL_drot = dL_drot;
-    gb.det_mode = det_mode; gb.acc64 = geom.acc64;
-    if (dL_dviewmatrix) {   // lgpose_backward_view: the chain's pose form and the fold of its partial rows (two launches for one)
-        gb.view_partials = view_partials;
-        lg::launch_gaussian_backward_view(gb, dL_dviewmatrix, stream);
+    lg::GaussBwdArgs gb = gauss_bwd_args(sc, rows, geom.gacc, geom.tlist, geom.tcount);
+    gb.radii = saved.radii; gb.det_mode = det_mode; gb.acc64 = geom.acc64;
+    if (mode.dL_dviewmatrix) {   // lgpose_backward_view: the chain's pose form and the fold of its partial rows (two launches for one)
+        gb.view_partials = mode.view_partials;
+        lg::launch_gaussian_backward_view(gb, mode.dL_dviewmatrix, stream);
     } else lg::launch_gaussian_backward(gb, stream);
     LG_STAGE_CHECK("gaussian backward");
     lg::prof_mark("gaussian_bwd", stream);
@@ -736,6 +758,27 @@ int backward_impl(int P, int R, const float* background, int width, int height, 
 
 }  // namespace
 
+// The C parameter lists onto the argument structs.  The six 3-D forwards spell their common parameters with the same names, and so do the four backwards:
+// each mapping is written once, as a macro because only the preprocessor can take a name from the entry point it is used in.  Every field is bound BY NAME.
+#define LG_FORWARD_ARGS(alloc, sc, out)                                                                                                                                                     \
+    FrameAllocs alloc; SceneArgs sc; FrameOutputs out;                                                                                                                                      \
+    alloc.geometry = geometry_alloc; alloc.geometry_user = geometry_user; alloc.binning = binning_alloc; alloc.binning_user = binning_user; alloc.image = image_alloc; alloc.image_user = image_user;\
+    sc.P = P; sc.width = width; sc.height = height; sc.background = background; sc.means3D = means3D; sc.colors_precomp = colors_precomp; sc.opacities = opacities; sc.scales = scales;     \
+    sc.scale_modifier = scale_modifier; sc.rotations = rotations; sc.cov3D_precomp = cov3D_precomp; sc.viewmatrix = viewmatrix; sc.beams = beam_inclinations;                               \
+    sc.near_f = (float)lidar_near; sc.far_f = (float)lidar_far;                                                                                                                             \
+    out.out_color = out_color; out.out_depth = out_depth; out.out_occ = out_occ; out.radii = radii; out.radii_xy = radii_xy
+// What the chain reads of the scene (the backwards and the chain's two test hooks); the seven rows every one of them has; the five scratch rows lidargs_backward_wedge lacks.
+#define LG_CHAIN_SCENE(sc)                                                                                                                                                                  \
+    sc.P = P; sc.means3D = means3D; sc.scales = scales; sc.scale_modifier = scale_modifier; sc.rotations = rotations; sc.cov3D_precomp = cov3D_precomp; sc.viewmatrix = viewmatrix
+#define LG_GRAD_ROWS(rows)                                                                                                                                                                  \
+    rows.dL_dmean2D = dL_dmean2D; rows.dL_dopacity = dL_dopacity; rows.dL_dcolor = dL_dcolor; rows.dL_dmean3D = dL_dmean3D; rows.dL_dcov3D = dL_dcov3D; rows.dL_dscale = dL_dscale; rows.dL_drot = dL_drot
+#define LG_SCRATCH_ROWS(rows)                                                                                                                                                               \
+    rows.dL_dconic = dL_dconic; rows.dL_ddepths = dL_ddepths; rows.dL_dsphere_means3D = dL_dsphere_means3D; rows.dL_dbasis_u1 = dL_dbasis_u1; rows.dL_dbasis_u2 = dL_dbasis_u2
+#define LG_BACKWARD_ARGS(sc, saved, grads)                                                                                                                                                  \
+    SceneArgs sc; SavedFrame saved; FrameGrads grads;                                                                                                                                       \
+    LG_CHAIN_SCENE(sc); sc.width = width; sc.height = height; sc.background = background;                                                                                                   \
+    saved.R = R; saved.radii = radii; saved.geom_buffer = geom_buffer; saved.binning_buffer = binning_buffer; saved.image_buffer = image_buffer;                                            \
+    grads.dL_dpix = dL_dpix; grads.dL_dout_depth = dL_dout_depth; grads.dL_dout_occ = dL_dout_occ; LG_GRAD_ROWS(grads.rows)
 extern "C" {
 
 int lidargs_abi_version(void) { return LIDARGS_ABI_VERSION; }
@@ -749,17 +792,14 @@ int lidargs_forward(lidargs_alloc_fn geometry_alloc, void* geometry_user, lidarg
                     int prefiltered, int lidar_far, int lidar_near, float* out_color, float* out_depth, float* out_occ,
                     int* radii, int* radii_xy, int debug, void* stream) {
     (void)D; (void)M; (void)shs; (void)projmatrix; (void)cam_pos; (void)prefiltered;
-    const float inf = std::numeric_limits<float>::infinity();
     FrameMode mode;
     mode.deterministic = lg::deterministic_requested();
     mode.strongest = lg::strongest_depth_requested();
     mode.median = mode.strongest || lg::median_depth_requested();
     if (mode.deterministic && mode.median)   // (a picked Gaussian's depth gradient is added with a float atomic: not what the other switch promises)
         return fail(LIDARGS_ERR_INVALID_ARGUMENT, "%s: a non-default LIDARGS_DEPTH (median, strongest) is not supported together with LIDARGS_DETERMINISTIC=1; unset one of them for this call", "lidargs_forward");
-    return forward_impl(geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user, P, background, width,
-                        height, means3D, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix,
-                        beam_inclinations, (float)lidar_near, (float)lidar_far, -inf, inf, nullptr, 0, out_color, out_depth,
-                        out_occ, nullptr, radii, radii_xy, debug, (hipStream_t)stream, mode);
+    LG_FORWARD_ARGS(alloc, sc, out);
+    return forward_impl(alloc, sc, out, mode, debug, (hipStream_t)stream);
 }
 
 int lidargs_forward_enqueue(lidargs_alloc_fn geometry_alloc, void* geometry_user, lidargs_alloc_fn binning_alloc, void* binning_user,
@@ -770,16 +810,12 @@ int lidargs_forward_enqueue(lidargs_alloc_fn geometry_alloc, void* geometry_user
                             int prefiltered, int lidar_far, int lidar_near, float* out_color, float* out_depth, float* out_occ,
                             int* radii, int* radii_xy, int debug, int instance_capacity, int tile_rows, unsigned* status_host, void* stream) {
     (void)D; (void)M; (void)shs; (void)projmatrix; (void)cam_pos; (void)prefiltered;
-    if (const int rc = lg::refuse_deterministic("lidargs_forward_enqueue")) return rc;
-    if (const int rc = lg::refuse_depth_mode("lidargs_forward_enqueue")) return rc;
+    if (const int rc = lg::refuse_modes("lidargs_forward_enqueue")) return rc;
     if (instance_capacity <= 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward_enqueue: instance_capacity must be positive%s");
-    const float inf = std::numeric_limits<float>::infinity();
     FrameMode mode;
     mode.instance_capacity = instance_capacity; mode.fixed_tile_rows = tile_rows; mode.status_host = status_host;
-    return forward_impl(geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user, P, background, width,
-                        height, means3D, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix,
-                        beam_inclinations, (float)lidar_near, (float)lidar_far, -inf, inf, nullptr, 0, out_color, out_depth,
-                        out_occ, nullptr, radii, radii_xy, debug, (hipStream_t)stream, mode);
+    LG_FORWARD_ARGS(alloc, sc, out);
+    return forward_impl(alloc, sc, out, mode, debug, (hipStream_t)stream);
 }
 
 int lidargs_backward(int P, int D, int M, int R, const float* background, int width, int height, const float* means3D,
@@ -791,11 +827,9 @@ int lidargs_backward(int P, int D, int M, int R, const float* background, int wi
                      float* dL_dopacity, float* dL_dcolor, float* dL_ddepths, float* dL_dmean3D, float* dL_dsphere_means3D,
                      float* dL_dbasis_u1, float* dL_dbasis_u2, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
                      int debug, void* stream) {
-    (void)D; (void)M; (void)shs; (void)projmatrix; (void)campos; (void)tan_fovx; (void)tan_fovy; (void)dL_dsh;
-    return backward_impl(P, R, background, width, height, means3D, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
-                         viewmatrix, beam_inclinations, radii, geom_buffer, binning_buffer, image_buffer, BackMode(), dL_dpix,
-                         dL_dout_depth, dL_dout_occ, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_ddepths, dL_dmean3D,
-                         dL_dsphere_means3D, dL_dbasis_u1, dL_dbasis_u2, dL_dcov3D, dL_dscale, dL_drot, debug, (hipStream_t)stream);
+    (void)D; (void)M; (void)shs; (void)colors_precomp; (void)projmatrix; (void)campos; (void)beam_inclinations; (void)tan_fovx; (void)tan_fovy; (void)dL_dsh;
+    LG_BACKWARD_ARGS(sc, saved, grads); LG_SCRATCH_ROWS(grads.rows);
+    return backward_impl(sc, saved, grads, BackMode(), debug, (hipStream_t)stream);
 }
 
 size_t lgpose_view_partial_floats(int P) { return lg::view_partial_floats(P); }
@@ -809,7 +843,7 @@ int lgpose_backward_view(int P, int D, int M, int R, const float* background, in
                           float* dL_dopacity, float* dL_dcolor, float* dL_ddepths, float* dL_dmean3D, float* dL_dsphere_means3D,
                           float* dL_dbasis_u1, float* dL_dbasis_u2, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
                           int debug, void* stream, float* dL_dviewmatrix, float* view_partials, size_t view_partial_floats) {
-    (void)D; (void)M; (void)shs; (void)projmatrix; (void)campos; (void)tan_fovx; (void)tan_fovy; (void)dL_dsh;
+    (void)D; (void)M; (void)shs; (void)colors_precomp; (void)projmatrix; (void)campos; (void)beam_inclinations; (void)tan_fovx; (void)tan_fovy; (void)dL_dsh;
     if (P < 0 || R < 0 || width <= 0 || height <= 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "backward_view: bad sizes%s");
     if (!dL_dviewmatrix) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "backward_view: dL_dviewmatrix is NULL%s");
     if (P == 0) {   // lidargs_backward's early return, and the sixteen zeros
@@ -818,11 +852,9 @@ int lgpose_backward_view(int P, int D, int M, int R, const float* background, in
     }
     if (!view_partials || ((uintptr_t)view_partials & 15u) || view_partial_floats < lg::view_partial_floats(P))
         return fail(LIDARGS_ERR_INVALID_ARGUMENT, "backward_view: view_partials is NULL, not 16-byte aligned or shorter than lgpose_view_partial_floats(P)%s");
-    return backward_impl(P, R, background, width, height, means3D, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
-                         viewmatrix, beam_inclinations, radii, geom_buffer, binning_buffer, image_buffer, BackMode(), dL_dpix,
-                         dL_dout_depth, dL_dout_occ, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_ddepths, dL_dmean3D,
-                         dL_dsphere_means3D, dL_dbasis_u1, dL_dbasis_u2, dL_dcov3D, dL_dscale, dL_drot, debug, (hipStream_t)stream,
-                         dL_dviewmatrix, view_partials);
+    BackMode mode; mode.dL_dviewmatrix = dL_dviewmatrix; mode.view_partials = view_partials;
+    LG_BACKWARD_ARGS(sc, saved, grads); LG_SCRATCH_ROWS(grads.rows);
+    return backward_impl(sc, saved, grads, mode, debug, (hipStream_t)stream);
 }
 
 int lidargs_visible_filter(lidargs_alloc_fn geometry_alloc, void* geometry_user, lidargs_alloc_fn binning_alloc, void* binning_user,
@@ -1033,29 +1065,18 @@ int lidargs_debug_gaussian_backward(int P, int line_f4, int stage, const unsigne
     if (stage < 0 || stage > 2 || (line_f4 == 8 && stage != 1)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_gaussian_backward: stage must be 0, 1 or 2, and 1 for the surfel line%s");
     if (!touched || !gacc || !tlist || !tcount) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_gaussian_backward: NULL required pointer%s");
     const bool chain = stage != 1;
+    SceneArgs sc; GradRows rows; LG_CHAIN_SCENE(sc); LG_GRAD_ROWS(rows); LG_SCRATCH_ROWS(rows);
     // the chain's rows, as backward_impl requires them (dL_dconic, dL_ddepths, dL_dsphere_means3D, dL_dbasis_u1/u2 stay optional)
-    if (chain && (!means3D || !viewmatrix || !dL_dmean2D || !dL_dopacity || !dL_dcolor || !dL_dmean3D || !dL_dscale || !dL_drot ||
-                  (cov3D_precomp && !dL_dcov3D)))
+    if (chain && (!means3D || !viewmatrix || !rows.required(cov3D_precomp)))
         return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_gaussian_backward: NULL required pointer%s");
     if (chain && !cov3D_precomp && (!scales || !rotations)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_gaussian_backward: need scales+rotations or cov3D_precomp%s");
     if (P == 0) return 0;
-    lg::ZeroRows zr;
-    zr.add(dL_dmean2D, 4); zr.add(dL_dconic, 4); zr.add(dL_dopacity, 1); zr.add(dL_dcolor, 2); zr.add(dL_ddepths, 1); zr.add(dL_dmean3D, 3);
-    zr.add(dL_dsphere_means3D, 3); zr.add(dL_dbasis_u1, 3); zr.add(dL_dbasis_u2, 3); zr.add(dL_dcov3D, 6); zr.add(dL_dscale, 3); zr.add(dL_drot, 4);
     if (stage != 2) {
-        lg::launch_zero_touched(touched, reinterpret_cast<float4*>(gacc), line_f4, (size_t)P, tlist, tcount, zr, stream);
+        lg::launch_zero_touched(touched, reinterpret_cast<float4*>(gacc), line_f4, (size_t)P, tlist, tcount, rows.zero_rows(), stream);
         LG_STAGE_CHECK("debug zero touched");
     }
     if (!chain) return 0;
-    lg::GaussBwdArgs gb;
-    gb.P = P; gb.scale_modifier = scale_modifier;
-    gb.view = viewmatrix;
-    gb.means3D = means3D; gb.scales = scales; gb.rotations = rotations; gb.cov3D_precomp = cov3D_precomp; gb.radii = nullptr;
-    gb.gacc = gacc; gb.tlist = tlist; gb.tcount = tcount;
-    gb.dL_dmean2D = dL_dmean2D; gb.dL_dconic = dL_dconic; gb.dL_dopacity = dL_dopacity; gb.dL_dcolor = dL_dcolor;
-    gb.dL_ddepths = dL_ddepths; gb.dL_dbasis_u1 = dL_dbasis_u1; gb.dL_dbasis_u2 = dL_dbasis_u2;
-    gb.dL_dsphere = dL_dsphere_means3D; gb.dL_dmean3D = dL_dmean3D; gb.dL_dcov3D = dL_dcov3D; gb.dL_dscale = dL_dscale;
-    gb.dL_drot = dL_drot;
+    lg::GaussBwdArgs gb = gauss_bwd_args(sc, rows, gacc, tlist, tcount); gb.radii = nullptr;
     lg::launch_gaussian_backward(gb, stream);
     LG_STAGE_CHECK("debug gaussian backward");
     return 0;
@@ -1077,20 +1098,11 @@ int lgpose_debug_view_backward(int P, const float* gacc, const float* means3D, c
     }
     if (!view_partials || ((uintptr_t)view_partials & 15u) || view_partial_floats < lg::view_partial_floats(P))
         return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_view_backward: view_partials is NULL, not 16-byte aligned or shorter than lgpose_view_partial_floats(P)%s");
-    if (!gacc || !tlist || !tcount || !means3D || !viewmatrix || !dL_dmean2D || !dL_dopacity || !dL_dcolor || !dL_dmean3D || !dL_dscale || !dL_drot ||
-        (cov3D_precomp && !dL_dcov3D) || ((mode_word == nullptr) != (acc64 == nullptr)))
+    SceneArgs sc; GradRows rows; LG_CHAIN_SCENE(sc); LG_GRAD_ROWS(rows); LG_SCRATCH_ROWS(rows);
+    if (!gacc || !tlist || !tcount || !means3D || !viewmatrix || !rows.required(cov3D_precomp) || ((mode_word == nullptr) != (acc64 == nullptr)))
         return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_view_backward: NULL required pointer%s");
     if (!cov3D_precomp && (!scales || !rotations)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_view_backward: need scales+rotations or cov3D_precomp%s");
-    lg::GaussBwdArgs gb;
-    gb.P = P; gb.scale_modifier = scale_modifier;
-    gb.view = viewmatrix;
-    gb.means3D = means3D; gb.scales = scales; gb.rotations = rotations; gb.cov3D_precomp = cov3D_precomp; gb.radii = nullptr;
-    gb.gacc = gacc; gb.tlist = tlist; gb.tcount = tcount;
-    gb.dL_dmean2D = dL_dmean2D; gb.dL_dconic = dL_dconic; gb.dL_dopacity = dL_dopacity; gb.dL_dcolor = dL_dcolor;
-    gb.dL_ddepths = dL_ddepths; gb.dL_dbasis_u1 = dL_dbasis_u1; gb.dL_dbasis_u2 = dL_dbasis_u2;
-    gb.dL_dsphere = dL_dsphere_means3D; gb.dL_dmean3D = dL_dmean3D; gb.dL_dcov3D = dL_dcov3D; gb.dL_dscale = dL_dscale;
-    gb.dL_drot = dL_drot;
-    gb.det_mode = mode_word; gb.acc64 = acc64;
+    lg::GaussBwdArgs gb = gauss_bwd_args(sc, rows, gacc, tlist, tcount); gb.radii = nullptr; gb.det_mode = mode_word; gb.acc64 = acc64;
     gb.view_partials = view_partials;
     lg::launch_gaussian_backward_view(gb, dL_dviewmatrix, stream);
     LG_STAGE_CHECK("debug view backward");
@@ -1104,14 +1116,12 @@ int lidargs_forward_shell(lidargs_alloc_fn geometry_alloc, void* geometry_user, 
                           const float* beam_inclinations, int lidar_far, int lidar_near, float shell_lo, float shell_hi,
                           const float* T_in, int transmittance_pass, float* out_color, float* out_depth, float* out_occ,
                           float* T_out, int* radii, int* radii_xy, int debug, void* stream) {
-    if (const int rc = lg::refuse_deterministic("lidargs_forward_shell")) return rc;
-    if (const int rc = lg::refuse_depth_mode("lidargs_forward_shell")) return rc;
+    if (const int rc = lg::refuse_modes("lidargs_forward_shell")) return rc;
     FrameMode mode;
-    mode.is_shell = true;
-    return forward_impl(geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user, P, background, width,
-                        height, means3D, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix,
-                        beam_inclinations, (float)lidar_near, (float)lidar_far, shell_lo, shell_hi, T_in, transmittance_pass,
-                        out_color, out_depth, out_occ, T_out, radii, radii_xy, debug, (hipStream_t)stream, mode);
+    mode.is_shell = true; mode.shell_lo = shell_lo; mode.shell_hi = shell_hi;
+    mode.T_in = T_in; mode.transmittance_pass = transmittance_pass; mode.T_out = T_out;
+    LG_FORWARD_ARGS(alloc, sc, out);
+    return forward_impl(alloc, sc, out, mode, debug, (hipStream_t)stream);
 }
 
 int lidargs_forward_shell_enqueue(lidargs_alloc_fn geometry_alloc, void* geometry_user, lidargs_alloc_fn binning_alloc, void* binning_user,
@@ -1122,16 +1132,14 @@ int lidargs_forward_shell_enqueue(lidargs_alloc_fn geometry_alloc, void* geometr
                                   const float* T_in, int transmittance_pass, float* out_color, float* out_depth, float* out_occ,
                                   float* T_out, int* radii, int* radii_xy, int debug, const unsigned* n_valid, int instance_capacity,
                                   int tile_rows, unsigned* status_host, void* stream) {
-    if (const int rc = lg::refuse_deterministic("lidargs_forward_shell_enqueue")) return rc;
-    if (const int rc = lg::refuse_depth_mode("lidargs_forward_shell_enqueue")) return rc;
+    if (const int rc = lg::refuse_modes("lidargs_forward_shell_enqueue")) return rc;
     if (instance_capacity <= 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward_shell_enqueue: instance_capacity must be positive%s");
     FrameMode mode;
-    mode.is_shell = true; mode.n_valid = n_valid;
+    mode.is_shell = true; mode.shell_lo = shell_lo; mode.shell_hi = shell_hi; mode.n_valid = n_valid;
+    mode.T_in = T_in; mode.transmittance_pass = transmittance_pass; mode.T_out = T_out;
     mode.instance_capacity = instance_capacity; mode.fixed_tile_rows = tile_rows; mode.status_host = status_host;
-    return forward_impl(geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user, P, background, width,
-                        height, means3D, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix,
-                        beam_inclinations, (float)lidar_near, (float)lidar_far, shell_lo, shell_hi, T_in, transmittance_pass,
-                        out_color, out_depth, out_occ, T_out, radii, radii_xy, debug, (hipStream_t)stream, mode);
+    LG_FORWARD_ARGS(alloc, sc, out);
+    return forward_impl(alloc, sc, out, mode, debug, (hipStream_t)stream);
 }
 
 // ---- column wedges (multi-GPU): rank g bins and renders the tile columns of pixel columns [col_lo, col_hi) only --------------------
@@ -1141,19 +1149,15 @@ int lidargs_forward_wedge(lidargs_alloc_fn geometry_alloc, void* geometry_user, 
                           float scale_modifier, const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
                           const float* beam_inclinations, int lidar_far, int lidar_near, int col_lo, int col_hi, float* out_color,
                           float* out_depth, float* out_occ, int* radii, int* radii_xy, int debug, void* stream) {
-    if (const int rc = lg::refuse_deterministic("lidargs_forward_wedge")) return rc;
-    if (const int rc = lg::refuse_depth_mode("lidargs_forward_wedge")) return rc;
+    if (const int rc = lg::refuse_modes("lidargs_forward_wedge")) return rc;
     if (col_lo < 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward_wedge: col_lo < 0%s");
     // lidargs_wedge_select_count bounds a Gaussian's reach from its scales and rotation; a precomputed covariance has no such bound
     // there, and a wedge rendered from an under-selected set would silently miss its boundary Gaussians
     if (cov3D_precomp) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward_wedge: cov3D_precomp is not supported on the column-wedge path (give scales + rotations)%s");
-    const float inf = std::numeric_limits<float>::infinity();
     FrameMode mode;
     mode.col_lo = col_lo; mode.col_hi = col_hi;
-    return forward_impl(geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user, P, background, width,
-                        height, means3D, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix,
-                        beam_inclinations, (float)lidar_near, (float)lidar_far, -inf, inf, nullptr, 0, out_color, out_depth, out_occ,
-                        nullptr, radii, radii_xy, debug, (hipStream_t)stream, mode);
+    LG_FORWARD_ARGS(alloc, sc, out);
+    return forward_impl(alloc, sc, out, mode, debug, (hipStream_t)stream);
 }
 
 int lidargs_forward_wedge_enqueue(lidargs_alloc_fn geometry_alloc, void* geometry_user, lidargs_alloc_fn binning_alloc, void* binning_user,
@@ -1163,19 +1167,15 @@ int lidargs_forward_wedge_enqueue(lidargs_alloc_fn geometry_alloc, void* geometr
                                   const float* beam_inclinations, int lidar_far, int lidar_near, int col_lo, int col_hi, float* out_color,
                                   float* out_depth, float* out_occ, int* radii, int* radii_xy, int debug, const unsigned* n_valid,
                                   int instance_capacity, int tile_rows, unsigned* status_host, void* stream) {
-    if (const int rc = lg::refuse_deterministic("lidargs_forward_wedge_enqueue")) return rc;
-    if (const int rc = lg::refuse_depth_mode("lidargs_forward_wedge_enqueue")) return rc;
+    if (const int rc = lg::refuse_modes("lidargs_forward_wedge_enqueue")) return rc;
     if (col_lo < 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward_wedge: col_lo < 0%s");
     if (cov3D_precomp) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward_wedge: cov3D_precomp is not supported on the column-wedge path (give scales + rotations)%s");
     if (instance_capacity <= 0) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "forward_wedge_enqueue: instance_capacity must be positive%s");
-    const float inf = std::numeric_limits<float>::infinity();
     FrameMode mode;
     mode.col_lo = col_lo; mode.col_hi = col_hi; mode.n_valid = n_valid;
     mode.instance_capacity = instance_capacity; mode.fixed_tile_rows = tile_rows; mode.status_host = status_host;
-    return forward_impl(geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user, P, background, width,
-                        height, means3D, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix,
-                        beam_inclinations, (float)lidar_near, (float)lidar_far, -inf, inf, nullptr, 0, out_color, out_depth, out_occ,
-                        nullptr, radii, radii_xy, debug, (hipStream_t)stream, mode);
+    LG_FORWARD_ARGS(alloc, sc, out);
+    return forward_impl(alloc, sc, out, mode, debug, (hipStream_t)stream);
 }
 
 int lidargs_backward_wedge(int P, int R, const float* background, int width, int height, const float* means3D, const float* colors_precomp,
@@ -1188,10 +1188,8 @@ int lidargs_backward_wedge(int P, int R, const float* background, int width, int
     if (cov3D_precomp) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "backward_wedge: cov3D_precomp is not supported on the column-wedge path (give scales + rotations)%s");
     BackMode mode;
     mode.col_lo = col_lo; mode.col_hi = col_hi;
-    return backward_impl(P, R, background, width, height, means3D, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix,
-                         beam_inclinations, radii, geom_buffer, binning_buffer, image_buffer, mode, dL_dpix, dL_dout_depth,
-                         dL_dout_occ, dL_dmean2D, nullptr, dL_dopacity, dL_dcolor, nullptr, dL_dmean3D, nullptr, nullptr, nullptr, dL_dcov3D,
-                         dL_dscale, dL_drot, debug, (hipStream_t)stream);
+    LG_BACKWARD_ARGS(sc, saved, grads);          // (no scratch rows on this entry point)
+    return backward_impl(sc, saved, grads, mode, debug, (hipStream_t)stream);
 }
 
 int lidargs_render_shell(int P, int R, const float* background, int width, int height, char* geom_buffer, char* binning_buffer,
@@ -1203,19 +1201,13 @@ int lidargs_render_shell(int P, int R, const float* background, int width, int h
     const lg::FrameLayout L = lg::frame_layout(R, width, height, -1, -1, lg::FRAME_SHELL);
     lg::BinView bin; L.bin_carve(binning_buffer, &bin);
     lg::ImgView img; lg::img_carve(image_buffer, width, height, lg::make_grid(width, height, 4).num_tiles(), &img);
-    lg::RenderFwdArgs ra;
+    FrameOutputs out; out.out_color = out_color; out.out_depth = out_depth; out.out_occ = out_occ;
+    lg::RenderFwdArgs ra = render_fwd_args(L, geom, bin, img, background, out);   // (touched: a repeated T-only pass sets the same marks again)
     ra.fill.cnt = nullptr;                       // a shell's backward keeps the slot grid
-    ra.grid = L.grid; ra.ranges = img.ranges; ra.point_list = bin.val_a; ra.rec = geom.rec; ra.rowspan = geom.rowspan;
-    ra.coltab = img.coltab; ra.rowtab = img.rowtab; ra.bg = background; ra.T_in = T_in;
-    ra.final_T = img.final_T; ra.T_pass = T_out;
-    ra.out_color = out_color; ra.out_depth = out_depth; ra.out_occ = out_occ;
-    ra.seg = bin.seg; ra.S = L.S; ra.seg_len = L.plan.seg_len;
-    ra.seg_lo = 0; ra.seg_hi = L.S; ra.front = 0;
+    ra.T_in = T_in; ra.T_pass = T_out; ra.transmittance_only = transmittance_pass;
     ra.alive = L.gated ? bin.alive : nullptr;    // written, like the flags, by the shell's phase 1
-    ra.flags = bin.flags; ra.R = L.Rp;           // written by the shell's phase 1 (lidargs_forward_shell)
-    ra.touched = geom.touched;                   // (a repeated T-only pass sets the same marks again)
+    ra.flags = bin.flags;                        // written by the shell's phase 1 (lidargs_forward_shell)
     ra.run_pass1 = transmittance_pass ? 1 : 0;   // phase 2 reuses the Tpass planes the shell's phase 1 left behind
-    ra.transmittance_only = transmittance_pass;
     ra.T_end_out = transmittance_pass ? nullptr : T_end_out;          // the combine writes it beside final_T
     if (!transmittance_pass && (!out_color || !out_depth || !out_occ)) return fail(LIDARGS_ERR_INVALID_ARGUMENT, "render_shell: NULL output%s");
     if (ra.run_pass1) run_pass1_rounds(ra, L.plan, bin.alive, stream);
@@ -1235,10 +1227,8 @@ int lidargs_backward_shell(int P, int R, const float* background, int width, int
                            float* dL_dcov3D, float* dL_dscale, float* dL_drot, int debug, void* stream) {
     BackMode mode;
     mode.is_shell = true; mode.behind = behind; mode.T_final_global = T_final_global;
-    return backward_impl(P, R, background, width, height, means3D, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
-                         viewmatrix, beam_inclinations, radii, geom_buffer, binning_buffer, image_buffer, mode,
-                         dL_dpix, dL_dout_depth, dL_dout_occ, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_ddepths, dL_dmean3D,
-                         dL_dsphere_means3D, dL_dbasis_u1, dL_dbasis_u2, dL_dcov3D, dL_dscale, dL_drot, debug, (hipStream_t)stream);
+    LG_BACKWARD_ARGS(sc, saved, grads); LG_SCRATCH_ROWS(grads.rows);
+    return backward_impl(sc, saved, grads, mode, debug, (hipStream_t)stream);
 }
 
 void lidargs_profile_enable(int on) {

@@ -344,6 +344,10 @@ int api_fail(int code, const char* msg);
 int api_check_launch(hipStream_t s, int debug, const char* what);
 int refuse_deterministic(const char* entry);    // 0, or LIDARGS_ERR_INVALID_ARGUMENT (message set) when the switch is on: entry points the mode does not cover
 int refuse_depth_mode(const char* entry);       // the same for a non-default depth mode (LIDARGS_DEPTH=median, strongest)
+inline int refuse_modes(const char* entry) {    // both, in this order: what every entry point but lidargs_forward starts with
+    if (const int rc = refuse_deterministic(entry)) return rc;
+    return refuse_depth_mode(entry);
+}
 // Device -> host read of `n` (<= 1024) words with `zero_bytes` at `zero` cleared BEHIND the copy on the same stream: the host waits
 // for the copy only.  Returns a hipError_t.
 int api_read_words_zero_behind(const uint32_t* dev, int n, uint32_t* out, void* zero, size_t zero_bytes, hipStream_t s);

@@ -18,15 +18,37 @@ static size_t sf_img_carve(char* base, int W, int H, int tiles, SfImgView* v) {
     return (size_t)(c.p - base) + 128;
 }
 
+// The surfels and the sensor as the preprocess and the per-surfel backward chain read them, and the backward's nine gradient rows: the
+// entry points fill both BY FIELD NAME (as api.hip's SceneArgs / GradRows), so no helper below hangs on an argument's position.
+namespace {
+struct SfScene { int P = 0; const float* viewmatrix = nullptr; const float* means3D = nullptr; const float* scales = nullptr; const float* rotations = nullptr; const float* transMat_precomp = nullptr; const float* beams = nullptr; };
+struct SfGradRows {   // dL_dnormal, dL_dtransMat, dL_dtransMat_2dtemp: optional
+    float* dL_dmean2D = nullptr; float* dL_dnormal = nullptr; float* dL_dopacity = nullptr; float* dL_dcolor = nullptr; float* dL_dmean3D = nullptr;
+    float* dL_dtransMat = nullptr; float* dL_dtransMat_2dtemp = nullptr; float* dL_dscale = nullptr; float* dL_drot = nullptr;
+    bool required() const { return dL_dmean2D && dL_dopacity && dL_dcolor && dL_dmean3D && dL_dscale && dL_drot; }
+    ZeroRows zero_rows() const {   // the rows the backward's first launch zeroes, with their widths (depth is written for every surfel by k_sf_gaussian_backward)
+        ZeroRows zr; zr.add(dL_dmean2D, 4); zr.add(dL_dnormal, 3); zr.add(dL_dopacity, 1); zr.add(dL_dcolor, 2); zr.add(dL_dmean3D, 3); zr.add(dL_dtransMat, 9);
+        zr.add(dL_dtransMat_2dtemp, 3); zr.add(dL_dscale, 2); zr.add(dL_drot, 4);
+        return zr;
+    }
+};
+}  // namespace
+// the per-surfel chain's arguments; W, H, radii and depth (an output, not a gradient) are each caller's own
+static SfGaussBwdArgs sf_gauss_bwd_args(const SfScene& sc, const SfGradRows& g, const float* gacc, const uint8_t* tlist, const uint16_t* tcount) {
+    SfGaussBwdArgs ga;
+    ga.P = sc.P; ga.view = sc.viewmatrix; ga.means3D = sc.means3D; ga.scales = sc.scales; ga.rotations = sc.rotations; ga.beams = sc.beams; ga.transMat = sc.transMat_precomp;
+    ga.gacc = gacc; ga.tlist = tlist; ga.tcount = tcount; ga.dL_dmean2D = g.dL_dmean2D; ga.dL_dnormal = g.dL_dnormal; ga.dL_dopacity = g.dL_dopacity; ga.dL_dcolor = g.dL_dcolor;
+    ga.dL_dmean3D = g.dL_dmean3D; ga.dL_dtransMat = g.dL_dtransMat; ga.dL_dtransMat_2dtemp = g.dL_dtransMat_2dtemp; ga.dL_dscale = g.dL_dscale; ga.dL_drot = g.dL_drot;
+    return ga;
+}
 // The surfel preprocess' parameters of a whole width x height frame at tile height TH: everything but the arrays it writes.  The forward,
 // the visible filter and the test hook (lidargs_debug_surfel_preprocess) all start from here, so the column step is the same value for each.
-static SfPreArgs sf_pre_params(int P, const TileGrid& grid, float scale_modifier, float near_f, float far_f, const float* viewmatrix,
-                               const float* means3D, const float* scales, const float* rotations, const float* beams, int* radii, int* radii_xy) {
+static SfPreArgs sf_pre_params(const SfScene& sc, const TileGrid& grid, float scale_modifier, float near_f, float far_f, int* radii, int* radii_xy) {
     SfPreArgs pa = SfPreArgs();
-    pa.P = P; pa.W = grid.W; pa.H = grid.H; pa.TH = grid.TH; pa.tiles_x = grid.tiles_x;
+    pa.P = sc.P; pa.W = grid.W; pa.H = grid.H; pa.TH = grid.TH; pa.tiles_x = grid.tiles_x;
     pa.scale_modifier = scale_modifier; pa.near_f = near_f; pa.far_f = far_f;
     pa.col_step = 2 * 3.14159265358979323846f / (float)grid.W;
-    pa.view = viewmatrix; pa.means3D = means3D; pa.scales = scales; pa.rotations = rotations; pa.beams = beams;
+    pa.view = sc.viewmatrix; pa.means3D = sc.means3D; pa.scales = sc.scales; pa.rotations = sc.rotations; pa.beams = sc.beams;
     pa.radii = radii; pa.radii_xy = radii_xy;
     return pa;
 }
@@ -40,17 +62,14 @@ static void sf_pre_outputs(SfPreArgs& pa, const float* opacities, const float* c
     pa.compact = compact; pa.touched = geom.touched; pa.prune = prune;
 }
 
-// The rows the backward's first launch zeroes, with their widths (depth is written for every surfel by k_sf_gaussian_backward)
-static ZeroRows sf_zero_rows(float* dL_dmean2D, float* dL_dnormal, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dtransMat,
-                             float* dL_dtransMat_2dtemp, float* dL_dscale, float* dL_drot) {
-    ZeroRows zr;
-    zr.add(dL_dmean2D, 4); zr.add(dL_dnormal, 3); zr.add(dL_dopacity, 1); zr.add(dL_dcolor, 2); zr.add(dL_dmean3D, 3); zr.add(dL_dtransMat, 9);
-    zr.add(dL_dtransMat_2dtemp, 3); zr.add(dL_dscale, 2); zr.add(dL_drot, 4);
-    return zr;
-}
-
 }  // namespace lg
 
+// The C parameter names the surfel entry points share onto the two structs, each stated once (bound by name, as api.hip's LG_*_ARGS).
+#define SF_SCENE(sc, beams_)                                                                                                                                                                \
+    lg::SfScene sc; sc.P = P; sc.viewmatrix = viewmatrix; sc.means3D = means3D; sc.scales = scales; sc.rotations = rotations; sc.transMat_precomp = transMat_precomp; sc.beams = beams_
+#define SF_GRAD_ROWS(rows)                                                                                                                                                                  \
+    lg::SfGradRows rows; rows.dL_dmean2D = dL_dmean2D; rows.dL_dnormal = dL_dnormal; rows.dL_dopacity = dL_dopacity; rows.dL_dcolor = dL_dcolor; rows.dL_dmean3D = dL_dmean3D;              \
+    rows.dL_dtransMat = dL_dtransMat; rows.dL_dtransMat_2dtemp = dL_dtransMat_2dtemp; rows.dL_dscale = dL_dscale; rows.dL_drot = dL_drot
 #define SF_CHECK(what) do { int rc_ = lg::api_check_launch(stream, debug, what); if (rc_) return rc_; } while (0)
 #define SF_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return lg::api_fail(LIDARGS_ERR_HIP, hipGetErrorString(e_)); } while (0)
 
@@ -65,8 +84,8 @@ int lidargs_surfel_forward(lidargs_alloc_fn geometry_alloc, void* geometry_user,
                            int* radii_xy, int debug, void* stream_) {
     (void)D; (void)M; (void)shs; (void)projmatrix; (void)cam_pos; (void)prefiltered; (void)pixels;   // `pixels` is never written by the reference either (R2/cr/forward.cu:522)
     hipStream_t stream = (hipStream_t)stream_;
-    if (const int rc = lg::refuse_deterministic("lidargs_surfel_forward")) return rc;   // (the surfel backward still adds with float atomics)
-    if (const int rc = lg::refuse_depth_mode("lidargs_surfel_forward")) return rc;    // (the surfel variant returns its own median plane, others[5])
+    // (the surfel backward still adds with float atomics; the surfel variant returns its own median plane, others[5])
+    if (const int rc = lg::refuse_modes("lidargs_surfel_forward")) return rc;
     if (P < 0 || width <= 0 || height < 2 || height > 65535) return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "surfel forward: bad sizes");
     if (colors_precomp == nullptr) return lg::api_fail(LIDARGS_ERR_NO_COLORS, "For non-RGB, provide precomputed Gaussian colors!");
     // transMat_precomp, as the reference treats it: its preprocess builds T from scales and rotations unconditionally (rect, normal,
@@ -90,8 +109,8 @@ int lidargs_surfel_forward(lidargs_alloc_fn geometry_alloc, void* geometry_user,
     lg::prof_begin(stream, 0);
     lg::ImgView tabs = lg::ImgView(); tabs.coltab = img.coltab; tabs.rowtab = img.rowtab;
     lg::launch_setup_tables(beam_inclinations, width, height, tabs, stream);
-    lg::SfPreArgs pa = lg::sf_pre_params(P, grid, scale_modifier, (float)lidar_near, (float)lidar_far, viewmatrix, means3D, scales, rotations,
-                                         beam_inclinations, radii, radii_xy);
+    SF_SCENE(sc, beam_inclinations);
+    lg::SfPreArgs pa = lg::sf_pre_params(sc, grid, scale_modifier, (float)lidar_near, (float)lidar_far, radii, radii_xy);
     lg::sf_pre_outputs(pa, opacities, colors_precomp, transMat_precomp, geom, lg::compact_spans(grid.tiles_x, height) ? 1 : 0,
                        lg::prune_footprints() ? 1 : 0);
     SF_HIP(hipMemsetAsync(geom.totals, 0, LG_TOTALS_WORDS * sizeof(uint32_t), stream));
@@ -157,16 +176,15 @@ int lidargs_surfel_backward(int P, int D, int M, int R, const float* background,
     // the chain to scales / rotations / means3D runs as always (R2/cr/backward.cu:730: Ts_precomp is only set when scales is NULL, and
     // that case -- "Ts_precomp error, to check!!", :661-664 -- cannot get past the forward); dL_dtransMat is what the caller returns for it
     if (!geom_buffer || !binning_buffer || !image_buffer) return lg::api_fail(LIDARGS_ERR_STATE, "surfel backward: missing forward buffers");
-    if (!means3D || !scales || !rotations || !viewmatrix || !beam_inclinations || !background || !radii || !dL_dpix || !dL_depths || !dL_dmean2D ||
-        !dL_dopacity || !dL_dcolor || !dL_dmean3D || !dL_dscale || !dL_drot || !depth)   // dL_dnormal, dL_dtransMat, dL_dtransMat_2dtemp: optional
+    SF_SCENE(sc, beam_inclinations); SF_GRAD_ROWS(rows);
+    if (!means3D || !scales || !rotations || !viewmatrix || !beam_inclinations || !background || !radii || !dL_dpix || !dL_depths || !rows.required() || !depth)
         return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "surfel backward: NULL required pointer");
     const lg::FrameLayout L = lg::frame_layout(R, width, height, -1, -1, lg::FRAME_SURFEL);
     lg::GeomView geom; lg::geom_carve(geom_buffer, (size_t)P, lg::SURFEL_BUFFERS, &geom);
     lg::BinView bin; L.bin_carve(binning_buffer, &bin);
     lg::SfImgView img; lg::sf_img_carve(image_buffer, width, height, L.grid.num_tiles(), &img);
     lg::prof_begin(stream, 1);
-    const lg::ZeroRows zr = lg::sf_zero_rows(dL_dmean2D, dL_dnormal, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dtransMat, dL_dtransMat_2dtemp, dL_dscale, dL_drot);
-    lg::launch_zero_touched(geom.touched, reinterpret_cast<float4*>(geom.gacc), 8, (size_t)P, geom.tlist, geom.tcount, zr, stream);   // the touched surfels' lines + lists, every backward
+    lg::launch_zero_touched(geom.touched, reinterpret_cast<float4*>(geom.gacc), 8, (size_t)P, geom.tlist, geom.tcount, rows.zero_rows(), stream);   // the touched surfels' lines + lists, every backward
     lg::prof_mark("bwd_zero", stream);
     lg::SfBwdArgs ba;
     ba.grid = L.grid; ba.ranges = img.ranges; ba.point_list = bin.val_a; ba.rec = geom.rec; ba.rowspan = geom.rowspan;
@@ -177,11 +195,7 @@ int lidargs_surfel_backward(int P, int D, int M, int R, const float* background,
     lg::launch_sf_render_backward(ba, stream);
     SF_CHECK("surfel render backward");
     lg::prof_mark("render_bwd", stream);
-    lg::SfGaussBwdArgs ga;
-    ga.P = P; ga.W = width; ga.H = height; ga.view = viewmatrix; ga.means3D = means3D; ga.scales = scales; ga.rotations = rotations;
-    ga.beams = beam_inclinations; ga.radii = radii; ga.transMat = transMat_precomp; ga.gacc = geom.gacc; ga.tlist = geom.tlist; ga.tcount = geom.tcount;
-    ga.dL_dmean2D = dL_dmean2D; ga.dL_dnormal = dL_dnormal; ga.dL_dopacity = dL_dopacity; ga.dL_dcolor = dL_dcolor; ga.dL_dmean3D = dL_dmean3D;
-    ga.dL_dtransMat = dL_dtransMat; ga.dL_dtransMat_2dtemp = dL_dtransMat_2dtemp; ga.dL_dscale = dL_dscale; ga.dL_drot = dL_drot; ga.depth = depth;
+    lg::SfGaussBwdArgs ga = lg::sf_gauss_bwd_args(sc, rows, geom.gacc, geom.tlist, geom.tcount); ga.W = width; ga.H = height; ga.radii = radii; ga.depth = depth;
     lg::launch_sf_gaussian_backward(ga, stream);
     SF_CHECK("surfel gaussian backward");
     lg::prof_mark("gaussian_bwd", stream);
@@ -194,15 +208,15 @@ int lidargs_surfel_visible_filter(lidargs_alloc_fn geometry_alloc, void* geometr
                                   const float* viewmatrix, const float* projmatrix, const float* beam_inclinations, int prefiltered,
                                   int lidar_far, int lidar_near, int* radii, int* radii_xy, int debug, void* stream_) {
     (void)geometry_alloc; (void)geometry_user; (void)binning_alloc; (void)binning_user; (void)image_alloc; (void)image_user;
-    (void)M; (void)projmatrix; (void)prefiltered; (void)transMat_precomp;
+    (void)M; (void)projmatrix; (void)prefiltered;   // (transMat_precomp: the filter's preprocess does not read it)
     hipStream_t stream = (hipStream_t)stream_;
     if (P < 0 || width <= 0 || height < 2) return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "surfel visible_filter: bad sizes");
     if (P == 0) return 0;
     if (!means3D || !scales || !rotations || !viewmatrix || !beam_inclinations || !radii || !radii_xy)
         return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "surfel visible_filter: NULL required pointer");
     const lg::TileGrid grid = lg::make_grid(width, height, lg::tile_rows());
-    const lg::SfPreArgs pa = lg::sf_pre_params(P, grid, scale_modifier, (float)lidar_near, (float)lidar_far, viewmatrix, means3D, scales, rotations,
-                                               beam_inclinations, radii, radii_xy);
+    SF_SCENE(sc, beam_inclinations);
+    const lg::SfPreArgs pa = lg::sf_pre_params(sc, grid, scale_modifier, (float)lidar_near, (float)lidar_far, radii, radii_xy);
     lg::launch_sf_preprocess(pa, true, stream);
     SF_CHECK("surfel filter preprocess");
     return 0;
@@ -229,7 +243,8 @@ int lidargs_debug_surfel_preprocess(int P, int width, int height, const float* m
     if (!filter_only && (!colors || !opacities || !rec || !rowspan || !spans || !key || !touched || !totals))
         return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_surfel_preprocess: NULL required pointer");
     if (P == 0) return 0;
-    lg::SfPreArgs pa = lg::sf_pre_params(P, grid, scale_modifier, near_f, far_f, viewmatrix, means3D, scales, rotations, beams, radii, radii_xy);
+    SF_SCENE(sc, beams);
+    lg::SfPreArgs pa = lg::sf_pre_params(sc, grid, scale_modifier, near_f, far_f, radii, radii_xy);
     if (!filter_only) {
         lg::GeomView geom; memset(&geom, 0, sizeof geom);
         geom.rec = reinterpret_cast<float4*>(rec); geom.rowspan = rowspan; geom.spans = reinterpret_cast<uint4*>(spans); geom.key_a = key;
@@ -253,22 +268,17 @@ int lidargs_debug_surfel_gaussian_backward(int P, int width, int height, int sta
     if (stage < 0 || stage > 2) return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_surfel_gaussian_backward: stage must be 0, 1 or 2");
     if (!touched || !gacc || !tlist || !tcount) return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_surfel_gaussian_backward: NULL required pointer");
     const bool chain = stage != 1;
+    SF_SCENE(sc, beams); SF_GRAD_ROWS(rows);
     // the chain's rows, as lidargs_surfel_backward requires them (dL_dnormal, dL_dtransMat, dL_dtransMat_2dtemp stay optional)
-    if (chain && (!means3D || !scales || !rotations || !viewmatrix || !beams || !radii || !dL_dmean2D || !dL_dopacity || !dL_dcolor || !dL_dmean3D ||
-                  !dL_dscale || !dL_drot || !depth))
+    if (chain && (!means3D || !scales || !rotations || !viewmatrix || !beams || !radii || !rows.required() || !depth))
         return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_surfel_gaussian_backward: NULL required pointer");
     if (P == 0) return 0;
     if (stage != 2) {
-        const lg::ZeroRows zr = lg::sf_zero_rows(dL_dmean2D, dL_dnormal, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dtransMat, dL_dtransMat_2dtemp, dL_dscale, dL_drot);
-        lg::launch_zero_touched(touched, reinterpret_cast<float4*>(gacc), 8, (size_t)P, tlist, tcount, zr, stream);
+        lg::launch_zero_touched(touched, reinterpret_cast<float4*>(gacc), 8, (size_t)P, tlist, tcount, rows.zero_rows(), stream);
         SF_CHECK("debug surfel zero touched");
     }
     if (!chain) return 0;
-    lg::SfGaussBwdArgs ga;
-    ga.P = P; ga.W = width; ga.H = height; ga.view = viewmatrix; ga.means3D = means3D; ga.scales = scales; ga.rotations = rotations;
-    ga.beams = beams; ga.radii = radii; ga.transMat = transMat_precomp; ga.gacc = gacc; ga.tlist = tlist; ga.tcount = tcount;
-    ga.dL_dmean2D = dL_dmean2D; ga.dL_dnormal = dL_dnormal; ga.dL_dopacity = dL_dopacity; ga.dL_dcolor = dL_dcolor; ga.dL_dmean3D = dL_dmean3D;
-    ga.dL_dtransMat = dL_dtransMat; ga.dL_dtransMat_2dtemp = dL_dtransMat_2dtemp; ga.dL_dscale = dL_dscale; ga.dL_drot = dL_drot; ga.depth = depth;
+    lg::SfGaussBwdArgs ga = lg::sf_gauss_bwd_args(sc, rows, gacc, tlist, tcount); ga.W = width; ga.H = height; ga.radii = radii; ga.depth = depth;
     lg::launch_sf_gaussian_backward(ga, stream);
     SF_CHECK("debug surfel gaussian backward");
     return 0;
