@@ -30,7 +30,7 @@ extern "C" {
  * median and strongest buffers of lidargs_forward / lidargs_forward_enqueue; no host read, no allocation, graph-capturable.
  *   Refused (LIDARGS_ERR_INVALID_ARGUMENT, before any launch): what lidargs_backward refuses; dL_dviewmatrix NULL; for P > 0 a NULL or
  *   misaligned view_partials or view_partial_floats < lgpose_view_partial_floats(P).  P = 0: returns 0, sixteen zeros are written.
- * Shell, wedge and surfel buffers have no such entry point: no gradient reaches their view matrix. */
+ * Shell and wedge buffers have no such entry point: no gradient reaches their view matrix.  Surfel buffers: include_surfel_pose/lidargs_surfel_pose.h. */
 size_t lgpose_view_partial_floats(int P);
 int lgpose_backward_view(
     int P, int D, int M, int R,

@@ -31,6 +31,10 @@ OUT = os.path.join(HERE, "diff_lidargs_rasterization", "liblidargs_hip.so")
 # include/ and the library's lidargs_* exports stay the drop-in boundary for the reference's interfaces.
 POSE_INCLUDE = os.path.join(ROOT, "include_pose")
 POSE_PREFIX = "lgpose_"
+# ... and the third: the surfel rasterizer's pose-gradient entry points (lgsfpose_*, include_surfel_pose/lidargs_surfel_pose.h), which run
+# lidargs_surfel_backward's host sequence.  A directory and prefix of their own, so that include_pose/ stays the 3-D form's three functions.
+SURFEL_POSE_INCLUDE = os.path.join(ROOT, "include_surfel_pose")
+SURFEL_POSE_PREFIX = "lgsfpose_"
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-fno-gpu-rdc", "-Wall",
           "-Wno-unused-function", "-Wno-unused-value"]
 SOURCES = {
@@ -85,9 +89,9 @@ def _listed(d, keep=lambda f: True):
 def deps(target):
     """What a library is rebuilt for: its own sources, every shared file of csrc/ that is not a .hip (headers and .inc, whichever
     target includes them: more than needed, never less), every header of its include directory and this file; the main library also
-    for the header of its pose entry points (POSE_INCLUDE)."""
+    for the headers of its pose entry points (POSE_INCLUDE, SURFEL_POSE_INCLUDE)."""
     return ([os.path.join(CSRC, f) for f in target.sources] + _listed(CSRC, lambda f: not f.endswith(".hip"))
-            + _listed(target.include) + (_listed(POSE_INCLUDE) if target.name == "hip" else []) + [os.path.abspath(__file__)])
+            + _listed(target.include) + (_listed(POSE_INCLUDE) + _listed(SURFEL_POSE_INCLUDE) if target.name == "hip" else []) + [os.path.abspath(__file__)])
 
 
 def stale(target):

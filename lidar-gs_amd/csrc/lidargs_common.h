@@ -606,6 +606,9 @@ void launch_gaussian_backward(const GaussBwdArgs& a, hipStream_t s);
 // a.view_partials, and a one-workgroup launch that folds the rows in double into dL_dviewmatrix[16].  No atomics, no host read.
 void launch_gaussian_backward_view(const GaussBwdArgs& a, float* dL_dviewmatrix, hipStream_t s);
 size_t view_partial_floats(int P);   // floats of view_partials for P Gaussians
+// the fold alone (k_fold_view_partials, one workgroup): `rows` partial rows of 16 floats summed in double into out[16]; the surfel
+// chain's pose form (surfel.hip launch_sf_gaussian_backward_view) writes rows of the same layout and folds them with it
+void launch_fold_view_partials(const float* partials, int rows, float* out, hipStream_t s);
 
 // ---- device-side helpers shared by the blend kernels (render.hip, surfel.hip) ----------------------------------------
 #ifdef __HIPCC__

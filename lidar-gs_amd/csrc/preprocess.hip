@@ -802,7 +802,10 @@ void launch_gaussian_backward(const GaussBwdArgs& a, hipStream_t s) {
 void launch_gaussian_backward_view(const GaussBwdArgs& a, float* dL_dviewmatrix, hipStream_t s) {
     const unsigned regions = (unsigned)((a.P + LG_REGION - 1) / LG_REGION);
     hipLaunchKernelGGL(k_gaussian_backward_view, dim3((regions + 3) / 4), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_fold_view_partials, dim3(1), dim3(16 * LG_VIEW_FOLD_GROUPS), 0, s, a.view_partials, (int)regions, dL_dviewmatrix);
+    launch_fold_view_partials(a.view_partials, (int)regions, dL_dviewmatrix, s);
+}
+void launch_fold_view_partials(const float* partials, int rows, float* out, hipStream_t s) {
+    hipLaunchKernelGGL(k_fold_view_partials, dim3(1), dim3(16 * LG_VIEW_FOLD_GROUPS), 0, s, partials, rows, out);
 }
 size_t view_partial_floats(int P) { return P > 0 ? 16 * (((size_t)P + LG_REGION - 1) / LG_REGION) : 0; }
 

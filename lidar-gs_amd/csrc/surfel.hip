@@ -6,6 +6,7 @@
 //   K7'  renderCUDA (forward)      R2/cr/forward.cu:327-547      -> k_sf_render_forward
 //   K8'  renderCUDA (backward)     R2/cr/backward.cu:143-605     -> k_sf_render_backward
 //   K10' preprocessCUDA (backward) R2/cr/backward.cu:607-749     -> k_sf_gaussian_backward
+//   (no reference counterpart)     the same chain + the gradient with respect to the view matrix -> k_sf_gaussian_backward_view
 // Binning (range sort, load-balanced instance emit, stable tile bin, ranges) is shared with the 3D variant
 // (binning.hip); so are the pixel mapping (one wave64 = 16 columns x 4 rows, per-lane row test against the
 // reference rect, tile width 16 = BLOCK_X) and the ray tables.
@@ -989,31 +990,37 @@ struct SfGaussBwdArgs {
     const float* gacc; const uint8_t* tlist; const uint16_t* tcount;   // packed sums (lines of touched surfels only) | the touched surfels, region by region
     float* dL_dmean2D; float* dL_dnormal; float* dL_dopacity; float* dL_dcolor; float* dL_dmean3D; float* dL_dtransMat;
     float* dL_dtransMat_2dtemp; float* dL_dscale; float* dL_drot; float* depth;
+    float* view_partials = nullptr; float scale_modifier = 1.f;   // the pose form alone (k_sf_gaussian_backward_view): one 64-byte row of dL/dviewmatrix sums per region | the forward's scale_modifier
 };
 
 // Sparse (round 5, as k_gaussian_backward in preprocess.hip): only the surfels the blend marked as touched have a gradient.  The
 // backward's first launch (k_zero_touched) zeroed every gradient row and listed the touched surfels region by region; here a block
 // covers four regions: every thread first writes the planar depth of four surfels (an output, not a gradient: R2/cr/backward.cu:670,
 // 0 for a culled one), then each wave runs the chain on the listed surfels of one region and overwrites their rows.
-__device__ __forceinline__ void sf_gb_row(const SfGaussBwdArgs& a, const int idx);
+// sf_gb_row<POSE> (the pose form, k_sf_gaussian_backward_view below): the row's twelve products of dL/dviewmatrix are added to the lane's
+// running sums ps[16] as well (slot 4r + k = element [r][k] of the matrix; slots 3, 7, 11, 15 stay zero).
+template <bool POSE = false>
+__device__ __forceinline__ void sf_gb_row(const SfGaussBwdArgs& a, const int idx, float* ps = nullptr);
+// the planar depth of the block's 4 * LG_REGION surfels, four per thread
+__device__ __forceinline__ void sf_gb_depth(const SfGaussBwdArgs& a) {
+    const float* vm = a.view;
+    const int b0 = blockIdx.x * 4 * LG_REGION;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int i = b0 + k * 256 + (int)threadIdx.x;
+        if (i >= a.P) break;
+        float dep = 0.f;
+        if (a.radii[i] > 0) {
+            const float3 pw = get3(a.means3D, i);
+            const float px = vm[0] * pw.x + vm[4] * pw.y + vm[8] * pw.z + vm[12], pz = vm[2] * pw.x + vm[6] * pw.y + vm[10] * pw.z + vm[14];
+            dep = sqrtf(px * px + pz * pz);                            // :670 (x, z only, as the reference)
+        }
+        a.depth[i] = dep;
+    }
+}
 __global__ void __launch_bounds__(256) k_sf_gaussian_backward(const SfGaussBwdArgs a) {
     const int lane = threadIdx.x & 63;
-    {
-        const float* vm = a.view;
-        const int b0 = blockIdx.x * 4 * LG_REGION;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int i = b0 + k * 256 + (int)threadIdx.x;
-            if (i >= a.P) break;
-            float dep = 0.f;
-            if (a.radii[i] > 0) {
-                const float3 pw = get3(a.means3D, i);
-                const float px = vm[0] * pw.x + vm[4] * pw.y + vm[8] * pw.z + vm[12], pz = vm[2] * pw.x + vm[6] * pw.y + vm[10] * pw.z + vm[14];
-                dep = sqrtf(px * px + pz * pz);                        // :670 (x, z only, as the reference)
-            }
-            a.depth[i] = dep;
-        }
-    }
+    sf_gb_depth(a);
     const int region = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int base = region * LG_REGION;
     if (base >= a.P) return;
@@ -1026,7 +1033,52 @@ __global__ void __launch_bounds__(256) k_sf_gaussian_backward(const SfGaussBwdAr
     }
 }
 
-__device__ __forceinline__ void sf_gb_row(const SfGaussBwdArgs& a, const int idx) {
+// The pose form of the launch above (lgsfpose_backward_view): the same depth plane, the same chain on the same lists, and
+// the gradient with respect to the view matrix on top, in the layout of preprocess.hip's k_gaussian_backward_view.  A lane adds the
+// twelve products of its rows (at most LG_REGION / 64 = 4 of them, in list order) to running sums; the wave folds the sums over its 64
+// lanes in a fixed order -- two gfx950 lane swaps, then DPP row rotations and quad permutes -- and writes them as the region's 64-byte
+// partial row: view_partials[16 region + 4r + k], zeros in column 3.  Every region of the launch writes its row (zeros where nothing
+// was touched), so the buffer need not be cleared.  No atomics, no LDS: given the same packed lines the rows are the same bits whatever
+// the order the waves run in.  k_fold_view_partials (preprocess.hip) sums the rows.
+__global__ void __launch_bounds__(256) k_sf_gaussian_backward_view(const SfGaussBwdArgs a) {
+    const int lane = threadIdx.x & 63;
+    sf_gb_depth(a);
+    const int region = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int base = region * LG_REGION;
+    if (base >= a.P) return;
+    int off = (int)a.tlist[base + lane];
+    int cnt = (int)a.tcount[region];
+    asm volatile("" : "+v"(off), "+v"(cnt));
+    float ps[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) ps[k] = 0.f;
+    for (int j = lane; j < cnt; j += 64) {
+        sf_gb_row<true>(a, base + off, ps);
+        if (j + 64 < cnt) off = (int)a.tlist[base + j + 64];
+    }
+    // (every lane of the wave is here again: the loop's trip count differs between lanes, the reduction below is wave-wide)
+    // halves of 32, then of 16: lane L is left with slots 4 (L >> 4) .. 4 (L >> 4) + 3 in ps[0..3], i.e. row L >> 4 of the matrix
+#pragma unroll
+    for (int k = 0; k < 8; k++) ps[k] = fold_halves32(ps[k], ps[k + 8]);
+#pragma unroll
+    for (int k = 0; k < 4; k++) ps[k] = fold_halves16(ps[k], ps[k + 4]);
+    // the sixteen lanes of a row hold partial sums of the same four slots: rotations by 8 and 4, then the quad's lanes 2 and 1 apart
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        float x = ps[k];
+        x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x128, 0xF, 0xF, true));   // row_ror:8
+        x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x124, 0xF, 0xF, true));   // row_ror:4
+        x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
+        x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
+        ps[k] = x;
+    }
+    // lanes 0, 16, 32, 48 store the four 16-byte quarters of the region's line with one instruction
+    if ((lane & 15) == 0)
+        reinterpret_cast<float4*>(a.view_partials)[4 * (size_t)region + (lane >> 4)] = make_float4(ps[0], ps[1], ps[2], ps[3]);
+}
+
+template <bool POSE>
+__device__ __forceinline__ void sf_gb_row(const SfGaussBwdArgs& a, const int idx, float* ps) {
     const float* vm = a.view;
     // the surfel's 128-byte line as eight 16-byte loads issued together (the slots are read all over the function: left to the
     // compiler they became a dozen 4-/8-/12-byte loads, each a pass over 64 different lines for the wave)
@@ -1094,6 +1146,23 @@ __device__ __forceinline__ void sf_gb_row(const SfGaussBwdArgs& a, const int idx
     const float s0 = a.scales[2 * idx], s1 = a.scales[2 * idx + 1];   // the backward ignores scale_modifier (:632)
     put2(a.dL_dscale, idx, sdot(dL0, c0), sdot(dL1, c1));
     put3(a.dL_dmean3D, idx, dLp.x, dLp.y, dLp.z);
+    if constexpr (POSE) {
+        // The matrix enters the preprocess in four rows: Tu[k] = sum_r vm[4r+k] m s0 c0[r], Tv likewise, Tw[k] = sum_r vm[4r+k] pw[r] +
+        // vm[12+k], n[k] = sg sum_r vm[4r+k] c2[r] (sg: the flip above).  So this row's share of dL/dvm[4r+k] is pw[r] gTw[k] +
+        // m s0 c0[r] gTu[k] + m s1 c1[r] gTv[k] + sg c2[r] gn[k], and of dL/dvm[12+k] it is gTw[k].  scale_modifier is in: this is the
+        // VJP of the forward's rows, with no reference counterpart to follow (the chain above drops it, as the reference does).
+        const float sg = cs > 0.f ? 1.f : -1.f;
+        const float m0 = a.scale_modifier * s0, m1 = a.scale_modifier * s1;
+        const float pr[3] = {pw.x, pw.y, pw.z}, a0[3] = {m0 * c0.x, m0 * c0.y, m0 * c0.z}, a1[3] = {m1 * c1.x, m1 * c1.y, m1 * c1.z};
+        const float a2[3] = {sg * c2.x, sg * c2.y, sg * c2.z};
+        const float wk[3] = {gTw.x, gTw.y, gTw.z}, uk[3] = {gTu.x, gTu.y, gTu.z}, vk[3] = {gTv.x, gTv.y, gTv.z}, nk[3] = {gn.x, gn.y, gn.z};
+#pragma unroll
+        for (int r = 0; r < 3; r++)
+#pragma unroll
+            for (int k = 0; k < 3; k++) ps[4 * r + k] += pr[r] * wk[k] + a0[r] * uk[k] + a1[r] * vk[k] + a2[r] * nk[k];
+#pragma unroll
+        for (int k = 0; k < 3; k++) ps[12 + k] += wk[k];
+    }
     // quat_to_rotmat_vjp with v_R columns (dL0*s0, dL1*s1, dtn)  (R2/cr/auxiliary.h:274-316)
     const float3 v0 = sf3(dL0.x * s0, dL0.y * s0, dL0.z * s0), v1 = sf3(dL1.x * s1, dL1.y * s1, dL1.z * s1), v2 = dtn;
     const float sn = 1.0f / sqrtf(q.w * q.w + q.x * q.x + q.y * q.y + q.z * q.z);
@@ -1109,6 +1178,12 @@ __device__ __forceinline__ void sf_gb_row(const SfGaussBwdArgs& a, const int idx
 void launch_sf_gaussian_backward(const SfGaussBwdArgs& a, hipStream_t s) {
     const unsigned regions = (unsigned)((a.P + LG_REGION - 1) / LG_REGION);
     hipLaunchKernelGGL(k_sf_gaussian_backward, dim3((regions + 3) / 4), dim3(256), 0, s, a);
+}
+// the pose form + the fold: a.view_partials holds 16 floats per region (view_partial_floats), dL_dviewmatrix 16 floats
+void launch_sf_gaussian_backward_view(const SfGaussBwdArgs& a, float* dL_dviewmatrix, hipStream_t s) {
+    const unsigned regions = (unsigned)((a.P + LG_REGION - 1) / LG_REGION);
+    hipLaunchKernelGGL(k_sf_gaussian_backward_view, dim3((regions + 3) / 4), dim3(256), 0, s, a);
+    launch_fold_view_partials(a.view_partials, (int)regions, dL_dviewmatrix, s);
 }
 
 }  // namespace lg

@@ -2,6 +2,7 @@
 // Counterpart of CudaRasterizer::Rasterizer::{forward,backward,visible_filter} of
 // R2/cuda_rasterizer/rasterizer.h:31-114 / rasterizer_impl.cu:200-518.
 #include "../../include/lidargs_rasterizer.h"
+#include "../../include_surfel_pose/lidargs_surfel_pose.h"
 #include <math.h>
 
 namespace lg {
@@ -160,16 +161,14 @@ int lidargs_surfel_forward(lidargs_alloc_fn geometry_alloc, void* geometry_user,
     return rendered;
 }
 
-int lidargs_surfel_backward(int P, int D, int M, int R, const float* background, int width, int height, const float* means3D,
-                            const float* shs, const float* colors_precomp, const float* scales, float scale_modifier,
-                            const float* rotations, const float* transMat_precomp, const float* viewmatrix, const float* projmatrix,
-                            const float* campos, const float* beam_inclinations, const int* radii, char* geom_buffer,
-                            char* binning_buffer, char* image_buffer, const float* dL_dpix, const float* dL_depths, float* dL_dmean2D,
-                            float* dL_dnormal, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dtransMat,
-                            float* dL_dtransMat_2dtemp, float* dL_dsh, float* dL_dscale, float* dL_drot, float* depth, int debug,
-                            void* stream_) {
-    (void)D; (void)M; (void)shs; (void)colors_precomp; (void)scale_modifier; (void)projmatrix; (void)campos; (void)dL_dsh;
-    hipStream_t stream = (hipStream_t)stream_;
+// lidargs_surfel_backward's host sequence.  dL_dviewmatrix (lgsfpose_backward_view, else NULL): the chain's pose form and the fold of its
+// partial rows run in place of the chain (two launches for one), with scale_modifier, which the chain itself does not read.
+static int sf_backward_impl(int P, int R, const float* background, int width, int height, const float* means3D, const float* scales,
+                            float scale_modifier, const float* rotations, const float* transMat_precomp, const float* viewmatrix,
+                            const float* beam_inclinations, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
+                            const float* dL_dpix, const float* dL_depths, float* dL_dmean2D, float* dL_dnormal, float* dL_dopacity,
+                            float* dL_dcolor, float* dL_dmean3D, float* dL_dtransMat, float* dL_dtransMat_2dtemp, float* dL_dscale,
+                            float* dL_drot, float* depth, int debug, hipStream_t stream, float* dL_dviewmatrix, float* view_partials) {
     if (P < 0 || R < 0 || width <= 0 || height < 2) return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "surfel backward: bad sizes");
     if (P == 0) return 0;
     // transMat_precomp with scales and rotations: the blend's backward runs on the precomputed rows (they are in the forward's records),
@@ -196,10 +195,67 @@ int lidargs_surfel_backward(int P, int D, int M, int R, const float* background,
     SF_CHECK("surfel render backward");
     lg::prof_mark("render_bwd", stream);
     lg::SfGaussBwdArgs ga = lg::sf_gauss_bwd_args(sc, rows, geom.gacc, geom.tlist, geom.tcount); ga.W = width; ga.H = height; ga.radii = radii; ga.depth = depth;
-    lg::launch_sf_gaussian_backward(ga, stream);
+    if (dL_dviewmatrix) {
+        ga.view_partials = view_partials; ga.scale_modifier = scale_modifier;
+        lg::launch_sf_gaussian_backward_view(ga, dL_dviewmatrix, stream);
+    } else lg::launch_sf_gaussian_backward(ga, stream);
     SF_CHECK("surfel gaussian backward");
     lg::prof_mark("gaussian_bwd", stream);
     return 0;
+}
+
+int lidargs_surfel_backward(int P, int D, int M, int R, const float* background, int width, int height, const float* means3D,
+                            const float* shs, const float* colors_precomp, const float* scales, float scale_modifier,
+                            const float* rotations, const float* transMat_precomp, const float* viewmatrix, const float* projmatrix,
+                            const float* campos, const float* beam_inclinations, const int* radii, char* geom_buffer,
+                            char* binning_buffer, char* image_buffer, const float* dL_dpix, const float* dL_depths, float* dL_dmean2D,
+                            float* dL_dnormal, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dtransMat,
+                            float* dL_dtransMat_2dtemp, float* dL_dsh, float* dL_dscale, float* dL_drot, float* depth, int debug,
+                            void* stream_) {
+    (void)D; (void)M; (void)shs; (void)colors_precomp; (void)projmatrix; (void)campos; (void)dL_dsh;
+    return sf_backward_impl(P, R, background, width, height, means3D, scales, scale_modifier, rotations, transMat_precomp, viewmatrix,
+                            beam_inclinations, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_depths, dL_dmean2D, dL_dnormal,
+                            dL_dopacity, dL_dcolor, dL_dmean3D, dL_dtransMat, dL_dtransMat_2dtemp, dL_dscale, dL_drot, depth, debug,
+                            (hipStream_t)stream_, nullptr, nullptr);
+}
+
+size_t lgsfpose_view_partial_floats(int P) { return lg::view_partial_floats(P); }
+
+// the pose entry points' own refusals, before lidargs_surfel_backward's: 1 = P == 0 (sixteen zeros queued, return 0), 0 = go on
+static int sf_pose_check(const char* who, int P, bool bad_sizes, const float* transMat_precomp, float* dL_dviewmatrix, float* view_partials,
+                         size_t view_partial_floats, hipStream_t stream) {
+    static thread_local char msg[256];
+    const auto refuse = [&](const char* what) { snprintf(msg, sizeof msg, "%s: %s", who, what); return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, msg); };
+    if (bad_sizes) return refuse("bad sizes");
+    if (!dL_dviewmatrix) return refuse("dL_dviewmatrix is NULL");
+    if (transMat_precomp)
+        return refuse("transMat_precomp together with dL_dviewmatrix (precomputed rows are in view space already: their dependence on the pose is the caller's, through dL_dtransMat)");
+    if (P == 0) {
+        SF_HIP(hipMemsetAsync(dL_dviewmatrix, 0, 16 * sizeof(float), stream));
+        return 1;
+    }
+    if (!view_partials || ((uintptr_t)view_partials & 15u) || view_partial_floats < lg::view_partial_floats(P))
+        return refuse("view_partials is NULL, not 16-byte aligned or shorter than lgsfpose_view_partial_floats(P)");
+    return 0;
+}
+
+int lgsfpose_backward_view(int P, int D, int M, int R, const float* background, int width, int height, const float* means3D,
+                           const float* shs, const float* colors_precomp, const float* scales, float scale_modifier,
+                           const float* rotations, const float* transMat_precomp, const float* viewmatrix, const float* projmatrix,
+                           const float* campos, const float* beam_inclinations, const int* radii, char* geom_buffer,
+                           char* binning_buffer, char* image_buffer, const float* dL_dpix, const float* dL_depths, float* dL_dmean2D,
+                           float* dL_dnormal, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dtransMat,
+                           float* dL_dtransMat_2dtemp, float* dL_dsh, float* dL_dscale, float* dL_drot, float* depth, int debug,
+                           void* stream_, float* dL_dviewmatrix, float* view_partials, size_t view_partial_floats) {
+    (void)D; (void)M; (void)shs; (void)colors_precomp; (void)projmatrix; (void)campos; (void)dL_dsh;
+    hipStream_t stream = (hipStream_t)stream_;
+    if (const int rc = sf_pose_check("surfel backward_view", P, P < 0 || R < 0 || width <= 0 || height < 2, transMat_precomp, dL_dviewmatrix,
+                                     view_partials, view_partial_floats, stream))
+        return rc < 0 ? rc : 0;
+    return sf_backward_impl(P, R, background, width, height, means3D, scales, scale_modifier, rotations, nullptr, viewmatrix,
+                            beam_inclinations, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_depths, dL_dmean2D, dL_dnormal,
+                            dL_dopacity, dL_dcolor, dL_dmean3D, dL_dtransMat, dL_dtransMat_2dtemp, dL_dscale, dL_drot, depth, debug, stream,
+                            dL_dviewmatrix, view_partials);
 }
 
 int lidargs_surfel_visible_filter(lidargs_alloc_fn geometry_alloc, void* geometry_user, lidargs_alloc_fn binning_alloc, void* binning_user,
@@ -281,6 +337,28 @@ int lidargs_debug_surfel_gaussian_backward(int P, int width, int height, int sta
     lg::SfGaussBwdArgs ga = lg::sf_gauss_bwd_args(sc, rows, gacc, tlist, tcount); ga.W = width; ga.H = height; ga.radii = radii; ga.depth = depth;
     lg::launch_sf_gaussian_backward(ga, stream);
     SF_CHECK("debug surfel gaussian backward");
+    return 0;
+}
+
+int lgsfpose_debug_view_backward(int P, int width, int height, const float* gacc, const float* means3D, const float* scales, float scale_modifier,
+                                 const float* rotations, const float* viewmatrix, const float* beams, const int* radii, float* dL_dmean2D,
+                                 float* dL_dnormal, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dtransMat,
+                                 float* dL_dtransMat_2dtemp, float* dL_dscale, float* dL_drot, float* depth, const unsigned char* tlist,
+                                 const unsigned short* tcount, float* dL_dviewmatrix, float* view_partials, size_t view_partial_floats,
+                                 void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const int debug = 0;
+    const float* transMat_precomp = nullptr;
+    if (const int rc = sf_pose_check("debug_surfel_view_backward", P, P < 0 || width <= 0 || height < 2, transMat_precomp, dL_dviewmatrix,
+                                     view_partials, view_partial_floats, stream))
+        return rc < 0 ? rc : 0;
+    SF_SCENE(sc, beams); SF_GRAD_ROWS(rows);
+    if (!gacc || !tlist || !tcount || !means3D || !scales || !rotations || !viewmatrix || !beams || !radii || !rows.required() || !depth)
+        return lg::api_fail(LIDARGS_ERR_INVALID_ARGUMENT, "debug_surfel_view_backward: NULL required pointer");
+    lg::SfGaussBwdArgs ga = lg::sf_gauss_bwd_args(sc, rows, gacc, tlist, tcount); ga.W = width; ga.H = height; ga.radii = radii; ga.depth = depth;
+    ga.view_partials = view_partials; ga.scale_modifier = scale_modifier;
+    lg::launch_sf_gaussian_backward_view(ga, dL_dviewmatrix, stream);
+    SF_CHECK("debug surfel view backward");
     return 0;
 }
 

@@ -4,7 +4,8 @@ Same public surface as R2/diff_lidargs_surfel_rasterization/__init__.py: `Gaussi
 (14 fields, :188-202), `GaussianRasterizer` with forward / markVisible / visible_filter (:204-273) and the
 functional `rasterize_gaussians` (:21-43).  forward returns (color[2,H,W], radii[P], others[7,H,W], pixels[P,1]);
 gradients flow to means3D, means2D (the [P,4] densification statistics), colors_precomp, opacities, scales[P,2]
-and rotations.  A precomputed transform (`cov3Ds_precomp` = transMat_precomp [P,9]) is honoured as the reference honours it --
+and rotations -- and, beyond the reference, to raster_settings.viewmatrix (the sensor pose) when that tensor requires grad (not together
+with a precomputed transform).  A precomputed transform (`cov3Ds_precomp` = transMat_precomp [P,9]) is honoured as the reference honours it --
 given NEXT TO scales / rotations through the functional `rasterize_gaussians`, it replaces the rows the blends use, and receives
 dL_dtransMat; spherical harmonics are not part of the LiDAR path (rejected natively).
 """
@@ -63,7 +64,38 @@ class _RasterizeGaussians(torch.autograd.Function):
                 grad_rotations, grad_transMat if cov3Ds_precomp.numel() else None, None)
 
 
+class _RasterizeGaussiansPose(torch.autograd.Function):
+    """The node of a frame whose `raster_settings.viewmatrix` requires grad (no reference counterpart): that tensor is one more input, in
+    front of `_RasterizeGaussians`' nine, and the backward asks the library for its gradient as well (lgsfpose_backward_view).  A node of
+    its own, so that the node above -- every other frame's -- stays what it was, line for line."""
+
+    @staticmethod
+    def forward(ctx, viewmatrix, *inputs):
+        _C.refuse_pose_with_transmat(inputs[7])                         # here, not first in backward
+        return _RasterizeGaussians.forward(ctx, *inputs)                # (raster_settings.viewmatrix is this tensor)
+
+    @staticmethod
+    def backward(ctx, grad_out_color, grad_radii, grad_others, grad_pix):
+        rs = ctx.raster_settings
+        colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning, img = ctx.saved_tensors
+        plane = lambda g, c: g if g is not None else torch.zeros((c, rs.image_height, rs.image_width), dtype=torch.float32, device=means3D.device)
+        (grad_means2D, grad_colors, grad_opacities, grad_means3D, _grad_transMat, grad_sh, grad_scales, grad_rotations, _depth,
+         grad_viewmatrix) = _C.rasterize_gaussians_backward(
+            rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix,
+            rs.projmatrix, rs.beam_inclinations, plane(grad_out_color, 2), plane(grad_others, 7), sh, rs.sh_degree, rs.campos, geom,
+            ctx.num_rendered, binning, img, rs.debug, want_intermediates=False, want_viewmatrix_grad=True)
+        # float32 [4, 4] in the layout of raster_settings.viewmatrix, then the nine slots of the node above
+        return (grad_viewmatrix.reshape(rs.viewmatrix.shape), grad_means3D, grad_means2D, grad_sh if sh.numel() else None, grad_colors,
+                grad_opacities, grad_scales, grad_rotations, None, None)
+
+
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
+    # The sensor pose is differentiable on request: a viewmatrix that requires grad becomes one more tensor input of the node and
+    # receives dL/dviewmatrix (culling, the beam model's pixel decisions, pruning and binning are not differentiated).  Otherwise the
+    # node is called exactly as before.
+    if raster_settings.viewmatrix.requires_grad and torch.is_grad_enabled():
+        return _RasterizeGaussiansPose.apply(raster_settings.viewmatrix, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                             cov3Ds_precomp, raster_settings)
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                                      raster_settings)
 

@@ -100,7 +100,8 @@ def signatures(include=INCLUDE, prefix="lidargs_"):
 
 def type_also(lib, include, prefix, package="diff_lidargs_rasterization"):
     """Types, on an already loaded `lib`, every function that the headers of a further directory declare under `prefix` (the main
-    library's pose entry points: build_hip.POSE_INCLUDE, POSE_PREFIX); a declared function the library lacks is an ImportError."""
+    library's pose entry points: build_hip.POSE_INCLUDE, POSE_PREFIX and SURFEL_POSE_INCLUDE, SURFEL_POSE_PREFIX); a declared function
+    the library lacks is an ImportError."""
     for name, (restype, argtypes) in signatures(include, prefix).items():
         try:
             fn = getattr(lib, name)
