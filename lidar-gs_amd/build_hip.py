@@ -35,6 +35,10 @@ POSE_PREFIX = "lgpose_"
 # lidargs_surfel_backward's host sequence.  A directory and prefix of their own, so that include_pose/ stays the 3-D form's three functions.
 SURFEL_POSE_INCLUDE = os.path.join(ROOT, "include_surfel_pose")
 SURFEL_POSE_PREFIX = "lgsfpose_"
+# ... and the fourth: sweep-motion compensation (lgsweep_*, include_sweep/lidargs_sweep.h, csrc/sweep_motion.hip), a warp of the means in front
+# of either rasterizer.  It reports through lidargs_last_error and every .hip of csrc/ belongs to a target, so it is part of this library.
+SWEEP_INCLUDE = os.path.join(ROOT, "include_sweep")
+SWEEP_PREFIX = "lgsweep_"
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-fno-gpu-rdc", "-Wall",
           "-Wno-unused-function", "-Wno-unused-value"]
 SOURCES = {
@@ -50,6 +54,7 @@ SOURCES = {
     "anchor_growing.hip": ["-ffp-contract=off"],   # anchor + offset * scaling is two roundings in torch: the voxel an offset falls into is compared bit for bit
     "knn.hip": ["-ffp-contract=off"],              # the 3-NN squared distances and the voxel quotients are compared bit for bit; the box bound prunes exactly only without contraction
     "metrics.hip": ["-ffp-contract=off"],          # the SSIM map and the float32 means round as scikit-image / torch write them
+    "sweep_motion.hip": ["-ffp-contract=on"],      # fused only inside an expression: the backward's two forms (with and without the reduced gradients) round dL_dmeans3D alike
 }
 # sources: {file of csrc/: [per-file flags]}; include: its header directory; prefix: of its symbols (<prefix>_abi_version, <prefix>_last_error,
 # the macro <PREFIX>_ABI_VERSION); package: the importer that the loader's error messages name (lidargs_abi.library)
@@ -89,9 +94,9 @@ def _listed(d, keep=lambda f: True):
 def deps(target):
     """What a library is rebuilt for: its own sources, every shared file of csrc/ that is not a .hip (headers and .inc, whichever
     target includes them: more than needed, never less), every header of its include directory and this file; the main library also
-    for the headers of its pose entry points (POSE_INCLUDE, SURFEL_POSE_INCLUDE)."""
+    for the headers of its pose and sweep entry points (POSE_INCLUDE, SURFEL_POSE_INCLUDE, SWEEP_INCLUDE)."""
     return ([os.path.join(CSRC, f) for f in target.sources] + _listed(CSRC, lambda f: not f.endswith(".hip"))
-            + _listed(target.include) + (_listed(POSE_INCLUDE) + _listed(SURFEL_POSE_INCLUDE) if target.name == "hip" else []) + [os.path.abspath(__file__)])
+            + _listed(target.include) + (_listed(POSE_INCLUDE) + _listed(SURFEL_POSE_INCLUDE) + _listed(SWEEP_INCLUDE) if target.name == "hip" else []) + [os.path.abspath(__file__)])
 
 
 def stale(target):
