@@ -9,6 +9,16 @@ exports exactly what include/ declares.  Staleness (stale, deps), the build loop
 are all derived from the table, and so is what the Python side loads (lidargs_abi.library takes a library's path, headers, version
 function and the name in its error messages from its entry): a further library is one more entry.
 
+A target's `include` and `prefix` are its primary, versioned interface (<prefix>_abi_version, <prefix>_last_error); `families` names what
+else the library exports: per family a header directory and a symbol prefix of its own.  Only `hip` has any.  Its pose-gradient entry
+points (`pose`: the 3-D rasterizer's, `surfel_pose`: the surfel rasterizer's, kept apart so that include_pose/ stays the 3-D form's
+three functions) run lidargs_backward's and lidargs_surfel_backward's host sequences and share the process-wide state, and sweep-motion
+compensation (`sweep`, csrc/sweep_motion.hip: a warp of the means in front of either rasterizer) reports through lidargs_last_error and
+every .hip of csrc/ belongs to a target: so all three are part of liblidargs_hip.so and not libraries of their own, while include/ and the
+library's lidargs_* exports stay the drop-in boundary for the reference's interfaces.  A family's headers are rebuilt for, hashed and
+typed exactly as the primary ones are (header_dirs); a further family is one more record in the `hip` entry, one header, and one line of
+tests/native_lib_checks.FAMILIES.
+
 Per-file flags: the per-Gaussian kernels (preprocess.hip) are HBM-bound, so they are built with
 -ffp-contract=off: every expression rounds as written, which keeps the unit vectors s = p/|p| that
 feed the cancellation-prone blend difference (s - q) bit-identical to an un-fused evaluation.
@@ -26,19 +36,6 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 OUT = os.path.join(HERE, "diff_lidargs_rasterization", "liblidargs_hip.so")
-# The main library's second header directory and symbol prefix: the pose-gradient entry points (lgpose_*, include_pose/lidargs_pose.h)
-# need lidargs_backward's host sequence and process-wide state, so they are part of liblidargs_hip.so and not a library of their own;
-# include/ and the library's lidargs_* exports stay the drop-in boundary for the reference's interfaces.
-POSE_INCLUDE = os.path.join(ROOT, "include_pose")
-POSE_PREFIX = "lgpose_"
-# ... and the third: the surfel rasterizer's pose-gradient entry points (lgsfpose_*, include_surfel_pose/lidargs_surfel_pose.h), which run
-# lidargs_surfel_backward's host sequence.  A directory and prefix of their own, so that include_pose/ stays the 3-D form's three functions.
-SURFEL_POSE_INCLUDE = os.path.join(ROOT, "include_surfel_pose")
-SURFEL_POSE_PREFIX = "lgsfpose_"
-# ... and the fourth: sweep-motion compensation (lgsweep_*, include_sweep/lidargs_sweep.h, csrc/sweep_motion.hip), a warp of the means in front
-# of either rasterizer.  It reports through lidargs_last_error and every .hip of csrc/ belongs to a target, so it is part of this library.
-SWEEP_INCLUDE = os.path.join(ROOT, "include_sweep")
-SWEEP_PREFIX = "lgsweep_"
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-fno-gpu-rdc", "-Wall",
           "-Wno-unused-function", "-Wno-unused-value"]
 SOURCES = {
@@ -57,10 +54,15 @@ SOURCES = {
     "sweep_motion.hip": ["-ffp-contract=on"],      # fused only inside an expression: the backward's two forms (with and without the reduced gradients) round dL_dmeans3D alike
 }
 # sources: {file of csrc/: [per-file flags]}; include: its header directory; prefix: of its symbols (<prefix>_abi_version, <prefix>_last_error,
-# the macro <PREFIX>_ABI_VERSION); package: the importer that the loader's error messages name (lidargs_abi.library)
-Target = collections.namedtuple("Target", "name out sources include prefix package")
+# the macro <PREFIX>_ABI_VERSION); package: the importer that the loader's error messages name (lidargs_abi.library); families: further
+# (name, header directory, symbol prefix) records of entry points that the same library exports (the docstring says which and why)
+Family = collections.namedtuple("Family", "name include prefix")
+Target = collections.namedtuple("Target", "name out sources include prefix package families", defaults=((),))
 TARGETS = {t.name: t for t in (
-    Target("hip", OUT, SOURCES, os.path.join(ROOT, "include"), "lidargs", "diff_lidargs_rasterization"),
+    Target("hip", OUT, SOURCES, os.path.join(ROOT, "include"), "lidargs", "diff_lidargs_rasterization", (
+        Family("pose", os.path.join(ROOT, "include_pose"), "lgpose"),
+        Family("surfel_pose", os.path.join(ROOT, "include_surfel_pose"), "lgsfpose"),
+        Family("sweep", os.path.join(ROOT, "include_sweep"), "lgsweep"))),
     Target("optim", os.path.join(HERE, "lidargs_optim", "liblidargs_optim.so"), {
         "adam.hip": ["-ffp-contract=off"],         # torch's op-by-op roundings; the steps its device kernels fuse are written as fmaf
     }, os.path.join(ROOT, "include_optim"), "lidargs_optim", "lidargs_optim"),
@@ -91,12 +93,16 @@ def _listed(d, keep=lambda f: True):
     return sorted(os.path.join(d, f) for f in os.listdir(d) if keep(f))
 
 
+def header_dirs(target):
+    """Every header directory of a target: the primary one first, then its families' in the table's order."""
+    return [target.include] + [f.include for f in target.families]
+
+
 def deps(target):
     """What a library is rebuilt for: its own sources, every shared file of csrc/ that is not a .hip (headers and .inc, whichever
-    target includes them: more than needed, never less), every header of its include directory and this file; the main library also
-    for the headers of its pose and sweep entry points (POSE_INCLUDE, SURFEL_POSE_INCLUDE, SWEEP_INCLUDE)."""
+    target includes them: more than needed, never less), every header of its header directories and this file."""
     return ([os.path.join(CSRC, f) for f in target.sources] + _listed(CSRC, lambda f: not f.endswith(".hip"))
-            + _listed(target.include) + (_listed(POSE_INCLUDE) + _listed(SURFEL_POSE_INCLUDE) + _listed(SWEEP_INCLUDE) if target.name == "hip" else []) + [os.path.abspath(__file__)])
+            + [h for d in header_dirs(target) for h in _listed(d)] + [os.path.abspath(__file__)])
 
 
 def stale(target):
@@ -107,8 +113,8 @@ def stale(target):
 
 
 def build_id_files():
-    """Everything the libraries are built from: csrc/, every target's public headers, this file."""
-    return _listed(CSRC) + [f for t in TARGETS.values() for f in _listed(t.include)] + [os.path.abspath(__file__)]
+    """Everything the libraries are built from: csrc/, every target's public headers (header_dirs), this file."""
+    return _listed(CSRC) + [h for t in TARGETS.values() for d in header_dirs(t) for h in _listed(d)] + [os.path.abspath(__file__)]
 
 
 def build_id():

@@ -19,9 +19,9 @@ import torch
 import lidargs_abi
 
 NUM_CHANNELS = 2  # R3/cr/config.h:15
-# The one CDLL of the process, every lidargs_* function typed from the headers (restype and argtypes: lidargs_abi).
+# The one CDLL of the process, every function of the library (lidargs_* and the families of its entry in build_hip.TARGETS: lgpose_*,
+# lgsfpose_*, lgsweep_*) typed from the headers (restype and argtypes: lidargs_abi).
 _lib = lidargs_abi.library("hip")
-lidargs_abi.type_also(_lib, lidargs_abi.build_hip.POSE_INCLUDE, lidargs_abi.build_hip.POSE_PREFIX)     # lgpose_*: include_pose/lidargs_pose.h
 _ptr, _stream = lidargs_abi.ptr, lidargs_abi.stream
 _ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_size_t)
 

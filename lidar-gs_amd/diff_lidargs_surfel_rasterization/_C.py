@@ -9,13 +9,9 @@ diff_lidargs_rasterization._C; there is no CPU path.
 """
 import torch
 
-import lidargs_abi
 from diff_lidargs_rasterization import _C as _base
 
-_lib = _base._lib
-# lgsfpose_*: include_surfel_pose/lidargs_surfel_pose.h, typed from the header on the process' one CDLL
-lidargs_abi.type_also(_lib, lidargs_abi.build_hip.SURFEL_POSE_INCLUDE, lidargs_abi.build_hip.SURFEL_POSE_PREFIX,
-                      package="diff_lidargs_surfel_rasterization")
+_lib = _base._lib     # the process' one CDLL: lgsfpose_* (include_surfel_pose/lidargs_surfel_pose.h) is typed on it with everything else
 _alloc_cb, _Scratch, _f32, _ptr, _stream, _require_device, _raise = (
     _base._alloc_cb, _base._Scratch, _base._f32, _base._ptr, _base._stream, _base._require_device, _base._raise)
 NUM_CHANNELS = 2   # R2/cr/config.h

@@ -1,9 +1,11 @@
 """lidargs_abi -- the Python side of the C ABI: one loader, every signature and integer constant read from the public headers.
 
-`library(name)` opens the library of `build_hip.TARGETS[name]` and sets `restype` and `argtypes` of every function its header directory
-declares; for "hip" the result is the one `CDLL` every module calls through (`diff_lidargs_rasterization._C._lib`).  The table says where
-the library and its headers are, how its symbols begin and which package the error messages name; `load()` is the same with these
-spelt out.  The headers are the only source: a new entry point is typed the moment it is declared, a prototype this parser cannot map is
+`library(name)` opens the library of `build_hip.TARGETS[name]` and sets `restype` and `argtypes` of every function its header directories
+declare, the primary one and those of its families alike; for "hip" the result is the one `CDLL` every module calls through
+(`diff_lidargs_rasterization._C._lib`).  The table says where the library and its headers are, how its symbols begin and which package
+the error messages name; `load()` is the same with these spelt out.  A prefix is written as the table writes it, without the underscore
+that ends it (`lidargs`, `lgpose`); `_prototype` alone adds it.
+The headers are the only source: a new entry point is typed the moment it is declared, a prototype this parser cannot map is
 an ImportError naming the function, never a function left untyped, and the expected ABI version and every other `#define LIDARGS_*
 <integer>` is read (`constants`), not mirrored.  What every call site needs around a call is here once as well: `ptr`, `stream`, `check`
 and `poison_scratch`.
@@ -31,9 +33,13 @@ INCLUDE = build_hip.TARGETS["hip"].include
 
 _BY_VALUE = {"int": C.c_int, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t}
 _RETURNS = dict(_BY_VALUE, **{"void": None, "const char*": C.c_char_p})
-_PROTOTYPE = re.compile(r"(?P<ret>[\w\s*]+?)\s*\b(?P<name>lidargs_\w+)\s*\((?P<params>.*)\)", re.S)
 _COMMENT = re.compile(r"/\*.*?\*/|//[^\n]*", re.S)
 _CONSTANT = re.compile(r"^[ \t]*#[ \t]*define[ \t]+(LIDARGS_\w+)[ \t]+(-?\d+|\(-?\d+\))[ \t]*$", re.M)
+
+
+def _prototype(prefix):
+    """A whole statement that declares a function named <prefix>_* (re keeps what it compiled)."""
+    return re.compile(r"(?P<ret>[\w\s*]+?)\s*\b(?P<name>" + re.escape(prefix) + r"_\w+)\s*\((?P<params>.*)\)", re.S)
 
 
 def _split_params(params):
@@ -59,11 +65,11 @@ def _param_type(decl, name):
     return ctype
 
 
-def parse_header(text, prefix="lidargs_"):
+def parse_header(text, prefix="lidargs"):
     """{function name: (restype, (argtypes, ...))} of every prototype in a header's text.  Comments, preprocessor lines, typedefs,
     enums and the extern "C" braces are dropped; every statement that is left must be a `lidargs_*` prototype (`prefix`: another
-    family of names, as the pose header's `lgpose_`)."""
-    prototype = _PROTOTYPE if prefix == "lidargs_" else re.compile(_PROTOTYPE.pattern.replace("lidargs_", re.escape(prefix)), re.S)
+    family of names, as the pose header's `lgpose`)."""
+    prototype = _prototype(prefix)
     src = _COMMENT.sub(" ", text)
     src = re.sub(r"^[ \t]*#.*$", " ", src, flags=re.M)
     src = re.sub(r"\b(typedef|enum)\b[^;{]*(\{[^}]*\})?[^;]*;", " ", src)
@@ -90,25 +96,12 @@ def _headers(include):
             yield f.read()
 
 
-def signatures(include=INCLUDE, prefix="lidargs_"):
+def signatures(include=INCLUDE, prefix="lidargs"):
     """The signatures of every header of a header directory (include/ unless another is named)."""
     sigs = {}
     for text in _headers(include):
         sigs.update(parse_header(text, prefix))
     return sigs
-
-
-def type_also(lib, include, prefix, package="diff_lidargs_rasterization"):
-    """Types, on an already loaded `lib`, every function that the headers of a further directory declare under `prefix` (the main
-    library's pose entry points: build_hip.POSE_INCLUDE, POSE_PREFIX and SURFEL_POSE_INCLUDE, SURFEL_POSE_PREFIX); a declared function
-    the library lacks is an ImportError."""
-    for name, (restype, argtypes) in signatures(include, prefix).items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
-            raise ImportError(f"{package}: {os.path.basename(lib._name)} does not export {name}, which the headers declare; rebuild it") from None
-        fn.restype, fn.argtypes = restype, argtypes
-    return lib
 
 
 def constants(include=INCLUDE):
@@ -123,17 +116,21 @@ def __getattr__(name):
     raise AttributeError(f"module 'lidargs_abi' has no attribute '{name}'")
 
 
-def load(path, include=INCLUDE, version_fn="lidargs_abi_version", version=None, package="diff_lidargs_rasterization"):
+def load(path, include=INCLUDE, version_fn="lidargs_abi_version", version=None, package="diff_lidargs_rasterization", families=()):
     """The typed CDLL of the library at `path` (liblidargs_hip.so unless the other arguments say otherwise): every function the headers
-    of `include` declare is typed, and `version_fn()` must return `version`: unless one is given, the macro of that name in upper case
-    (LIDARGS_ABI_VERSION), as the headers define it.  `package` names the importer in the error messages."""
+    of `include` declare, and of each of `families` (build_hip.Family: a header directory and the prefix of its names), is typed, and
+    `version_fn()` must return `version`: unless one is given, the macro of that name in upper case (LIDARGS_ABI_VERSION), as the
+    headers define it.  `package` names the importer in the error messages."""
     so = os.path.basename(path)
     if not os.path.exists(path):
         raise ImportError(
             f"{package}: native library {path} is missing. Build it with "
             "`python lidar-gs_amd/build_hip.py` (hipcc --offload-arch=gfx950). There is no CPU fallback.")
     lib = C.CDLL(path)
-    for name, (restype, argtypes) in signatures(include).items():
+    sigs = signatures(include)
+    for family in families:
+        sigs.update(signatures(family.include, family.prefix))
+    for name, (restype, argtypes) in sigs.items():
         try:
             fn = getattr(lib, name)
         except AttributeError:
@@ -155,7 +152,7 @@ def library_constants(name):
 def library(name):
     """load() of the library `name` of build_hip.TARGETS, with everything taken from its entry."""
     t = build_hip.TARGETS[name]
-    return load(t.out, include=t.include, version_fn=t.prefix + "_abi_version", package=t.package)
+    return load(t.out, include=t.include, version_fn=t.prefix + "_abi_version", package=t.package, families=t.families)
 
 
 def ptr(t):

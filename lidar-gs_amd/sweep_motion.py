@@ -18,9 +18,7 @@ import torch
 import lidargs_abi
 from diff_lidargs_rasterization import _C as _base
 
-_lib = _base._lib
-# lgsweep_*: include_sweep/lidargs_sweep.h, typed from the header on the process' one CDLL
-lidargs_abi.type_also(_lib, lidargs_abi.build_hip.SWEEP_INCLUDE, lidargs_abi.build_hip.SWEEP_PREFIX, package="sweep_motion")
+_lib = _base._lib     # the process' one CDLL: lgsweep_* (include_sweep/lidargs_sweep.h) is typed on it with everything else
 _ptr, _stream = lidargs_abi.ptr, lidargs_abi.stream
 _POISON = lidargs_abi.poison_scratch()
 

@@ -11,8 +11,11 @@ import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADERS = [os.path.join(ROOT, "include", "lidargs_rasterizer.h"), os.path.join(ROOT, "include_pose", "lidargs_pose.h")]
+import build_hip
+
+HIP = build_hip.TARGETS["hip"]             # the frame entry points: the primary header and the `pose` family's
+HEADERS = [os.path.join(HIP.include, "lidargs_rasterizer.h"),
+           os.path.join(next(f.include for f in HIP.families if f.name == "pose"), "lidargs_pose.h")]
 
 INVALID, NO_COLORS, STATE = -1, -2, -5        # LIDARGS_ERR_INVALID_ARGUMENT, _NO_COLORS, _STATE (include/lidargs_rasterizer.h)
 

@@ -2,46 +2,29 @@
 plain C and declares exactly the expected functions, the library exports exactly those under that prefix, the binding's one CDLL types
 them from the header, and arguments are refused before any device work.  The `lidargs_*` side of the library is tests/test_abi_cpu.py's."""
 import ctypes
-import os
-import re
-import subprocess
 
 import pytest
 
 import build_hip
 import lidargs_abi
+from native_lib_checks import check_family
 
 DECLARED = {"lgpose_backward_view", "lgpose_view_partial_floats", "lgpose_debug_view_backward"}
 
 
 def test_header_library_and_binding_agree(hip_lib_built):
-    assert os.listdir(build_hip.POSE_INCLUDE) == ["lidargs_pose.h"] and build_hip.POSE_PREFIX == "lgpose_"
-    header = os.path.join(build_hip.POSE_INCLUDE, "lidargs_pose.h")
-    r = subprocess.run(["gcc", "-std=c99", "-fsyntax-only", "-Wall", "-Werror", "-x", "c", header], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    typed = lidargs_abi.signatures(build_hip.POSE_INCLUDE, build_hip.POSE_PREFIX)
-    assert set(typed) == DECLARED
-    with pytest.raises(ImportError):                                        # nothing of the lidargs_* family hides in this directory
-        lidargs_abi.signatures(build_hip.POSE_INCLUDE)
-    out = subprocess.run(["nm", "-D", "--defined-only", hip_lib_built], capture_output=True, text=True, check=True).stdout
-    assert set(re.findall(r" T (lgpose_\w+)", out)) == DECLARED
-    assert header in build_hip.deps(build_hip.TARGETS["hip"])               # the library is rebuilt for it
-    assert not any(header in build_hip.deps(t) for t in build_hip.TARGETS.values() if t.name != "hip")
+    typed = check_family("pose", "lidargs_pose.h", DECLARED, hip_lib_built)
     i, f, z, p = ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_void_p   # written from the header by eye
     back = lidargs_abi.signatures()["lidargs_backward"]
     assert typed["lgpose_backward_view"] == (i, back[1] + (p, p, z))       # lidargs_backward's list + three
     assert typed["lgpose_view_partial_floats"] == (z, (i,))
     assert typed["lgpose_debug_view_backward"] == (i, (i, p, p, p, f, p, p, p) + (p,) * 12 + (p, p, p, p, p, p, z, p))
-    from diff_lidargs_rasterization import _C
-    for name, (restype, argtypes) in typed.items():
-        fn = getattr(_C._lib, name)
-        assert fn.restype is restype and tuple(fn.argtypes) == argtypes, name
 
 
 def test_a_declared_function_the_library_lacks_is_an_import_error(hip_lib_built, tmp_path):
     (tmp_path / "x.h").write_text("int lgpose_not_there(int a);\n")
     with pytest.raises(ImportError, match="does not export lgpose_not_there"):
-        lidargs_abi.type_also(ctypes.CDLL(hip_lib_built), str(tmp_path), "lgpose_")
+        lidargs_abi.load(hip_lib_built, families=(build_hip.Family("tmp", str(tmp_path), "lgpose"),))
 
 
 def test_arguments_are_refused_before_any_device_work(hip_lib_built):

@@ -3,33 +3,18 @@ liblidargs_hip.so): the header is plain C99 and declares exactly the expected fu
 prefix, the surfel binding types them from the header on the process' one CDLL, and arguments are refused before any device work.
 The 3-D form's side is tests/test_pose_abi_cpu.py's, the `lidargs_*` side tests/test_abi_cpu.py's."""
 import ctypes
-import os
-import re
-import subprocess
 
 import pytest
 
-import build_hip
 import lidargs_abi
+from native_lib_checks import check_family
 
 DECLARED = {"lgsfpose_backward_view", "lgsfpose_view_partial_floats", "lgsfpose_debug_view_backward"}
 ALIGNED = ctypes.c_void_p(0x1000)                                           # a pointer that passes the checks and is never dereferenced
 
 
 def test_header_library_and_binding_agree(hip_lib_built):
-    assert os.listdir(build_hip.SURFEL_POSE_INCLUDE) == ["lidargs_surfel_pose.h"] and build_hip.SURFEL_POSE_PREFIX == "lgsfpose_"
-    header = os.path.join(build_hip.SURFEL_POSE_INCLUDE, "lidargs_surfel_pose.h")
-    r = subprocess.run(["gcc", "-std=c99", "-fsyntax-only", "-Wall", "-Werror", "-x", "c", header], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    typed = lidargs_abi.signatures(build_hip.SURFEL_POSE_INCLUDE, build_hip.SURFEL_POSE_PREFIX)
-    assert set(typed) == DECLARED
-    for other in ("lidargs_", build_hip.POSE_PREFIX):                       # nothing of the other families hides in this directory
-        with pytest.raises(ImportError):
-            lidargs_abi.signatures(build_hip.SURFEL_POSE_INCLUDE, other)
-    out = subprocess.run(["nm", "-D", "--defined-only", hip_lib_built], capture_output=True, text=True, check=True).stdout
-    assert set(re.findall(r" T (lgsfpose_\w+)", out)) == DECLARED
-    assert header in build_hip.deps(build_hip.TARGETS["hip"])               # the library is rebuilt for it
-    assert not any(header in build_hip.deps(t) for t in build_hip.TARGETS.values() if t.name != "hip")
+    typed = check_family("surfel_pose", "lidargs_surfel_pose.h", DECLARED, hip_lib_built)
     i, f, z, p = ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_void_p   # written from the header by eye
     back = lidargs_abi.signatures()["lidargs_surfel_backward"]
     assert typed["lgsfpose_backward_view"] == (i, back[1] + (p, p, z))      # lidargs_surfel_backward's list + three
@@ -38,9 +23,6 @@ def test_header_library_and_binding_agree(hip_lib_built):
     from diff_lidargs_surfel_rasterization import _C
     from diff_lidargs_rasterization import _C as base
     assert _C._lib is base._lib                                             # the one CDLL of the process
-    for name, (restype, argtypes) in typed.items():
-        fn = getattr(_C._lib, name)
-        assert fn.restype is restype and tuple(fn.argtypes) == argtypes, name
 
 
 def _backward_view_args(P=4, transMat=None, out=ALIGNED, partials=ALIGNED, n=None, width=64, height=8, lib=None):

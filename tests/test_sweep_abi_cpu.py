@@ -3,34 +3,18 @@ header is plain C and declares exactly the expected functions, the library expor
 `lidargs_`, the binding's one CDLL types them from the header, and arguments are refused before any device work (never-dereferenced
 pointers: no device is needed).  The `lidargs_*` side of the library is tests/test_abi_cpu.py's."""
 import ctypes
-import os
-import re
-import subprocess
 
 import pytest
 
 import build_hip
-import lidargs_abi
+from native_lib_checks import check_family
 
 DECLARED = {"lgsweep_partial_floats", "lgsweep_forward", "lgsweep_backward"}
 
 
 def test_header_library_and_binding_agree(hip_lib_built):
-    assert os.listdir(build_hip.SWEEP_INCLUDE) == ["lidargs_sweep.h"] and build_hip.SWEEP_PREFIX == "lgsweep_"
-    header = os.path.join(build_hip.SWEEP_INCLUDE, "lidargs_sweep.h")
-    r = subprocess.run(["gcc", "-std=c99", "-fsyntax-only", "-Wall", "-Werror", "-x", "c", header], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    typed = lidargs_abi.signatures(build_hip.SWEEP_INCLUDE, build_hip.SWEEP_PREFIX)
-    assert set(typed) == DECLARED
-    for other in ("lidargs_", build_hip.POSE_PREFIX, build_hip.SURFEL_POSE_PREFIX):          # nothing of another family hides in this directory
-        with pytest.raises(ImportError):
-            lidargs_abi.signatures(build_hip.SWEEP_INCLUDE, other)
-    out = subprocess.run(["nm", "-D", "--defined-only", hip_lib_built], capture_output=True, text=True, check=True).stdout
-    assert set(re.findall(r" T (lgsweep_\w+)", out)) == DECLARED
-    assert set(re.findall(r" T (lidargs_\w+)", out)) == set(lidargs_abi.signatures())         # the drop-in boundary is what include/ declares
+    typed = check_family("sweep", "lidargs_sweep.h", DECLARED, hip_lib_built)
     assert "sweep_motion.hip" in build_hip.SOURCES
-    assert header in build_hip.deps(build_hip.TARGETS["hip"])                                 # the library is rebuilt for it
-    assert not any(header in build_hip.deps(t) for t in build_hip.TARGETS.values() if t.name != "hip")
     i, f, z, p = ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_void_p               # written from the header by eye
     assert typed["lgsweep_partial_floats"] == (z, (i,))
     assert typed["lgsweep_forward"] == (i, (i, p, p, p, f, f, i, p, p))
@@ -38,9 +22,6 @@ def test_header_library_and_binding_agree(hip_lib_built):
     import sweep_motion
     from diff_lidargs_rasterization import _C
     assert sweep_motion._lib is _C._lib                                                      # the process' one CDLL
-    for name, (restype, argtypes) in typed.items():
-        fn = getattr(_C._lib, name)
-        assert fn.restype is restype and tuple(fn.argtypes) == argtypes, name
 
 
 def test_arguments_are_refused_before_any_device_work(hip_lib_built):
