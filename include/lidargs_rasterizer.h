@@ -39,6 +39,17 @@
  * lidargs_backward on those buffers -- which reads no environment -- returns gradients that are a pure function
  * of its inputs (64-bit integer accumulation across workgroups instead of float atomics).  lidargs_forward_enqueue,
  * the shell / wedge forwards and lidargs_surfel_forward return LIDARGS_ERR_INVALID_ARGUMENT while it is set.
+ *
+ * LIDARGS_DEPTH in the environment of lidargs_forward (read at every call; literal values only, anything else is the
+ * default) selects what out_depth holds: unset = the expected range (sum of range x alpha x T); `median` = the range
+ * of the Gaussian at which the transmittance falls through one half; `strongest` = the range of the Gaussian with the
+ * largest blend weight alpha x T, a LiDAR's strongest return; `second` = its second return, the range of the Gaussian
+ * with the largest weight among those at least LIDARGS_RETURN_GAP metres of range (read at the same call; unset = 0)
+ * away from the strongest one, 0 where there is none.  Under the three values the image buffer is asked for 4 bytes
+ * per pixel more (the Gaussian each pixel returned) and the geometry buffer carries a mode bit; lidargs_backward on
+ * such buffers sends a pixel's dL_dout_depth to that one Gaussian and does not know by which rule it was picked.
+ * out_color, out_occ and radii are the default forward's.  The same entry points refuse the three values as refuse
+ * LIDARGS_DETERMINISTIC=1, and lidargs_forward refuses them together with it.
  */
 #ifndef LIDARGS_RASTERIZER_H
 #define LIDARGS_RASTERIZER_H

@@ -282,14 +282,14 @@ int refuse_deterministic(const char* entry) {
     if (!deterministic_requested()) return 0;
     return fail(LIDARGS_ERR_INVALID_ARGUMENT, "%s: LIDARGS_DETERMINISTIC=1 is not supported by this entry point (only lidargs_forward / lidargs_backward are); unset it for this call", entry);
 }
-// LIDARGS_DEPTH=median / strongest, the same way: set by the first forward whose depth is one Gaussian's range (either value makes
+// LIDARGS_DEPTH=median / strongest / second, the same way: set by the first forward whose depth is one Gaussian's range (each value makes
 // "median buffers": LG_MODE_MEDIAN and the id plane), never cleared.  Until then a backward launches exactly what it launched before
 // the modes existed; from then on the first blend walk asks the buffer's mode word and k_median_backward is queued (it retires on one
 // load on a default buffer).  The buffer's word decides every result, not this flag.
 std::atomic<bool> g_median_seen{false};
 int refuse_depth_mode(const char* entry) {
     if (!picked_depth_requested()) return 0;
-    return fail(LIDARGS_ERR_INVALID_ARGUMENT, "%s: a non-default LIDARGS_DEPTH (median, strongest) is not supported by this entry point (only lidargs_forward / lidargs_backward are); unset it for this call", entry);
+    return fail(LIDARGS_ERR_INVALID_ARGUMENT, "%s: a non-default LIDARGS_DEPTH (median, strongest, second) is not supported by this entry point (only lidargs_forward / lidargs_backward are); unset it for this call", entry);
 }
 int api_read_words_zero_behind(const uint32_t* dev, int n, uint32_t* out, void* zero, size_t zero_bytes, hipStream_t s) {
     hipError_t e = (hipError_t)read_words_begin(dev, n, s);
@@ -561,6 +561,10 @@ struct FrameMode {
     // median_id plane behind everything else, the mode word gets LG_MODE_MEDIAN, and k_render_median / k_render_strongest overwrites
     // out_depth behind the blend (never together with `deterministic`).  `strongest` (only with `median`) picks the rule of that walk.
     bool median = false, strongest = false;
+    // LIDARGS_DEPTH=second (only with `median`, never with `strongest`): k_render_second behind the blend instead, with `return_gap`
+    // (LIDARGS_RETURN_GAP, metres) among its arguments -- the forward's alone: the buffers are median buffers and do not carry it
+    bool second = false;
+    float return_gap = 0.f;
 };
 
 // The preprocess' parameters of a whole frame on `grid`: no column wedge, full span records, pruning on, every row valid.  The forward,
@@ -674,9 +678,15 @@ int forward_impl(const FrameAllocs alloc, const SceneArgs sc, const FrameOutputs
         lg::MedianFwdArgs ma;
         ma.grid = L.grid; ma.ranges = img.ranges; ma.point_list = bin.val_a; ma.rec = geom.rec; ma.rowspan = geom.rowspan;
         ma.coltab = img.coltab; ma.rowtab = img.rowtab; ma.out_depth = out.out_depth; ma.median_id = img.median_id;
+        if (mode.second) {
+            lg::launch_render_second(ma, mode.return_gap, stream);
+            LG_STAGE_CHECK("render second");
+            lg::prof_mark("render_second", stream);
+        } else {
         lg::launch_render_median(ma, mode.strongest, stream);
         LG_STAGE_CHECK(mode.strongest ? "render strongest" : "render median");
         lg::prof_mark(mode.strongest ? "render_strongest" : "render_median", stream);
+        }
     }
 
     // the selection a backward on these buffers will make (backward_impl starts from the same call): counted now, while the buffers are certainly alive
@@ -795,9 +805,11 @@ int lidargs_forward(lidargs_alloc_fn geometry_alloc, void* geometry_user, lidarg
     FrameMode mode;
     mode.deterministic = lg::deterministic_requested();
     mode.strongest = lg::strongest_depth_requested();
-    mode.median = mode.strongest || lg::median_depth_requested();
+    mode.second = lg::second_depth_requested();
+    mode.median = mode.strongest || mode.second || lg::median_depth_requested();
+    if (mode.second) mode.return_gap = lg::return_gap();
     if (mode.deterministic && mode.median)   // (a picked Gaussian's depth gradient is added with a float atomic: not what the other switch promises)
-        return fail(LIDARGS_ERR_INVALID_ARGUMENT, "%s: a non-default LIDARGS_DEPTH (median, strongest) is not supported together with LIDARGS_DETERMINISTIC=1; unset one of them for this call", "lidargs_forward");
+        return fail(LIDARGS_ERR_INVALID_ARGUMENT, "%s: a non-default LIDARGS_DEPTH (median, strongest, second) is not supported together with LIDARGS_DETERMINISTIC=1; unset one of them for this call", "lidargs_forward");
     LG_FORWARD_ARGS(alloc, sc, out);
     return forward_impl(alloc, sc, out, mode, debug, (hipStream_t)stream);
 }

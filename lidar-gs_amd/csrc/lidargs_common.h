@@ -107,8 +107,8 @@ __device__ __forceinline__ uint2 span_unpack(uint32_t w) {            // -> (xsp
 // Word 4 now carries the forward's accumulation mode to every backward on the buffer: 0 (the forward's memset) = float atomics,
 // 1 = deterministic (LIDARGS_DETERMINISTIC=1 at the forward: the geometry buffer then ends in GeomView::acc64).  The backward's
 // KERNELS read it; the host never does, so a cloned or offloaded buffer carries its mode along and no backward waits for a read.
-// Bit 1 (LIDARGS_DEPTH=median or strongest at the forward): out_depth is one Gaussian's range -- the median's or the strongest
-// return's; a backward need not know which -- and the image buffer ends in ImgView::median_id; the backward's blend then treats
+// Bit 1 (LIDARGS_DEPTH=median, strongest or second at the forward): out_depth is one Gaussian's range -- the median's, the strongest
+// return's or the second return's; a backward need not know which -- and the image buffer ends in ImgView::median_id; the backward's blend then treats
 // dL/ddepth as zero and k_median_backward sends it to the one Gaussian each pixel names.  The two bits exclude each other
 // (lidargs_forward refuses both at once: that add is a float atomic), so the word is 0, 1 or 2.
 #define LG_TOTALS_MODE_WORD 4
@@ -268,11 +268,11 @@ struct ImgView {
     uint2* ranges;        // [tiles]
     float2* coltab;       // [W]  (cos beta, sin beta)
     float2* rowtab;       // [H]  (cos alpha, sin alpha) of pixel row y
-    uint32_t* median_id;  // [N] median and strongest modes only (behind everything else, as GeomView::acc64 is: the default buffer is byte for byte
-                          //     what it was): the Gaussian whose range the pixel returned, 0xFFFFFFFF = none (render.hip depth_pick_walk)
+    uint32_t* median_id;  // [N] median, strongest and second modes only (behind everything else, as GeomView::acc64 is: the default buffer is byte for byte
+                          //     what it was): the Gaussian whose range the pixel returned, 0xFFFFFFFF = none (render.hip depth_pick_walk, k_render_second)
 };
 
-// median: carve ImgView::median_id as well.  The forward asks for it only under LIDARGS_DEPTH=median / strongest; a backward always computes the
+// median: carve ImgView::median_id as well.  The forward asks for it only under LIDARGS_DEPTH=median / strongest / second; a backward always computes the
 // address (it does not know the mode) and hands it to a kernel that reads it only where the buffer's mode word says it is there.
 inline size_t img_carve(char* base, int W, int H, int tiles, ImgView* v, bool median = false) {
     Carver c(base);
@@ -343,7 +343,7 @@ void lane_stats_read(unsigned long long* out, int reset);              // render
 int api_fail(int code, const char* msg);
 int api_check_launch(hipStream_t s, int debug, const char* what);
 int refuse_deterministic(const char* entry);    // 0, or LIDARGS_ERR_INVALID_ARGUMENT (message set) when the switch is on: entry points the mode does not cover
-int refuse_depth_mode(const char* entry);       // the same for a non-default depth mode (LIDARGS_DEPTH=median, strongest)
+int refuse_depth_mode(const char* entry);       // the same for a non-default depth mode (LIDARGS_DEPTH=median, strongest, second)
 inline int refuse_modes(const char* entry) {    // both, in this order: what every entry point but lidargs_forward starts with
     if (const int rc = refuse_deterministic(entry)) return rc;
     return refuse_depth_mode(entry);
@@ -582,6 +582,10 @@ struct MedianFwdArgs {
     float* out_depth; uint32_t* median_id;
 };
 void launch_render_median(const MedianFwdArgs& a, bool strongest, hipStream_t s);   // k_render_median, or k_render_strongest
+// LIDARGS_DEPTH=second (the rule: switches.h second_depth_requested): k_render_second in the same frame and on the same two planes -- two
+// walks of the list in one launch, the strongest return s first, then from T = 1 the heaviest counting entry at least `gap` metres of
+// range (float32) away from s.  The backward does not know the rule: the buffers are median buffers.
+void launch_render_second(const MedianFwdArgs& a, float gap, hipStream_t s);
 struct MedianBwdArgs { const uint32_t* mode; const uint32_t* median_id; const float* dL_ddepth; float* gacc; size_t N; uint32_t P; };
 void launch_median_backward(const MedianBwdArgs& a, hipStream_t s);
 void launch_count_backward_entries(const RenderBwdArgs& a, unsigned long long* out, hipStream_t s);   // diagnostics: adds the list entries k_render_backward gathers to *out

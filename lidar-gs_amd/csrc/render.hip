@@ -314,7 +314,7 @@ __device__ __forceinline__ void walk_T_only_v2(const int cnt, const float4* s_re
 // compose) is T while the pixel is live and 0 once its walk has tripped here.
 // alpha of one parked entry (park_record / park_compact: r0 = s.xyz | B, r1, r2) for the pixel looking along (qxy, qz), `op` being the
 // entry's opacity on the pixel's row (0 outside its row span: the rect's row test); 0 where the pixel does not take the entry.  The
-// one text of the expression for the full walk below and the median / strongest walk (depth_pick_walk), which must take exactly the same entries.
+// one text of the expression for the full walk below and the median / strongest / second walks (depth_pick_walk, k_render_second), which must take exactly the same entries.
 __device__ __forceinline__ float entry_alpha(const float4& r0, const float4& r1, const float4& r2, const float op, const v2f qxy, const float qz) {
     const v2f exy = v2f{r0.x, r0.y} - qxy;
     const float ez = r0.z - qz;
@@ -1043,6 +1043,109 @@ void launch_render_median(const MedianFwdArgs& a, const bool strongest, hipStrea
     const dim3 grid((unsigned)a.grid.window_patches());
     if (strongest) hipLaunchKernelGGL(k_render_strongest, grid, dim3(64), 0, s, a);
     else hipLaunchKernelGGL(k_render_median, grid, dim3(64), 0, s, a);
+}
+
+// LIDARGS_DEPTH=second: the range of the pixel's second return (the rule: switches.h second_depth_requested), in the frame of
+// depth_pick_walk -- one wave64 per 16 x 4 patch, the list through LDS 64 records at a time, entry_alpha for membership and alpha, four
+// entries per exit test -- and on its two planes.  Two walks of the list in one launch:
+//   walk 1 is depth_pick_walk<true>'s, expression for expression: s = the strongest return (its range and Gaussian), left at T <= best;
+//   walk 2 starts again at the head of the list from T = 1, with the same T, stop and weight expressions (so every entry has the
+//     weight it had in walk 1).  A counting entry is a candidate if it is not s and |its range - s's range| >= gap (float32); the
+//     candidate with the largest weight wins, strict >: the nearer one among equal weights.  The pixel leaves at the blend's stop, at
+//     the end of the list, or at the first T <= best2: a later weight is alpha' T' <= 0.99 T < best2 (best2 = 0 while there is no
+//     candidate, and T >= 1e-4, so before the first candidate this cannot fire).  A pixel without s has no counting entry and never opens.
+// No candidate: range 0, id 0xFFFFFFFF.  Both chunk loops are bounded by the list length; their barriers sit on wave-uniform paths (the
+// workgroup is one wave and the loop conditions are ballots).
+__global__ void __launch_bounds__(64) k_render_second(const MedianFwdArgs a, const float gap) {
+    __shared__ float4 s_rec[4 * LG_CHUNK];
+    __shared__ float4 s_oprow[LG_CHUNK];
+    __shared__ uint32_t s_gid[LG_CHUNK];
+    const int lane = threadIdx.x;
+    const int wpt = a.grid.waves_per_tile;
+    const int patch = a.grid.global_patch(blockIdx.x);
+    const int tile = patch / wpt, sub = patch - tile * wpt;
+    const uint2 tr = a.ranges[tile];
+    const uint32_t n = tr.y - tr.x;
+    const PixelSetup px = pixel_setup(a.grid, a.coltab, a.rowtab, tile, sub, lane);
+    const int y0 = (tile / a.grid.tiles_x) * a.grid.TH + sub * LG_WAVE_ROWS;       // first pixel row of the patch
+    const float* oprow = reinterpret_cast<const float*>(s_oprow) + (lane >> 4);
+    const v2f qxy = v2f{px.q.x, px.q.y};
+    const uint32_t nchunks = (n + LG_CHUNK - 1) / LG_CHUNK;
+    // chunk c of the list into LDS, as depth_pick_walk stages it -> entries in it; the slots behind them hold zero records (alpha = 0)
+    auto stage = [&](const uint32_t c) -> int {
+        const uint32_t k = c * LG_CHUNK + (uint32_t)lane;
+        const bool have = k < n;
+        const uint32_t g = have ? a.point_list[tr.x + k] : 0u;
+        const Staged st = gather_record(a.rec, a.rowspan, g, have);
+        __syncthreads();
+        park_record(s_rec, lane, st);
+        s_oprow[lane] = rows_opacity(st.span, st.a3.y, y0);
+        s_gid[lane] = g;
+        __syncthreads();
+        return (int)min((uint32_t)LG_CHUNK, n - c * LG_CHUNK);
+    };
+
+    float T = 1.0f, best = 0.f, range_s = 0.f;                         // walk 1: the strongest return
+    uint32_t id_s = 0xFFFFFFFFu;
+    bool open = px.inside;
+    for (uint32_t c = 0; c < nchunks && __ballot(open) != 0ull; c++) {
+        const int cnt = stage(c);
+        for (int j = 0; j < cnt && __ballot(open) != 0ull; j += 4) {
+            float alpha[4], depth[4]; uint32_t gid[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                alpha[u] = entry_alpha(s_rec[j + u], s_rec[LG_CHUNK + j + u], s_rec[2 * LG_CHUNK + j + u], oprow[4 * (j + u)], qxy, px.q.z);
+                depth[u] = s_rec[3 * LG_CHUNK + j + u].x;
+                gid[u] = s_gid[j + u];
+            }
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const bool take = open && alpha[u] > 0.f;
+                const float test = T * (1.f - alpha[u]);
+                const bool counts = take && test >= 0.0001f;
+                const bool wins = counts && alpha[u] * T > best;
+                best = wins ? alpha[u] * T : best;
+                range_s = wins ? depth[u] : range_s;
+                id_s = wins ? gid[u] : id_s;
+                T = counts ? test : T;
+                open = open && (counts || !take) && T > best;
+            }
+        }
+    }
+
+    float best2 = 0.f, range = 0.f;                                    // walk 2: the heaviest candidate
+    uint32_t id = 0xFFFFFFFFu;
+    T = 1.0f;
+    open = px.inside && id_s != 0xFFFFFFFFu;
+    for (uint32_t c = 0; c < nchunks && __ballot(open) != 0ull; c++) {
+        const int cnt = stage(c);
+        for (int j = 0; j < cnt && __ballot(open) != 0ull; j += 4) {
+            float alpha[4], depth[4]; uint32_t gid[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                alpha[u] = entry_alpha(s_rec[j + u], s_rec[LG_CHUNK + j + u], s_rec[2 * LG_CHUNK + j + u], oprow[4 * (j + u)], qxy, px.q.z);
+                depth[u] = s_rec[3 * LG_CHUNK + j + u].x;
+                gid[u] = s_gid[j + u];
+            }
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const bool take = open && alpha[u] > 0.f;
+                const float test = T * (1.f - alpha[u]);
+                const bool counts = take && test >= 0.0001f;
+                const bool candidate = counts && gid[u] != id_s && fabsf(depth[u] - range_s) >= gap;
+                const bool wins = candidate && alpha[u] * T > best2;
+                best2 = wins ? alpha[u] * T : best2;
+                range = wins ? depth[u] : range;
+                id = wins ? gid[u] : id;
+                T = counts ? test : T;
+                open = open && (counts || !take) && T > best2;
+            }
+        }
+    }
+    if (px.inside) { a.out_depth[px.pix] = range; a.median_id[px.pix] = id; }
+}
+void launch_render_second(const MedianFwdArgs& a, const float gap, hipStream_t s) {
+    hipLaunchKernelGGL(k_render_second, dim3((unsigned)a.grid.window_patches()), dim3(64), 0, s, a, gap);
 }
 
 // ------------------------------------------------------------------------------------------------

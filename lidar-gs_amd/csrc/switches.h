@@ -84,8 +84,37 @@ inline bool median_depth_requested() { const char* e = getenv("LIDARGS_DEPTH"); 
 // largest blend weight alpha x T (render.hip k_render_strongest).  Its buffers are median buffers to every backward: the depth is one
 // Gaussian's, named in the same id plane.  Only the literal value `strongest`; read like `median`.
 inline bool strongest_depth_requested() { const char* e = getenv("LIDARGS_DEPTH"); return e && strcmp(e, "strongest") == 0; }
-// either of them: the depth of the next forward is one Gaussian's range, not the expected range (what the other entry points refuse)
-inline bool picked_depth_requested() { return median_depth_requested() || strongest_depth_requested(); }
+// LIDARGS_DEPTH=second: the third supported value -- the range of the pixel's SECOND return, what a LiDAR in multi-return mode reports
+// behind its strongest one (render.hip k_render_second).  THE RULE, stated here and in DESIGN 4d; everything else cites it.  Per pixel,
+// over its list in blend order, entries are taken and count exactly as under `strongest` (power <= 0, alpha = min(0.99, o exp(power))
+// >= 1/255; the entry at which T (1 - alpha) < 1e-4 ends the pixel and does not count), with the weight w = alpha T:
+//   1. s = the strongest return, picked bit for bit by the strongest rule: the largest w, the nearer entry among equal weights;
+//   2. the candidates are the counting entries j != s with |depths[j] - depths[s]| >= G, compared in float32 on the float32 ranges the
+//      records hold (a sensor cannot separate echoes closer than its pulse length; G = return_gap() below);
+//   3. the second return is the candidate with the largest w, the nearer one among equal weights: its range, its id in the id plane;
+//   4. no candidate (no taker, a single taker, every other taker inside the gap): range 0, id 0xFFFFFFFF, as a pixel without a taker.
+// With G = 0 this is the second-largest weight.  Its buffers are median buffers, like `strongest`'s.  Only the literal value `second`.
+inline bool second_depth_requested() { const char* e = getenv("LIDARGS_DEPTH"); return e && strcmp(e, "second") == 0; }
+// any of them: the depth of the next forward is one Gaussian's range, not the expected range (what the other entry points refuse)
+inline bool picked_depth_requested() { return median_depth_requested() || strongest_depth_requested() || second_depth_requested(); }
+// LIDARGS_RETURN_GAP = G of the rule above in metres, as a float32.  Read at every forward, by lidargs_forward only, and used only under
+// LIDARGS_DEPTH=second; it does not travel in the buffers (a backward does not know the rule).  Accepted if and only if the WHOLE string
+// matches [0-9]+(\.[0-9]*)?|\.[0-9]+ -- no sign, exponent or blank -- and its value, rounded to double and then to float32, is finite;
+// unset, empty or anything else: 0.  (diff_lidargs_rasterization.return_gap() is the same rule in Python.)
+inline float return_gap() {
+    const char* e = getenv("LIDARGS_RETURN_GAP");
+    if (!e) return 0.f;
+    const char* p = e;
+    size_t whole = 0, frac = 0;
+    while (*p >= '0' && *p <= '9') { p++; whole++; }
+    const bool dot = *p == '.';
+    if (dot) { p++; while (*p >= '0' && *p <= '9') { p++; frac++; } }
+    if (*p != 0 || (whole == 0 && !(dot && frac > 0))) return 0.f;
+    char* end = nullptr;
+    const double v = strtod(e, &end);
+    if (end != p || !(v < 0x1.ffffffp127)) return 0.f;    // (2^128 - 2^103: from there on the nearest float32 is infinity)
+    return (float)v;
+}
 // LIDARGS_NG_FORWARD_T16=0, LIDARGS_NG_BACKWARD_T16=0 (first character '0'): the decode's forward / backward on the 32x32x2 kernels, which
 // k = 8, 10 take in any case, instead of the 16x16x4 ones (A/B, test variants)
 inline bool ng_forward_t16_allowed() { return !env_starts_with("LIDARGS_NG_FORWARD_T16", '0'); }

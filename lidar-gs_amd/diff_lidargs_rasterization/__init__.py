@@ -15,23 +15,43 @@ The native side is lidar-gs_amd/csrc/*.hip behind the C ABI of include/lidargs_r
 """
 from typing import NamedTuple
 
+import math
 import os
+import re
+import struct
 
 import torch
 import torch.nn as nn
 
 from . import _C
 
-__all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "depth_mode"]
+__all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "depth_mode", "return_gap"]
 
 
 def depth_mode():
     """Which depth the next forward of this process returns: "median" (the range of the Gaussian at which the transmittance falls through
     one half; LIDARGS_DEPTH=median, read by the library at every lidargs_forward), "strongest" (the range of the Gaussian with the largest
-    blend weight alpha x T, a LiDAR's strongest return; LIDARGS_DEPTH=strongest) or "expected" (sum of range x alpha x T: unset, empty or
-    any other value).  The backward follows the forward that made its buffers, not the environment at its own time."""
+    blend weight alpha x T, a LiDAR's strongest return; LIDARGS_DEPTH=strongest), "second" (the range of its second return: the heaviest
+    entry at least return_gap() metres of range away from the strongest one, 0 where there is none; LIDARGS_DEPTH=second) or "expected"
+    (sum of range x alpha x T: unset, empty or any other value).  The backward follows the forward that made its buffers, not the
+    environment at its own time."""
     value = os.environ.get("LIDARGS_DEPTH")
-    return value if value in ("median", "strongest") else "expected"
+    return value if value in ("median", "strongest", "second") else "expected"
+
+
+def return_gap():
+    """The range gap G in metres that the next forward under LIDARGS_DEPTH=second puts between the strongest and the second return:
+    LIDARGS_RETURN_GAP, read by the library at every lidargs_forward and used in that mode only, by the rule of csrc/switches.h
+    return_gap() -- the whole string matches [0-9]+(\\.[0-9]*)?|\\.[0-9]+ (no sign, exponent or blank) and its value, rounded to double and
+    then to float32, is finite; unset, empty or anything else: 0.  -> the float32 value, as a float."""
+    value = os.environ.get("LIDARGS_RETURN_GAP")
+    if value is None or not re.fullmatch(r"[0-9]+(\.[0-9]*)?|\.[0-9]+", value):
+        return 0.0
+    try:
+        gap = struct.unpack("f", struct.pack("f", float(value)))[0]
+    except OverflowError:       # finite as a double, beyond float32
+        return 0.0
+    return gap if math.isfinite(gap) else 0.0
 
 
 class GaussianRasterizationSettings(NamedTuple):
