@@ -288,8 +288,8 @@ int refuse_deterministic(const char* entry) {
 // load on a default buffer).  The buffer's word decides every result, not this flag.
 std::atomic<bool> g_median_seen{false};
 int refuse_depth_mode(const char* entry) {
-    if (!picked_depth_requested()) return 0;
-    return fail(LIDARGS_ERR_INVALID_ARGUMENT, "%s: a non-default LIDARGS_DEPTH (median, strongest, second) is not supported by this entry point (only lidargs_forward / lidargs_backward are); unset it for this call", entry);
+    if (!picked(depth_mode())) return 0;
+    return fail(LIDARGS_ERR_INVALID_ARGUMENT, "%s: a non-default LIDARGS_DEPTH (" LG_PICKED_DEPTH_NAMES ") is not supported by this entry point (only lidargs_forward / lidargs_backward are); unset it for this call", entry);
 }
 int api_read_words_zero_behind(const uint32_t* dev, int n, uint32_t* out, void* zero, size_t zero_bytes, hipStream_t s) {
     hipError_t e = (hipError_t)read_words_begin(dev, n, s);
@@ -557,15 +557,17 @@ struct FrameMode {
     // lidargs_forward under LIDARGS_DETERMINISTIC=1: the geometry buffer is asked for with its 64-bit accumulator lines behind everything
     // else and its mode word set (lidargs_common.h LG_TOTALS_MODE_WORD); every backward on these buffers then adds up in fixed point.
     bool deterministic = false;
-    // lidargs_forward under LIDARGS_DEPTH=median or strongest -- the depth is one Gaussian's range: the image buffer is asked for with the
-    // median_id plane behind everything else, the mode word gets LG_MODE_MEDIAN, and k_render_median / k_render_strongest overwrites
-    // out_depth behind the blend (never together with `deterministic`).  `strongest` (only with `median`) picks the rule of that walk.
-    bool median = false, strongest = false;
-    // LIDARGS_DEPTH=second (only with `median`, never with `strongest`): k_render_second behind the blend instead, with `return_gap`
-    // (LIDARGS_RETURN_GAP, metres) among its arguments -- the forward's alone: the buffers are median buffers and do not carry it
-    bool second = false;
+    // lidargs_forward under a picked LIDARGS_DEPTH (switches.h DepthMode: anything but Expected) -- the depth is one Gaussian's range: the
+    // image buffer is asked for with the median_id plane behind everything else, the mode word gets LG_MODE_MEDIAN ("median buffers",
+    // whichever rule picked), and launch_render_picked overwrites out_depth behind the blend by the mode's rule (never together with
+    // `deterministic`).  `return_gap` (LIDARGS_RETURN_GAP, metres) is read by Second alone, and is the forward's alone: the buffers do not carry it.
+    lg::DepthMode depth = lg::DepthMode::Expected;
     float return_gap = 0.f;
 };
+// by lg::DepthMode: what launch_render_picked's launch is called in a stage check's error and in the profile (Expected has no such launch)
+const struct { const char* check; const char* mark; } PICKED_STAGE[] = {
+    {nullptr, nullptr}, {"render median", "render_median"}, {"render strongest", "render_strongest"}, {"render second", "render_second"}};
+static_assert(sizeof(PICKED_STAGE) / sizeof(PICKED_STAGE[0]) == lg::DEPTH_MODE_COUNT, "one stage per lg::DepthMode");
 
 // The preprocess' parameters of a whole frame on `grid`: no column wedge, full span records, pruning on, every row valid.  The forward,
 // the visible filter and the test hook (lidargs_debug_preprocess) all start from here, so the column steps are the same values for each.
@@ -607,7 +609,8 @@ int forward_impl(const FrameAllocs alloc, const SceneArgs sc, const FrameOutputs
 
     char* geom_p = alloc.geometry(alloc.geometry_user, lg::geom_carve(nullptr, (size_t)P, lg::GAUSS_BUFFERS, nullptr, mode.deterministic));
     if (!geom_p) return fail(LIDARGS_ERR_ALLOC, "geometry allocator returned NULL%s");
-    char* img_p = alloc.image(alloc.image_user, lg::img_carve(nullptr, width, height, grid4.num_tiles(), nullptr, mode.median));
+    const bool picked = lg::picked(mode.depth);
+    char* img_p = alloc.image(alloc.image_user, lg::img_carve(nullptr, width, height, grid4.num_tiles(), nullptr, picked));
     if (!img_p) return fail(LIDARGS_ERR_ALLOC, "image allocator returned NULL%s");
     lg::GeomView geom; lg::geom_carve(geom_p, (size_t)P, lg::GAUSS_BUFFERS, &geom);
     lg::ImgView img; lg::img_carve(img_p, width, height, grid4.num_tiles(), &img);
@@ -616,7 +619,7 @@ int forward_impl(const FrameAllocs alloc, const SceneArgs sc, const FrameOutputs
         lg::g_deterministic_seen.store(true, std::memory_order_relaxed);   // (before the buffer can reach any backward)
         LG_HIP(hipMemsetD32Async((hipDeviceptr_t)(geom.totals + LG_TOTALS_MODE_WORD), (int)lg::LG_MODE_DETERMINISTIC, 1, stream));   // (0 = the default, from the line above)
     }
-    if (mode.median) {
+    if (picked) {
         lg::g_median_seen.store(true, std::memory_order_relaxed);          // (before the buffer can reach any backward)
         LG_HIP(hipMemsetD32Async((hipDeviceptr_t)(geom.totals + LG_TOTALS_MODE_WORD), (int)lg::LG_MODE_MEDIAN, 1, stream));
     }
@@ -674,19 +677,13 @@ int forward_impl(const FrameAllocs alloc, const SceneArgs sc, const FrameOutputs
     LG_STAGE_CHECK("render combine");
     lg::prof_mark("render_combine", stream);
     }
-    if (mode.median) {   // behind either form of the blend: out_depth becomes the picked Gaussian's range, the image buffer's last plane names it
+    if (picked) {   // behind either form of the blend: out_depth becomes the picked Gaussian's range, the image buffer's last plane names it
         lg::MedianFwdArgs ma;
         ma.grid = L.grid; ma.ranges = img.ranges; ma.point_list = bin.val_a; ma.rec = geom.rec; ma.rowspan = geom.rowspan;
         ma.coltab = img.coltab; ma.rowtab = img.rowtab; ma.out_depth = out.out_depth; ma.median_id = img.median_id;
-        if (mode.second) {
-            lg::launch_render_second(ma, mode.return_gap, stream);
-            LG_STAGE_CHECK("render second");
-            lg::prof_mark("render_second", stream);
-        } else {
-        lg::launch_render_median(ma, mode.strongest, stream);
-        LG_STAGE_CHECK(mode.strongest ? "render strongest" : "render median");
-        lg::prof_mark(mode.strongest ? "render_strongest" : "render_median", stream);
-        }
+        lg::launch_render_picked(ma, mode.depth, mode.return_gap, stream);
+        LG_STAGE_CHECK(PICKED_STAGE[(int)mode.depth].check);
+        lg::prof_mark(PICKED_STAGE[(int)mode.depth].mark, stream);
     }
 
     // the selection a backward on these buffers will make (backward_impl starts from the same call): counted now, while the buffers are certainly alive
@@ -804,12 +801,10 @@ int lidargs_forward(lidargs_alloc_fn geometry_alloc, void* geometry_user, lidarg
     (void)D; (void)M; (void)shs; (void)projmatrix; (void)cam_pos; (void)prefiltered;
     FrameMode mode;
     mode.deterministic = lg::deterministic_requested();
-    mode.strongest = lg::strongest_depth_requested();
-    mode.second = lg::second_depth_requested();
-    mode.median = mode.strongest || mode.second || lg::median_depth_requested();
-    if (mode.second) mode.return_gap = lg::return_gap();
-    if (mode.deterministic && mode.median)   // (a picked Gaussian's depth gradient is added with a float atomic: not what the other switch promises)
-        return fail(LIDARGS_ERR_INVALID_ARGUMENT, "%s: a non-default LIDARGS_DEPTH (median, strongest, second) is not supported together with LIDARGS_DETERMINISTIC=1; unset one of them for this call", "lidargs_forward");
+    mode.depth = lg::depth_mode();
+    if (mode.depth == lg::DepthMode::Second) mode.return_gap = lg::return_gap();
+    if (mode.deterministic && lg::picked(mode.depth))   // (a picked Gaussian's depth gradient is added with a float atomic: not what the other switch promises)
+        return fail(LIDARGS_ERR_INVALID_ARGUMENT, "%s: a non-default LIDARGS_DEPTH (" LG_PICKED_DEPTH_NAMES ") is not supported together with LIDARGS_DETERMINISTIC=1; unset one of them for this call", "lidargs_forward");
     LG_FORWARD_ARGS(alloc, sc, out);
     return forward_impl(alloc, sc, out, mode, debug, (hipStream_t)stream);
 }

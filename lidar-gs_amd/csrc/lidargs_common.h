@@ -269,7 +269,7 @@ struct ImgView {
     float2* coltab;       // [W]  (cos beta, sin beta)
     float2* rowtab;       // [H]  (cos alpha, sin alpha) of pixel row y
     uint32_t* median_id;  // [N] median, strongest and second modes only (behind everything else, as GeomView::acc64 is: the default buffer is byte for byte
-                          //     what it was): the Gaussian whose range the pixel returned, 0xFFFFFFFF = none (render.hip depth_pick_walk, k_render_second)
+                          //     what it was): the Gaussian whose range the pixel returned, 0xFFFFFFFF = none (render.hip depth_store)
 };
 
 // median: carve ImgView::median_id as well.  The forward asks for it only under LIDARGS_DEPTH=median / strongest / second; a backward always computes the
@@ -569,23 +569,21 @@ struct RenderBwdArgs {
 // max |term| per (Gaussian, slot) in gacc, the second adds the terms up as 64-bit integers on the grid that maximum fixes (det_encode).
 void launch_render_backward(const RenderBwdArgs& a, hipStream_t s);
 
-// LIDARGS_DEPTH=median (DESIGN.md "Median-range depth").  Forward: behind the blend, one wave per 16 x 4 patch walks the tile's list from
-// T = 1 until every pixel's transmittance has fallen to one half, overwrites out_depth with the range of the last entry taken above one
-// half and names that Gaussian in median_id.  LIDARGS_DEPTH=strongest (`strongest` below): the same walk with the other rule -- the
-// entry with the largest blend weight alpha x T, until no pixel's T exceeds its best weight.  Backward, for both: dL_ddepth[pixel] is
-// added (weight 1) to the range slot of that Gaussian's packed line; a fixed small grid that retires on one load unless the buffer's
-// mode word has LG_MODE_MEDIAN.
+// A picked LIDARGS_DEPTH (switches.h DepthMode: Median, Strongest, Second; DESIGN.md "Median-range depth").  Forward: behind the blend,
+// one wave per 16 x 4 patch walks the tile's list from T = 1, overwrites out_depth with the range of the entry the mode's rule picks and
+// names that Gaussian in median_id (0, 0xFFFFFFFF where it picks none).  The rules are stated once, above render.hip's depth_walk:
+// Median -- the last entry taken above T = one half; Strongest -- the entry with the largest blend weight alpha x T; Second -- a second
+// walk in the same launch for the heaviest entry at least `gap` metres of range (float32) away from the strongest one.  One launcher
+// for all three (`gap` is read by Second alone; Expected launches nothing).  Backward, whichever rule picked: the buffers are "median
+// buffers" -- dL_ddepth[pixel] is added (weight 1) to the range slot of that Gaussian's packed line; a fixed small grid that retires on
+// one load unless the buffer's mode word has LG_MODE_MEDIAN.
 struct MedianFwdArgs {
     TileGrid grid;
     const uint2* ranges; const uint32_t* point_list; const float4* rec; const uint32_t* rowspan;
     const float2* coltab; const float2* rowtab;
     float* out_depth; uint32_t* median_id;
 };
-void launch_render_median(const MedianFwdArgs& a, bool strongest, hipStream_t s);   // k_render_median, or k_render_strongest
-// LIDARGS_DEPTH=second (the rule: switches.h second_depth_requested): k_render_second in the same frame and on the same two planes -- two
-// walks of the list in one launch, the strongest return s first, then from T = 1 the heaviest counting entry at least `gap` metres of
-// range (float32) away from s.  The backward does not know the rule: the buffers are median buffers.
-void launch_render_second(const MedianFwdArgs& a, float gap, hipStream_t s);
+void launch_render_picked(const MedianFwdArgs& a, DepthMode mode, float gap, hipStream_t s);   // k_render_median, k_render_strongest or k_render_second
 struct MedianBwdArgs { const uint32_t* mode; const uint32_t* median_id; const float* dL_ddepth; float* gacc; size_t N; uint32_t P; };
 void launch_median_backward(const MedianBwdArgs& a, hipStream_t s);
 void launch_count_backward_entries(const RenderBwdArgs& a, unsigned long long* out, hipStream_t s);   // diagnostics: adds the list entries k_render_backward gathers to *out

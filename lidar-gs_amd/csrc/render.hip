@@ -314,7 +314,7 @@ __device__ __forceinline__ void walk_T_only_v2(const int cnt, const float4* s_re
 // compose) is T while the pixel is live and 0 once its walk has tripped here.
 // alpha of one parked entry (park_record / park_compact: r0 = s.xyz | B, r1, r2) for the pixel looking along (qxy, qz), `op` being the
 // entry's opacity on the pixel's row (0 outside its row span: the rect's row test); 0 where the pixel does not take the entry.  The
-// one text of the expression for the full walk below and the median / strongest / second walks (depth_pick_walk, k_render_second), which must take exactly the same entries.
+// one text of the expression for the full walk below and the median / strongest / second walks (depth_walk), which must take exactly the same entries.
 __device__ __forceinline__ float entry_alpha(const float4& r0, const float4& r1, const float4& r2, const float op, const v2f qxy, const float qz) {
     const v2f exy = v2f{r0.x, r0.y} - qxy;
     const float ez = r0.z - qz;
@@ -958,194 +958,137 @@ void launch_render_combine(const RenderFwdArgs& a, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// LIDARGS_DEPTH=median / strongest: the range of ONE Gaussian per pixel, in a launch of its own behind the blend (whichever form that
-// took).  One wave64 per 16 x 4 patch walks its tile's list in list order from T = 1, 64 records at a time through LDS.  Per pixel, for
-// every entry it takes (entry_alpha: the full walk's membership, skips and alpha) --
-//   median:     if T > 0.5:  pick = the entry;      then  T *= 1 - alpha
+// LIDARGS_DEPTH=median / strongest / second (switches.h DepthMode): the range of ONE Gaussian per pixel, in a launch of its own behind
+// the blend (whichever form that took).  One wave64 per 16 x 4 patch walks its tile's list in list order from T = 1, 64 records at a
+// time through LDS (depth_walk).  Per pixel, for every entry it takes (entry_alpha: the full walk's membership, skips and alpha) --
+//   median (median_step):     if T > 0.5:  pick = the entry;      then  T *= 1 - alpha
 //     so the pixel ends with the entry at which T falls through one half -- or its last taker, if T never gets there.  The blend's
 //     T < 1e-4 stop cannot fire above one half (alpha <= 0.99 leaves T >= 0.005), so above one half this walk and the blend's see the
 //     same T.  The pixel leaves at T <= 0.5.
-//   strongest:  test = T (1 - alpha);  if test < 1e-4 the pixel ends and this entry does not count (the blend's stop, its expression);
-//     otherwise  w = alpha T (the blend's weight);  if w > best (strict: among equal weights the nearer entry stays):  best = w,
-//     pick = the entry;      then  T = test
+//   strongest (heaviest_step, every entry eligible):  test = T (1 - alpha);  if test < 1e-4 the pixel ends and this entry does not count
+//     (the blend's stop, its expression); otherwise  w = alpha T (the blend's weight);  if w > best (strict: among equal weights the
+//     nearer entry stays):  best = w, pick = the entry;      then  T = test
 //     so the pixel ends with its strongest return.  It leaves at T <= best: a later weight is alpha' T' <= 0.99 T < best.
-// No taker: range 0, id 0xFFFFFFFF.  A plain serial walk on purpose: it leaves when every pixel of the patch has left, which on
-// saturating frames is a few entries in; the blend kernels are not touched.
-template <bool STRONGEST>
-__device__ __forceinline__ void depth_pick_walk(const MedianFwdArgs& a) {
+//   second (the rule: switches.h DepthMode::Second): two walks of the list in one launch.  Walk 1 is the strongest walk:
+//     s = the strongest return (its range and Gaussian).  Walk 2 starts again at the head of the list from T = 1 with the same step
+//     (so every entry has the weight it had in walk 1), but an entry is eligible only as a candidate: it is not s and |its range - s's
+//     range| >= gap (float32).  The candidate with the largest weight wins, strict >: the nearer one among equal weights.  The pixel
+//     leaves at the blend's stop, at the end of the list, or at the first T <= best: a later weight is alpha' T' <= 0.99 T < best (best
+//     = 0 while there is no candidate, and T >= 1e-4, so before the first candidate this cannot fire).  A pixel without s has no
+//     counting entry and never opens.
+// No taker, no candidate: range 0, id 0xFFFFFFFF.  A plain serial walk on purpose: it leaves when every pixel of the patch has left,
+// which on saturating frames is a few entries in; the blend kernels are not touched.
+struct DepthPick {                                                     // one pixel's state in a walk
+    float T = 1.0f, range = 0.f;
+    float best = 0.f;                                                  // (heaviest_step only) the largest eligible weight so far
+    uint32_t id = 0xFFFFFFFFu;
+};
+// -> the pixel stays open (median: T > 0.5)
+__device__ __forceinline__ bool median_step(DepthPick& p, const bool take, const float alpha, const float depth, const uint32_t gid) {
+    p.range = take ? depth : p.range;
+    p.id = take ? gid : p.id;
+    p.T = take ? p.T * (1.f - alpha) : p.T;
+    return p.T > 0.5f;
+}
+// -> the pixel stays open (T > best and not stopped: an entry behind can still be the pick)
+__device__ __forceinline__ bool heaviest_step(DepthPick& p, const bool take, const float alpha, const float depth, const uint32_t gid, const bool eligible) {
+    const float test = p.T * (1.f - alpha);
+    const bool counts = take && test >= 0.0001f;
+    const bool wins = counts && eligible && alpha * p.T > p.best;
+    p.best = wins ? alpha * p.T : p.best;
+    p.range = wins ? depth : p.range;
+    p.id = wins ? gid : p.id;
+    p.T = counts ? test : p.T;
+    return (counts || !take) && p.T > p.best;
+}
+// the workgroup's patch: its tile's list, its pixels, its first pixel row, and the LDS one chunk of the list is staged in (every walk of a launch uses the same)
+struct DepthPatch { uint2 tr; uint32_t n; PixelSetup px; int y0; float4* s_rec; float4* s_oprow; uint32_t* s_gid; };
+__device__ __forceinline__ DepthPatch depth_patch(const MedianFwdArgs& a) {
+    // (static LDS of whichever kernel this is inlined into: each of the three calls it once, so each has these 5376 B once)
     __shared__ float4 s_rec[4 * LG_CHUNK];
     __shared__ float4 s_oprow[LG_CHUNK];
     __shared__ uint32_t s_gid[LG_CHUNK];
-    const int lane = threadIdx.x;
     const int wpt = a.grid.waves_per_tile;
     const int patch = a.grid.global_patch(blockIdx.x);
     const int tile = patch / wpt, sub = patch - tile * wpt;
-    const uint2 tr = a.ranges[tile];
-    const uint32_t n = tr.y - tr.x;
-    const PixelSetup px = pixel_setup(a.grid, a.coltab, a.rowtab, tile, sub, lane);
-    const int y0 = (tile / a.grid.tiles_x) * a.grid.TH + sub * LG_WAVE_ROWS;       // first pixel row of the patch
+    DepthPatch f;
+    f.tr = a.ranges[tile];
+    f.n = f.tr.y - f.tr.x;
+    f.px = pixel_setup(a.grid, a.coltab, a.rowtab, tile, sub, (int)threadIdx.x);
+    f.y0 = (tile / a.grid.tiles_x) * a.grid.TH + sub * LG_WAVE_ROWS;
+    f.s_rec = s_rec; f.s_oprow = s_oprow; f.s_gid = s_gid;
+    return f;
+}
+// One walk of the patch's list: step(take, alpha, range, id) -> `the pixel stays open` for every entry, in list order, while any pixel
+// of the patch is open.  Both loops are bounded by the list length; the barriers sit on wave-uniform paths (the workgroup is one wave
+// and the loop conditions are ballots).
+template <typename Step>
+__device__ __forceinline__ void depth_walk(const MedianFwdArgs& a, const DepthPatch& f, bool open, Step step) {
+    float4* const s_rec = f.s_rec; float4* const s_oprow = f.s_oprow; uint32_t* const s_gid = f.s_gid;
+    const int lane = threadIdx.x;
     const float* oprow = reinterpret_cast<const float*>(s_oprow) + (lane >> 4);
-    const v2f qxy = v2f{px.q.x, px.q.y};
-
-    float T = 1.0f, range = 0.f;
-    float best = 0.f;                                                  // (strongest only) the largest weight so far
-    uint32_t id = 0xFFFFFFFFu;
-    bool open = px.inside;                                             // median: T > 0.5; strongest: T > best and not stopped -- an entry behind can still be the pick
-    const uint32_t nchunks = (n + LG_CHUNK - 1) / LG_CHUNK;
-    for (uint32_t c = 0; c < nchunks && __ballot(open) != 0ull; c++) { // (wave-uniform: the workgroup is one wave)
+    const v2f qxy = v2f{f.px.q.x, f.px.q.y};
+    const uint32_t nchunks = (f.n + LG_CHUNK - 1) / LG_CHUNK;
+    for (uint32_t c = 0; c < nchunks && __ballot(open) != 0ull; c++) {
+        // chunk c of the list into LDS; the slots behind its cnt entries hold zero records (alpha = 0)
         const uint32_t k = c * LG_CHUNK + (uint32_t)lane;
-        const bool have = k < n;
-        const uint32_t g = have ? a.point_list[tr.x + k] : 0u;
+        const bool have = k < f.n;
+        const uint32_t g = have ? a.point_list[f.tr.x + k] : 0u;
         const Staged st = gather_record(a.rec, a.rowspan, g, have);
         __syncthreads();
         park_record(s_rec, lane, st);
-        s_oprow[lane] = rows_opacity(st.span, st.a3.y, y0);
+        s_oprow[lane] = rows_opacity(st.span, st.a3.y, f.y0);
         s_gid[lane] = g;
         __syncthreads();
-        const int cnt = (int)min((uint32_t)LG_CHUNK, n - c * LG_CHUNK);
+        const int cnt = (int)min((uint32_t)LG_CHUNK, f.n - c * LG_CHUNK);
         // Four entries per exit test: their LDS reads and alphas do not depend on the pixel's state and are in flight together, the four
         // updates behind them are a few selects each.  A pixel that has left ignores every later entry (`take` asks `open`), so WHEN the
-        // wave leaves changes no result; the slots in [cnt, 64) hold this chunk's zero records (alpha = 0), so a last group may reach over cnt.
+        // wave leaves changes no result; a last group may reach over cnt into the zero records.
         for (int j = 0; j < cnt && __ballot(open) != 0ull; j += 4) {
             float alpha[4], depth[4]; uint32_t gid[4];
 #pragma unroll
             for (int u = 0; u < 4; u++) {
-                alpha[u] = entry_alpha(s_rec[j + u], s_rec[LG_CHUNK + j + u], s_rec[2 * LG_CHUNK + j + u], oprow[4 * (j + u)], qxy, px.q.z);
+                alpha[u] = entry_alpha(s_rec[j + u], s_rec[LG_CHUNK + j + u], s_rec[2 * LG_CHUNK + j + u], oprow[4 * (j + u)], qxy, f.px.q.z);
                 depth[u] = s_rec[3 * LG_CHUNK + j + u].x;
                 gid[u] = s_gid[j + u];
             }
 #pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const bool take = open && alpha[u] > 0.f;
-                if (STRONGEST) {
-                    const float test = T * (1.f - alpha[u]);
-                    const bool counts = take && test >= 0.0001f;
-                    const bool wins = counts && alpha[u] * T > best;
-                    best = wins ? alpha[u] * T : best;
-                    range = wins ? depth[u] : range;
-                    id = wins ? gid[u] : id;
-                    T = counts ? test : T;
-                    open = open && (counts || !take) && T > best;
-                } else {
-                    range = take ? depth[u] : range;
-                    id = take ? gid[u] : id;
-                    T = take ? T * (1.f - alpha[u]) : T;
-                    open = open && T > 0.5f;
-                }
+            for (int u = 0; u < 4; u++) {                              // (the step runs for a pixel that has left too, as selects: no branch)
+                const bool stays = step(open && alpha[u] > 0.f, alpha[u], depth[u], gid[u]);
+                open = open && stays;
             }
         }
     }
-    if (px.inside) { a.out_depth[px.pix] = range; a.median_id[px.pix] = id; }
 }
-__global__ void __launch_bounds__(64) k_render_median(const MedianFwdArgs a) { depth_pick_walk<false>(a); }
-__global__ void __launch_bounds__(64) k_render_strongest(const MedianFwdArgs a) { depth_pick_walk<true>(a); }
-void launch_render_median(const MedianFwdArgs& a, const bool strongest, hipStream_t s) {
-    const dim3 grid((unsigned)a.grid.window_patches());
-    if (strongest) hipLaunchKernelGGL(k_render_strongest, grid, dim3(64), 0, s, a);
-    else hipLaunchKernelGGL(k_render_median, grid, dim3(64), 0, s, a);
+__device__ __forceinline__ void depth_store(const MedianFwdArgs& a, const DepthPatch& f, const DepthPick& p) {
+    if (f.px.inside) { a.out_depth[f.px.pix] = p.range; a.median_id[f.px.pix] = p.id; }
 }
-
-// LIDARGS_DEPTH=second: the range of the pixel's second return (the rule: switches.h second_depth_requested), in the frame of
-// depth_pick_walk -- one wave64 per 16 x 4 patch, the list through LDS 64 records at a time, entry_alpha for membership and alpha, four
-// entries per exit test -- and on its two planes.  Two walks of the list in one launch:
-//   walk 1 is depth_pick_walk<true>'s, expression for expression: s = the strongest return (its range and Gaussian), left at T <= best;
-//   walk 2 starts again at the head of the list from T = 1, with the same T, stop and weight expressions (so every entry has the
-//     weight it had in walk 1).  A counting entry is a candidate if it is not s and |its range - s's range| >= gap (float32); the
-//     candidate with the largest weight wins, strict >: the nearer one among equal weights.  The pixel leaves at the blend's stop, at
-//     the end of the list, or at the first T <= best2: a later weight is alpha' T' <= 0.99 T < best2 (best2 = 0 while there is no
-//     candidate, and T >= 1e-4, so before the first candidate this cannot fire).  A pixel without s has no counting entry and never opens.
-// No candidate: range 0, id 0xFFFFFFFF.  Both chunk loops are bounded by the list length; their barriers sit on wave-uniform paths (the
-// workgroup is one wave and the loop conditions are ballots).
+__global__ void __launch_bounds__(64) k_render_median(const MedianFwdArgs a) {
+    const DepthPatch f = depth_patch(a);
+    DepthPick p;
+    depth_walk(a, f, f.px.inside, [&](bool take, float alpha, float depth, uint32_t gid) { return median_step(p, take, alpha, depth, gid); });
+    depth_store(a, f, p);
+}
+__global__ void __launch_bounds__(64) k_render_strongest(const MedianFwdArgs a) {
+    const DepthPatch f = depth_patch(a);
+    DepthPick p;
+    depth_walk(a, f, f.px.inside, [&](bool take, float alpha, float depth, uint32_t gid) { return heaviest_step(p, take, alpha, depth, gid, true); });
+    depth_store(a, f, p);
+}
 __global__ void __launch_bounds__(64) k_render_second(const MedianFwdArgs a, const float gap) {
-    __shared__ float4 s_rec[4 * LG_CHUNK];
-    __shared__ float4 s_oprow[LG_CHUNK];
-    __shared__ uint32_t s_gid[LG_CHUNK];
-    const int lane = threadIdx.x;
-    const int wpt = a.grid.waves_per_tile;
-    const int patch = a.grid.global_patch(blockIdx.x);
-    const int tile = patch / wpt, sub = patch - tile * wpt;
-    const uint2 tr = a.ranges[tile];
-    const uint32_t n = tr.y - tr.x;
-    const PixelSetup px = pixel_setup(a.grid, a.coltab, a.rowtab, tile, sub, lane);
-    const int y0 = (tile / a.grid.tiles_x) * a.grid.TH + sub * LG_WAVE_ROWS;       // first pixel row of the patch
-    const float* oprow = reinterpret_cast<const float*>(s_oprow) + (lane >> 4);
-    const v2f qxy = v2f{px.q.x, px.q.y};
-    const uint32_t nchunks = (n + LG_CHUNK - 1) / LG_CHUNK;
-    // chunk c of the list into LDS, as depth_pick_walk stages it -> entries in it; the slots behind them hold zero records (alpha = 0)
-    auto stage = [&](const uint32_t c) -> int {
-        const uint32_t k = c * LG_CHUNK + (uint32_t)lane;
-        const bool have = k < n;
-        const uint32_t g = have ? a.point_list[tr.x + k] : 0u;
-        const Staged st = gather_record(a.rec, a.rowspan, g, have);
-        __syncthreads();
-        park_record(s_rec, lane, st);
-        s_oprow[lane] = rows_opacity(st.span, st.a3.y, y0);
-        s_gid[lane] = g;
-        __syncthreads();
-        return (int)min((uint32_t)LG_CHUNK, n - c * LG_CHUNK);
-    };
-
-    float T = 1.0f, best = 0.f, range_s = 0.f;                         // walk 1: the strongest return
-    uint32_t id_s = 0xFFFFFFFFu;
-    bool open = px.inside;
-    for (uint32_t c = 0; c < nchunks && __ballot(open) != 0ull; c++) {
-        const int cnt = stage(c);
-        for (int j = 0; j < cnt && __ballot(open) != 0ull; j += 4) {
-            float alpha[4], depth[4]; uint32_t gid[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                alpha[u] = entry_alpha(s_rec[j + u], s_rec[LG_CHUNK + j + u], s_rec[2 * LG_CHUNK + j + u], oprow[4 * (j + u)], qxy, px.q.z);
-                depth[u] = s_rec[3 * LG_CHUNK + j + u].x;
-                gid[u] = s_gid[j + u];
-            }
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const bool take = open && alpha[u] > 0.f;
-                const float test = T * (1.f - alpha[u]);
-                const bool counts = take && test >= 0.0001f;
-                const bool wins = counts && alpha[u] * T > best;
-                best = wins ? alpha[u] * T : best;
-                range_s = wins ? depth[u] : range_s;
-                id_s = wins ? gid[u] : id_s;
-                T = counts ? test : T;
-                open = open && (counts || !take) && T > best;
-            }
-        }
-    }
-
-    float best2 = 0.f, range = 0.f;                                    // walk 2: the heaviest candidate
-    uint32_t id = 0xFFFFFFFFu;
-    T = 1.0f;
-    open = px.inside && id_s != 0xFFFFFFFFu;
-    for (uint32_t c = 0; c < nchunks && __ballot(open) != 0ull; c++) {
-        const int cnt = stage(c);
-        for (int j = 0; j < cnt && __ballot(open) != 0ull; j += 4) {
-            float alpha[4], depth[4]; uint32_t gid[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                alpha[u] = entry_alpha(s_rec[j + u], s_rec[LG_CHUNK + j + u], s_rec[2 * LG_CHUNK + j + u], oprow[4 * (j + u)], qxy, px.q.z);
-                depth[u] = s_rec[3 * LG_CHUNK + j + u].x;
-                gid[u] = s_gid[j + u];
-            }
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const bool take = open && alpha[u] > 0.f;
-                const float test = T * (1.f - alpha[u]);
-                const bool counts = take && test >= 0.0001f;
-                const bool candidate = counts && gid[u] != id_s && fabsf(depth[u] - range_s) >= gap;
-                const bool wins = candidate && alpha[u] * T > best2;
-                best2 = wins ? alpha[u] * T : best2;
-                range = wins ? depth[u] : range;
-                id = wins ? gid[u] : id;
-                T = counts ? test : T;
-                open = open && (counts || !take) && T > best2;
-            }
-        }
-    }
-    if (px.inside) { a.out_depth[px.pix] = range; a.median_id[px.pix] = id; }
+    const DepthPatch f = depth_patch(a);
+    DepthPick s, p;                                                    // walk 1: the strongest return; walk 2: the heaviest candidate
+    depth_walk(a, f, f.px.inside, [&](bool take, float alpha, float depth, uint32_t gid) { return heaviest_step(s, take, alpha, depth, gid, true); });
+    depth_walk(a, f, f.px.inside && s.id != 0xFFFFFFFFu, [&](bool take, float alpha, float depth, uint32_t gid) {
+        return heaviest_step(p, take, alpha, depth, gid, gid != s.id && fabsf(depth - s.range) >= gap);
+    });
+    depth_store(a, f, p);
 }
-void launch_render_second(const MedianFwdArgs& a, const float gap, hipStream_t s) {
-    hipLaunchKernelGGL(k_render_second, dim3((unsigned)a.grid.window_patches()), dim3(64), 0, s, a, gap);
+void launch_render_picked(const MedianFwdArgs& a, const DepthMode mode, const float gap, hipStream_t s) {
+    const dim3 grid((unsigned)a.grid.window_patches());
+    if (mode == DepthMode::Second) hipLaunchKernelGGL(k_render_second, grid, dim3(64), 0, s, a, gap);
+    else if (mode == DepthMode::Strongest) hipLaunchKernelGGL(k_render_strongest, grid, dim3(64), 0, s, a);
+    else if (mode == DepthMode::Median) hipLaunchKernelGGL(k_render_median, grid, dim3(64), 0, s, a);
 }
 
 // ------------------------------------------------------------------------------------------------

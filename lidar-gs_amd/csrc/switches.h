@@ -75,28 +75,52 @@ inline bool uses_small_sort(size_t n) { return n <= switches().small_sort_max &&
 // function of its inputs (lidargs_common.h "deterministic accumulation").  Read at EVERY call (a caller may flip it between two frames of
 // one process), and by forward entry points only: a backward takes the mode from the buffers.  Unset, empty, 0: off.
 inline bool deterministic_requested() { return env_on("LIDARGS_DETERMINISTIC"); }
-// LIDARGS_DEPTH=median: a supported mode -- lidargs_forward returns the median range per pixel (the range of the Gaussian at which the
-// transmittance falls through one half: render.hip k_render_median) instead of the expected range, and makes buffers on which every
-// lidargs_backward sends a pixel's depth gradient to that one Gaussian.  Read at EVERY call, by forward entry points only (the mode
-// travels in the buffers, like the deterministic one).  Only the literal value `median` turns it on: unset, empty, anything else = expected.
-inline bool median_depth_requested() { const char* e = getenv("LIDARGS_DEPTH"); return e && strcmp(e, "median") == 0; }
-// LIDARGS_DEPTH=strongest: the other supported value of the same switch -- the range of the pixel's strongest return, the entry with the
-// largest blend weight alpha x T (render.hip k_render_strongest).  Its buffers are median buffers to every backward: the depth is one
-// Gaussian's, named in the same id plane.  Only the literal value `strongest`; read like `median`.
-inline bool strongest_depth_requested() { const char* e = getenv("LIDARGS_DEPTH"); return e && strcmp(e, "strongest") == 0; }
-// LIDARGS_DEPTH=second: the third supported value -- the range of the pixel's SECOND return, what a LiDAR in multi-return mode reports
-// behind its strongest one (render.hip k_render_second).  THE RULE, stated here and in DESIGN 4d; everything else cites it.  Per pixel,
-// over its list in blend order, entries are taken and count exactly as under `strongest` (power <= 0, alpha = min(0.99, o exp(power))
-// >= 1/255; the entry at which T (1 - alpha) < 1e-4 ends the pixel and does not count), with the weight w = alpha T:
-//   1. s = the strongest return, picked bit for bit by the strongest rule: the largest w, the nearer entry among equal weights;
-//   2. the candidates are the counting entries j != s with |depths[j] - depths[s]| >= G, compared in float32 on the float32 ranges the
-//      records hold (a sensor cannot separate echoes closer than its pulse length; G = return_gap() below);
-//   3. the second return is the candidate with the largest w, the nearer one among equal weights: its range, its id in the id plane;
-//   4. no candidate (no taker, a single taker, every other taker inside the gap): range 0, id 0xFFFFFFFF, as a pixel without a taker.
-// With G = 0 this is the second-largest weight.  Its buffers are median buffers, like `strongest`'s.  Only the literal value `second`.
-inline bool second_depth_requested() { const char* e = getenv("LIDARGS_DEPTH"); return e && strcmp(e, "second") == 0; }
-// any of them: the depth of the next forward is one Gaussian's range, not the expected range (what the other entry points refuse)
-inline bool picked_depth_requested() { return median_depth_requested() || strongest_depth_requested() || second_depth_requested(); }
+// LIDARGS_DEPTH: which depth lidargs_forward returns.  Read at EVERY call, by forward entry points only (the mode travels in the buffers,
+// like the deterministic one).  Only the literal names of the table below select a mode: unset, empty, anything else = Expected.
+enum class DepthMode {
+    // the expected range, sum of range x alpha x T: the default
+    Expected,
+    // LIDARGS_DEPTH=median: a supported mode -- lidargs_forward returns the median range per pixel (the range of the Gaussian at which the
+    // transmittance falls through one half: render.hip k_render_median) instead of the expected range, and makes buffers on which every
+    // lidargs_backward sends a pixel's depth gradient to that one Gaussian ("median buffers").
+    Median,
+    // LIDARGS_DEPTH=strongest: the other supported value of the same switch -- the range of the pixel's strongest return, the entry with the
+    // largest blend weight alpha x T (render.hip k_render_strongest).  Its buffers are median buffers to every backward: the depth is one
+    // Gaussian's, named in the same id plane.
+    Strongest,
+    // LIDARGS_DEPTH=second: the third supported value -- the range of the pixel's SECOND return, what a LiDAR in multi-return mode reports
+    // behind its strongest one (render.hip k_render_second).  THE RULE, stated here and in DESIGN 4d; everything else cites it.  Per pixel,
+    // over its list in blend order, entries are taken and count exactly as under `strongest` (power <= 0, alpha = min(0.99, o exp(power))
+    // >= 1/255; the entry at which T (1 - alpha) < 1e-4 ends the pixel and does not count), with the weight w = alpha T:
+    //   1. s = the strongest return, picked bit for bit by the strongest rule: the largest w, the nearer entry among equal weights;
+    //   2. the candidates are the counting entries j != s with |depths[j] - depths[s]| >= G, compared in float32 on the float32 ranges the
+    //      records hold (a sensor cannot separate echoes closer than its pulse length; G = return_gap() below);
+    //   3. the second return is the candidate with the largest w, the nearer one among equal weights: its range, its id in the id plane;
+    //   4. no candidate (no taker, a single taker, every other taker inside the gap): range 0, id 0xFFFFFFFF, as a pixel without a taker.
+    // With G = 0 this is the second-largest weight.  Its buffers are median buffers, like `strongest`'s.
+    Second
+};
+// The values' names, by value: the only place of csrc/ that spells them (diff_lidargs_rasterization.depth_mode() is the same table in
+// Python), and the picked ones as the error messages list them.
+constexpr int DEPTH_MODE_COUNT = (int)DepthMode::Second + 1;             // what every table indexed by a DepthMode is checked against
+constexpr const char* DEPTH_MODE_NAMES[] = {"expected", "median", "strongest", "second"};
+static_assert(sizeof(DEPTH_MODE_NAMES) / sizeof(DEPTH_MODE_NAMES[0]) == DEPTH_MODE_COUNT, "one name per DepthMode");
+#define LG_PICKED_DEPTH_NAMES "median, strongest, second"
+constexpr bool lists_the_picked_names(const char* list) {
+    for (int i = 1; i < DEPTH_MODE_COUNT; i++) {
+        for (const char* n = DEPTH_MODE_NAMES[i]; *n;) if (*list++ != *n++) return false;
+        if (i < DEPTH_MODE_COUNT - 1 && (*list++ != ',' || *list++ != ' ')) return false;
+    }
+    return *list == 0;
+}
+static_assert(lists_the_picked_names(LG_PICKED_DEPTH_NAMES), "LG_PICKED_DEPTH_NAMES is every name but the first, joined by \", \"");
+inline DepthMode depth_mode() {
+    const char* e = getenv("LIDARGS_DEPTH");
+    for (int i = 1; e && i < DEPTH_MODE_COUNT; i++) if (strcmp(e, DEPTH_MODE_NAMES[i]) == 0) return (DepthMode)i;
+    return DepthMode::Expected;
+}
+// any of them but Expected: the depth of a forward is one Gaussian's range, not the expected range (what the other entry points refuse)
+inline bool picked(DepthMode m) { return m != DepthMode::Expected; }
 // LIDARGS_RETURN_GAP = G of the rule above in metres, as a float32.  Read at every forward, by lidargs_forward only, and used only under
 // LIDARGS_DEPTH=second; it does not travel in the buffers (a backward does not know the rule).  Accepted if and only if the WHOLE string
 // matches [0-9]+(\.[0-9]*)?|\.[0-9]+ -- no sign, exponent or blank -- and its value, rounded to double and then to float32, is finite;

@@ -36,7 +36,7 @@ def depth_mode():
     (sum of range x alpha x T: unset, empty or any other value).  The backward follows the forward that made its buffers, not the
     environment at its own time."""
     value = os.environ.get("LIDARGS_DEPTH")
-    return value if value in ("median", "strongest", "second") else "expected"
+    return value if value in ("median", "strongest", "second") else "expected"      # (the names of csrc/switches.h DepthMode: DEPTH_MODE_NAMES)
 
 
 def return_gap():

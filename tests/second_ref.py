@@ -1,6 +1,6 @@
-"""LIDARGS_DEPTH=second restated (csrc/switches.h second_depth_requested): the second-return rule on top of
-tests/strongest_ref.py's blend table, and a float64 torch forward whose depth output is depth[second_id], so that torch.autograd gives
-the mode's reference gradients.  The lists, the table, the float64 helpers and the scenes are strongest_ref's; the pick is written here.
+"""LIDARGS_DEPTH=second restated (csrc/switches.h DepthMode::Second): the second-return rule on top of
+tests/strongest_ref.py's blend table, as a RULE (`rule(gap)`) for depth_modes.reference -- the float64 torch forward whose depth
+output is depth[second_id] -- and the hand-placed rays of the second-return tests with their worked-out answers.
 
 The rule.  Entries are taken and count as under `strongest` (strongest_ref.blend: `taken`, weight w = alpha T).  Per pixel:
     1. s = the strongest return: the largest w, the nearer entry among equal weights (the table's `pos`);
@@ -15,18 +15,20 @@ Undecided pixels give no vote in a comparison and get a zero upstream depth grad
   * the runner-up candidate's weight is >= (1 - TIE) x the second's, or
   * some counting entry other than s has ||depth_j - depth_s| - G| <= EDGE metres (it falls inside or outside the gap by rounding).
 """
+import types
+
 import numpy as np
 import torch
 
+import depth_modes as dm
 import median_ref as mr
-import preprocess_ref as pr
 import strongest_ref as sr
-from median_ref import F64, H, SIGMA, OFF, THIN_N, THIN_OP, _t, pixel_lists
+from depth_modes import F64, H
+from median_ref import SIGMA, OFF, THIN_N, THIN_OP
 
 TIE = sr.TIE                   # 1e-3
 EDGE = 1e-3                    # metres
 CAP = sr.CAP                   # undecided pixels / pixels with a taker, at most, on every scene and gap used (asserted on the CPU)
-GRAD_KEYS = mr.GRAD_KEYS
 GAPS = (None, 0.505)           # LIDARGS_RETURN_GAP of the tests: unset (0) and a gap between the 1-cm layers of the hand-placed rays
 PLACED_GAPS = GAPS + (2.005,)
 
@@ -72,9 +74,20 @@ def restate(f, rs, gap):
                 decided=decided.reshape(shape), has_taker=rs["has_taker"], strongest_id=rs["strongest_id"], pick=p, table=t)
 
 
-def undecided_fraction(r):
-    """Undecided pixels as a fraction of the pixels that have a taker."""
-    return float((~r["decided"] & r["has_taker"]).sum()) / max(1, int(r["has_taker"].sum()))
+def chosen(r, dist, gap):
+    """The float64 chain's own pick, on the weights of its table `r` (strongest_ref.blend) and its ranges `dist`."""
+    t = r["table"]
+    I = t["idx"]
+    p = pick(t["weight"].numpy(), t["taken"].numpy(), t["pos"].numpy(), dist.detach().numpy()[I.numpy()], gap_value(gap))
+    has = torch.as_tensor(p["has"])
+    picked = I[torch.arange(I.shape[0]), torch.as_tensor(p["pos2"])]
+    return torch.where(has, picked, torch.full_like(picked, -1)), torch.where(has, dist[picked], torch.zeros(I.shape[0], dtype=F64))
+
+
+def rule(gap):
+    """The RULE at `gap` metres (None: unset)."""
+    return types.SimpleNamespace(blend=sr.blend, restate=lambda f, scene, W, H: restate(f, sr.restate(f, scene, W, H), gap), id_key="second_id",
+                                 chosen=lambda r, dist: chosen(r, dist, gap))
 
 
 def exit_positions(r):
@@ -93,57 +106,6 @@ def exit_positions(r):
     return first[has], behind[has], best2[np.arange(wc.shape[0]), first][has], p["pos2"][has]
 
 
-def reference(scene, W, H, grads, gap, f=None):
-    """The float64 reference of a second-mode forward + backward, built as strongest_ref.reference is: K1's formulas in front of
-    strongest_ref.blend, the depth output being the range of the entry this file's rule picks, upstream gradients `grads` = (dL_dcolor
-    [2,H,W], dL_ddepth [1,H,W], dL_docc [1,H,W]) with dL_ddepth zeroed on undecided pixels.  -> dict: the restatement's planes
-    (restate), `fwd`, `depth`, `dL_ddepth_masked` and the six gradient arrays (util.GRAD_KEYS_SR)."""
-    from oracle import lgo
-    if f is None:
-        f = lgo.forward(scene["means3D"], scene["colors"], scene["opacities"], scene["scales"], scene["rotations"], scene["viewmatrix"],
-                        scene["beams"], W, H, bg=scene["bg"])
-    P = scene["means3D"].shape[0]
-    rs = restate(f, sr.restate(f, scene, W, H), gap)
-    idx, valid = pixel_lists(f, W, H)
-    vis = np.asarray(f.radii).reshape(-1) > 0
-    assert vis[idx[valid]].all()
-    remap = np.cumsum(vis) - 1                                               # Gaussian id -> row among the visible ones
-    leaf = lambda a: _t(a).requires_grad_(True)
-    means, scales, rots = leaf(scene["means3D"]), leaf(scene["scales"]), leaf(scene["rotations"])
-    opac, colors = leaf(scene["opacities"].reshape(-1)), leaf(scene["colors"])
-    sel = torch.as_tensor(np.nonzero(vis)[0])
-    k = pr.k1(means[sel], pr.cov6_of(scales[sel], rots[sel]), _t(np.asarray(scene["viewmatrix"]).reshape(16)))
-    rec = pr.record(k, damped=True)
-    e = torch.zeros(idx.shape + (2,), dtype=F64, requires_grad=True)
-    r = sr.blend(remap[idx], valid, _t(pr.pixel_dirs(W, H, scene["beams"]).reshape(-1, 3)), rec["conic"], opac[sel], colors[sel], k["dist"],
-                 k["u1"], k["u2"], k["dir"], _t(scene["bg"]), e)
-    # the float64 chain's own pick, on its own weights and ranges
-    t = r["table"]
-    I = t["idx"]
-    p = pick(t["weight"].numpy(), t["taken"].numpy(), t["pos"].numpy(), k["dist"].detach().numpy()[I.numpy()], gap_value(gap))
-    rows = torch.arange(I.shape[0])
-    has = torch.as_tensor(p["has"])
-    picked = I[rows, torch.as_tensor(p["pos2"])]
-    mine = np.where(p["has"], sel[picked].numpy(), -1)
-    same = mine == rs["second_id"].ravel()
-    assert same[rs["decided"].ravel()].all(), "the float64 chain and the oracle's float32 records disagree on a decided pixel"
-    depth = torch.where(has, k["dist"][picked], torch.zeros(I.shape[0], dtype=F64))
-    gc, gd, go = (_t(g) for g in grads)
-    gd_masked = gd.reshape(-1) * torch.as_tensor(rs["decided"].ravel() & same, dtype=F64)
-    loss = (r["color"].T.reshape(-1) * gc.reshape(-1)).sum() + (depth * gd_masked).sum() + (r["occ"] * go.reshape(-1)).sum()
-    gm, gs, gq, gop, gcol, ge = torch.autograd.grad(loss, [means, scales, rots, opac, colors, e])
-    g2 = np.zeros((P, 4))
-    pair = ge.numpy()
-    np.add.at(g2[:, 0], idx[valid], pair[valid][:, 0])
-    np.add.at(g2[:, 1], idx[valid], pair[valid][:, 1])
-    np.add.at(g2[:, 2], idx[valid], np.sqrt((pair[valid] ** 2).sum(-1)))      # the densification statistic: a sum of per-pixel norms
-    out = dict(rs)
-    out.update(fwd=f, depth=depth.detach().numpy().reshape(1, H, W),
-               dL_ddepth_masked=gd_masked.numpy().reshape(1, H, W).astype(np.float32), dL_dmeans3D=gm.numpy(), dL_dmeans2D=g2,
-               dL_dcolors=gcol.numpy(), dL_dopacity=gop.numpy().reshape(P, 1), dL_dscales=gs.numpy(), dL_drotations=gq.numpy())
-    return out
-
-
 # ---- the scenes of tests/test_second_depth_cpu.py and tests/test_second_depth_gpu.py ------------------------------------------------
 VEIL_N, VEIL_OP, LATE_N, LATE_OP, WALL = sr.VEIL_N, sr.VEIL_OP, sr.LATE_N, sr.LATE_OP, sr.WALL
 FAR_N, FAR_OP = 80, 0.005          # 80 layers behind a 0.5 surface: the wall behind them sits in the list's second 64-entry chunk
@@ -160,35 +122,38 @@ RAYS = {   # case: (x, y, [(range, opacity)]); W - 1 is written as -1
     "first column": (0, 6, [(12.0, 0.4), (18.0, 0.9)]),                 # (its footprint reaches over the seam into the last tile column)
 }
 NOTHING = (40, 13)
+# The worked-out answers (range in m; 0 = no second return) at G = 0 and G = 0.505, from the nominal alphas 0.995 x opacity:
+#   0.4/0.9              weights 0.40, 0.54: s = 20 m, the other is 10 m away
+#   split surface        weights 0.50, 0.30, 0.18: s = 10.00 m; its neighbour at 10.02 m, or past the gap the wall
+#   veil                 s = the wall (0.31); the layers' weights fall from 0.10: the first layer
+#   thin                 s = layer 0; weights fall: layer 1 (10.01 m), or the first layer past the gap (10.51 m)
+#   late wall            s = the wall (0.54, list position 100): layer 0
+#   far second           weights 0.4975, 80 layers of at most 0.0025, the wall 0.8955 x 0.5025 x 0.995^80 = 0.30: s = 10 m, and the wall is
+#                        the heaviest other entry at EITHER gap -- the rule's arithmetic, step 3.  (The layer at 10.01 m is the FIRST
+#                        candidate at G = 0: the second walk carries best2 = 0.0025 past list position 64 and must not leave before the wall.)
+ANSWERS = {"0.4/0.9": (10.0, 10.0), "split surface": (10.02, 20.0), "single": (0.0, 0.0), "pair inside the gap": (10.02, 0.0), "veil": (10.0, 10.0),
+           "thin": (10.01, 10.51), "late wall": (10.0, 10.0), "far second": (20.0, 20.0), "first column": (12.0, 12.0), "last column": (10.0, 10.0),
+           "nothing": (0.0, 0.0)}
 
 
 def placed(W, gap=None):
     """Hand-placed rays, laid out and sized as strongest_ref.placed's (SIGMA wide, OFF x SIGMA beside their pixel's centre: alpha =
     0.995 x opacity).  -> scene, {case: (x, y, range of the second return or 0, index of its Gaussian or -1)} for `gap`, {case: indices
     of the ray's Gaussians}.  The wanted answer is worked out here by the rule's arithmetic on the nominal alphas and ranges."""
-    from util import placed_scene
     G = gap_value(gap)
-    pc, py, dist, op, want, members = [], [], [], [], {}, {}
-    for case, (x, y, gs) in RAYS.items():
-        x = W - 1 if x < 0 else x
-        first = len(dist)
-        T, w = 1.0, []
-        for d, o in gs:
-            a = o * np.exp(-0.5 * OFF * OFF)
-            w.append(a * T)
-            T *= 1.0 - a
-            pc.append(x + OFF * SIGMA / (2 * np.pi / W)); py.append(float(y)); dist.append(d); op.append(o)
+    scene, first, members = dm.placed_layout(RAYS, W, SIGMA, OFF)
+    want = {}
+    for case, (_, _, gs) in RAYS.items():
+        w, T = sr.nominal_weights(gs)
         assert T >= 1e-4                                                  # (no ray reaches the blend's stop: every entry counts)
         s = max(range(len(gs)), key=lambda j: (w[j], -j))
         cand = [j for j in range(len(gs)) if j != s and abs(gs[j][0] - gs[s][0]) >= G]
         second = max(cand, key=lambda j: (w[j], -j)) if cand else -1
-        want[case] = (x, y, gs[second][0] if cand else 0.0, first + second if cand else -1)
-        members[case] = np.arange(first, len(dist))
+        x, y, base = first[case]
+        want[case] = (x, y, gs[second][0] if cand else 0.0, base + second if cand else -1)
     want["nothing"] = NOTHING + (0.0, -1)
     members["nothing"] = np.arange(0)
-    dist = np.array(dist)
-    sigma = np.sqrt((SIGMA * dist) ** 2 - 0.01)               # the 2-D covariance gets + 0.01 (R3/cr/forward.cu:166-167)
-    return placed_scene(pc, py, dist, sigma, op, W, H), want, members
+    return scene, want, members
 
 
 PLACED = ("second64", "second250", "second256")
@@ -215,7 +180,4 @@ def scene(name):
 
 
 def upstream(name):
-    """The upstream gradients (dL_dcolor [2,H,W], dL_ddepth [1,H,W], dL_docc [1,H,W]) the tests use for scene `name`: median_ref's and
-    strongest_ref's for their scenes (the float32 budget of BACKWARD_SCENES is asserted for exactly these), numbered on for this file's."""
-    import lidargs_scenes as sc
-    return sc.upstream_grads(H, scene(name)[1], 300 + SCENES.index(name))
+    return mr.upstream(name, SCENES, scene)

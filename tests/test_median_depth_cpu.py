@@ -1,22 +1,11 @@
 """LIDARGS_DEPTH=median without a GPU: the restatement (tests/median_ref.py) on rays whose answer is known by arithmetic, the cap on
-undecided pixels for every scene the GPU tests use, and the switch's parse rule through a probe of this test's own around csrc/switches.h."""
-import os
-import shutil
-import subprocess
-
+undecided pixels for every scene the GPU tests use, and the switch's parse rule through the probe around csrc/switches.h (tests/depth_modes.py)."""
 import numpy as np
 import pytest
 
+import depth_modes as dm
 import median_ref as mr
 from oracle import lgo
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "lidar-gs_amd", "csrc")
-
-
-def _forward(scene, W):
-    return lgo.forward(scene["means3D"], scene["colors"], scene["opacities"], scene["scales"], scene["rotations"], scene["viewmatrix"],
-                       scene["beams"], W, mr.H, bg=scene["bg"])
 
 
 @pytest.fixture(scope="module")
@@ -25,7 +14,7 @@ def restated():
     out = {}
     for name in mr.SCENES:
         scene, W = mr.scene(name)
-        f = _forward(scene, W)
+        f = dm.oracle_forward(scene, W)
         out[name] = (scene, W, f, mr.restate(f, scene, W, mr.H))
     return out
 
@@ -63,7 +52,7 @@ def test_restated_blend_is_the_oracles_and_undecided_pixels_stay_under_the_cap(n
     np.testing.assert_allclose(r["color"], f.color, rtol=0, atol=3e-5)
     np.testing.assert_allclose(r["expected"], f.depth[0], rtol=3e-5, atol=3e-4)
     np.testing.assert_allclose(r["occ"], f.occ[0], rtol=0, atol=3e-5)
-    frac = mr.undecided_fraction(r)
+    frac = dm.undecided_fraction(r)
     print(f"{name}: {int(r['has_taker'].sum())} pixels with a taker, {int(r['crossed'].sum())} cross one half, undecided {frac:.4f}")
     assert r["has_taker"].sum() >= 20 and frac <= mr.CAP
     # a median is a taker in front of the crossing: its range is never behind the expected range's farthest contributor
@@ -79,7 +68,7 @@ def test_random_scenes_exercise_the_rule(restated):
         assert r["crossed"].sum() >= 50 and (r["has_taker"] & ~r["crossed"]).sum() >= 10, name
         assert (np.abs(r["median_depth"] - r["expected"])[r["has_taker"]] > 1.0).sum() >= 20, name
     assert any((~restated[n][3]["has_taker"]).sum() >= 10 for n in mr.RANDOM)
-    assert any(mr.pixel_lists(restated[n][2], restated[n][1], mr.H)[1].sum(1).max() > 64 for n in mr.RANDOM)
+    assert any(dm.pixel_lists(restated[n][2], restated[n][1], mr.H)[1].sum(1).max() > 64 for n in mr.RANDOM)
 
 
 def _conforming_evaluations(scene, W, grads):
@@ -111,7 +100,7 @@ def _evaluations_over_the_budget(name, restated):
     scene, W, f, _ = restated[name]
     gc, gd, go = mr.upstream(name)
     nodepth = (gc, np.zeros_like(gd), go)
-    ref = mr.reference(scene, W, mr.H, nodepth, f=f)
+    ref = dm.reference(scene, W, mr.H, nodepth, mr.RULE, f=f)
     missed = []
     for what, r in _conforming_evaluations(scene, W, nodepth):
         for k in GRAD_KEYS_SR:
@@ -148,7 +137,7 @@ def test_reference_gradient_of_the_depth_lands_on_the_median_gaussian(restated):
     scene, W, f, r = restated[name]
     rng = np.random.default_rng(5)
     gd = rng.normal(size=(1, mr.H, W)).astype(np.float32)
-    ref = mr.reference(scene, W, mr.H, (np.zeros((2, mr.H, W), np.float32), gd, np.zeros((1, mr.H, W), np.float32)), f=f)
+    ref = dm.reference(scene, W, mr.H, (np.zeros((2, mr.H, W), np.float32), gd, np.zeros((1, mr.H, W), np.float32)), mr.RULE, f=f)
     P = scene["means3D"].shape[0]
     want = np.zeros(P)
     ok = r["decided"] & (r["median_id"] >= 0)
@@ -161,31 +150,15 @@ def test_reference_gradient_of_the_depth_lands_on_the_median_gaussian(restated):
         assert np.abs(ref[k]).max() == 0.0, k
 
 
-PROBE = r"""
-#include <stdio.h>
-#include "switches.h"
-int main() { printf("%d\n", lg::median_depth_requested() ? 1 : 0); return 0; }
-"""
-
-
-@pytest.mark.parametrize("value, want", [(None, "0"), ("", "0"), ("median", "1"), ("Median", "0"), ("1", "0"), ("median ", "0"), ("expected", "0")],
+@pytest.mark.parametrize("value", [None, "", "median", "Median", "1", "median ", "expected"],
                          ids=["unset", "empty", "median", "Median", "1", "trailing blank", "expected"])
-def test_the_switch_parses_as_specified(value, want, tmp_path_factory):
+def test_the_switch_parses_as_specified(value, tmp_path_factory):
     """Only the literal `median` turns the mode on; the header compiles as a plain C++ program under -Wall -Wextra -Werror."""
-    gxx = shutil.which("g++")
-    if not gxx:
+    exe = dm.build_probe(tmp_path_factory)
+    if not exe:
         pytest.skip("no g++")
-    d = tmp_path_factory.getbasetemp() / "median_probe"
-    exe = str(d / "probe")
-    if not os.path.exists(exe):
-        d.mkdir(exist_ok=True)
-        (d / "probe.cpp").write_text(PROBE)
-        subprocess.run([gxx, "-std=c++17", "-Wall", "-Wextra", "-Werror", "-O1", "-I", CSRC, str(d / "probe.cpp"), "-o", exe], check=True)
-    env = {k: v for k, v in os.environ.items() if k != "LIDARGS_DEPTH"}
-    if value is not None:
-        env["LIDARGS_DEPTH"] = value
-    r = subprocess.run([exe], env=env, capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0 and r.stdout.strip() == want, (value, r.stdout, r.stderr)
+    assert dm.DEPTH_CASES[value] == ("median" if value == "median" else "expected")
+    assert dm.probe(exe, value, None)[0] == dm.DEPTH_CASES[value], value
 
 
 def test_depth_mode_of_the_python_package(monkeypatch):

@@ -1,24 +1,12 @@
 """LIDARGS_DEPTH=strongest without a GPU: the restatement (tests/strongest_ref.py) on rays whose answer is known by arithmetic, the cap
-on undecided pixels for every scene the GPU tests use, the bound the kernel's early exit rests on, and the switch's parse rule through a
-probe of this test's own around csrc/switches.h."""
-import os
-import shutil
-import subprocess
-
+on undecided pixels for every scene the GPU tests use, the bound the kernel's early exit rests on, and the switch's parse rule through the
+probe around csrc/switches.h (tests/depth_modes.py)."""
 import numpy as np
 import pytest
 
+import depth_modes as dm
 import median_ref as mr
 import strongest_ref as sr
-from oracle import lgo
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "lidar-gs_amd", "csrc")
-
-
-def _forward(scene, W):
-    return lgo.forward(scene["means3D"], scene["colors"], scene["opacities"], scene["scales"], scene["rotations"], scene["viewmatrix"],
-                       scene["beams"], W, sr.H, bg=scene["bg"])
 
 
 @pytest.fixture(scope="module")
@@ -27,7 +15,7 @@ def restated():
     out = {}
     for name in sr.SCENES:
         scene, W = sr.scene(name)
-        f = _forward(scene, W)
+        f = dm.oracle_forward(scene, W)
         out[name] = (scene, W, f, sr.restate(f, scene, W, sr.H), mr.restate(f, scene, W, sr.H))
     return out
 
@@ -78,7 +66,7 @@ def test_restated_blend_is_the_oracles_and_undecided_pixels_stay_under_the_cap(n
     np.testing.assert_allclose(r["color"], f.color, rtol=0, atol=3e-5)
     np.testing.assert_allclose(r["expected"], f.depth[0], rtol=3e-5, atol=3e-4)
     np.testing.assert_allclose(r["occ"], f.occ[0], rtol=0, atol=3e-5)
-    frac = sr.undecided_fraction(r)
+    frac = dm.undecided_fraction(r)
     print(f"{name}: {int(r['has_taker'].sum())} pixels with a taker, undecided {frac:.4f}")
     assert r["has_taker"].sum() >= 20 and frac <= sr.CAP
     has = r["strongest_id"] >= 0
@@ -114,32 +102,15 @@ def test_nothing_behind_the_exit_can_win(name, restated):
     assert (t["pos"][rows] <= first).all()
 
 
-PROBE = r"""
-#include <stdio.h>
-#include "switches.h"
-int main() { printf("%d%d%d\n", lg::median_depth_requested() ? 1 : 0, lg::strongest_depth_requested() ? 1 : 0, lg::picked_depth_requested() ? 1 : 0); return 0; }
-"""
-
-
-@pytest.mark.parametrize("value, want", [(None, "000"), ("", "000"), ("strongest", "011"), ("median", "101"), ("Strongest", "000"), ("Median", "000"),
-                                         ("1", "000"), ("strongest ", "000"), ("expected", "000")],
+@pytest.mark.parametrize("value", [None, "", "strongest", "median", "Strongest", "Median", "1", "strongest ", "expected"],
                          ids=["unset", "empty", "strongest", "median", "Strongest", "Median", "1", "trailing blank", "expected"])
-def test_the_switch_parses_as_specified(value, want, tmp_path_factory):
+def test_the_switch_parses_as_specified(value, tmp_path_factory):
     """Only the literals `strongest` and `median` select a mode; the header compiles as a plain C++ program under -Wall -Wextra -Werror."""
-    gxx = shutil.which("g++")
-    if not gxx:
+    exe = dm.build_probe(tmp_path_factory)
+    if not exe:
         pytest.skip("no g++")
-    d = tmp_path_factory.getbasetemp() / "strongest_probe"
-    exe = str(d / "probe")
-    if not os.path.exists(exe):
-        d.mkdir(exist_ok=True)
-        (d / "probe.cpp").write_text(PROBE)
-        subprocess.run([gxx, "-std=c++17", "-Wall", "-Wextra", "-Werror", "-O1", "-I", CSRC, str(d / "probe.cpp"), "-o", exe], check=True)
-    env = {k: v for k, v in os.environ.items() if k != "LIDARGS_DEPTH"}
-    if value is not None:
-        env["LIDARGS_DEPTH"] = value
-    r = subprocess.run([exe], env=env, capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0 and r.stdout.strip() == want, (value, r.stdout, r.stderr)
+    assert dm.DEPTH_CASES[value] == (value if value in ("strongest", "median") else "expected")
+    assert dm.probe(exe, value, None)[0] == dm.DEPTH_CASES[value], value
 
 
 def test_depth_mode_of_the_python_package(monkeypatch):
